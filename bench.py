@@ -139,6 +139,34 @@ def emit(line):
         data = data[os.write(fd, data):]
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x4844
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float32 (bytes, verdicts and status codes are small integers, exact in float32).  The arrays
+    share their first axis (one row per batch or per blob).  Past DUMP_MAX_BYTES in all, the same fixed, seeded sample of rows is kept of each, in row
+    order, and sample_rows.npy (float64) names the rows; two runs with the same arguments sample the same rows."""
+    import numpy as np
+    arrays = {name: np.asarray(a).astype(np.float32) for name, a in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    assert all(len(a) == rows for a in arrays.values()), {name: a.shape for name, a in arrays.items()}
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(rows, 1)
+    keep = min(rows, DUMP_MAX_BYTES // (row_bytes + 8))
+    os.makedirs(path, exist_ok=True)
+    sample = os.path.join(path, "sample_rows.npy")
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        np.save(sample, idx.astype(np.float64))
+    elif os.path.exists(sample):
+        os.remove(sample)                                          # (left by an earlier, larger dump into the same directory)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    sys.stderr.write(f"bench.py: --dump-outputs: {', '.join(f'{n}{list(a.shape)}' for n, a in arrays.items())} -> {path}"
+                     + (f" ({keep} of {rows} rows)\n" if keep < rows else "\n"))
+
+
 def launcher_command(n, argv, port):
     """The command the driver itself uses for N > 1 (task statement): one rank per GPU under torch.distributed.run, rendezvous on 127.0.0.1."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
@@ -234,7 +262,14 @@ def main():
                          "runs); N = 1: the CPU all-threads trials, the mixed / mid-size legs.  config.skipped_for_time names what was dropped")
     ap.add_argument("--sweep", action="store_true",
                     help="criterion sweep: verify_blob_kzg_proof_batch for n in {1,..,64} and the five single-op benches, single calls on host inputs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32; verify: verdicts and status per "
+                         "batch, commit / proof: the 48-byte points and status per blob; past 64 MB a fixed, seeded sample of rows, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.sweep:
+        ap.error("--dump-outputs dumps the timed steps of the headline path; --sweep has none")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -254,7 +289,7 @@ def main():
         # test hook (tests/test_bench_launcher.py, no GPU): every rank reports how it was started; rank 0 prints the line
         if rank == 0:
             emit({"metric": "echo", "argv": sys.argv[1:], "world": world, "gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-                  "exchange": args.exchange, "master_addr": os.environ.get("MASTER_ADDR")})
+                  "exchange": args.exchange, "master_addr": os.environ.get("MASTER_ADDR"), "dump_outputs": args.dump_outputs})
         time.sleep(float(os.environ.get("KZG355_BENCH_ECHO_SLEEP", "0")))      # (test hook: ranks that stay up long enough to be interrupted)
         raise SystemExit(int(os.environ.get("KZG355_BENCH_ECHO_RC", "0")) if rank == world - 1 else 0)
     # Rehearsal hook (never set by the driver): KZG355_BENCH_FORCE_DIST=1 with one rank under torch.distributed.run makes the N = 1 run take the N > 1 code path --
@@ -263,9 +298,6 @@ def main():
     multi = world > 1 or (bool(os.environ.get("KZG355_BENCH_FORCE_DIST")) and "WORLD_SIZE" in os.environ)
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start N ranks with `python bench.py --gpus N` or torch.distributed.run --nproc-per-node N")
-    # 24 hardware queues instead of the HIP runtime's 4 (concurrent small calls are chains on several streams each): the variable
-    # belongs to the process and must be set before its first HIP call -- here, in front of torch -- since the library no longer sets it itself
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
     import torch
     import torch.distributed as dist
     if world > 1 and not os.environ.get("KZG355_BENCH_ONE_GPU") and torch.cuda.device_count() < world:
@@ -319,7 +351,7 @@ def main():
         s.free()
         return
 
-    K, W = max(1, args.steps), max(0, args.warmup)
+    K, W = args.steps, args.warmup
     skipped = []                                   # legs dropped for --max-seconds (config.skipped_for_time)
 
     def time_left():
@@ -375,6 +407,7 @@ def main():
 
     exchange_acc = {}                              # stage / exchange wall times of the sharded path, accumulated over the timed steps (this rank)
     mode_now = ["alltoall" if args.exchange == "both" else args.exchange]      # the exchange the sharded steps take right now
+    last_step = {}                                 # the buffers the latest step handed back, by reference (--dump-outputs copies them after the timed steps)
 
     def run_steps(g):
         """one launch set over g independent 64-blob batches; returns when the results are on the host."""
@@ -382,21 +415,37 @@ def main():
         if args.op == "commit":
             rc = L.kzg355_blob_to_kzg_commitment_many_device(out48, st, t_blobs.data_ptr(), nb, s.handle)
             assert rc == 0 and out48.raw[:48 * nb] == commitments[:48 * nb]
+            last_step.update(rows=nb, points=out48, status=st)
         elif args.op == "proof":
             rc = L.kzg355_compute_blob_kzg_proof_many_device(out48, st, t_blobs.data_ptr(), t_c.data_ptr(), nb, s.handle)
             assert rc == 0 and out48.raw[:48 * nb] == proofs[:48 * nb]
+            last_step.update(rows=nb, points=out48, status=st)
         elif not multi and args.host_inputs:
             rc = L.kzg355_verify_blob_kzg_proof_batch_many(ok, stg, h_blobs.ctypes.data_as(C.c_char_p), commitments, proofs, n_local, g, s.handle)
             assert rc == 0, rc
             assert bytes(ok)[:g] == b"\x01" * g, "a verification returned false on honest inputs"     # (one memcmp: a Python loop over 8192 verdicts costs ~1 ms per step)
+            last_step.update(rows=g, verdicts=ok, status=stg)
         elif not multi and not args.sharded_path:
             rc = L.kzg355_verify_blob_kzg_proof_batch_many_device(ok, stg, t_blobs.data_ptr(), t_c.data_ptr(), t_p.data_ptr(), n_local, g, s.handle)
             assert rc == 0, rc
             assert bytes(ok)[:g] == b"\x01" * g, "a verification returned false on honest inputs"     # (one memcmp: a Python loop over 8192 verdicts costs ~1 ms per step)
+            last_step.update(rows=g, verdicts=ok, status=stg)
         else:
             # stage 1 on the local shard -> ONE all-to-all of the 160-byte records + decoded points (RCCL over xGMI) -> stage 2 on this rank's share of the batches
             oks, sts = verify_blob_kzg_proof_batch_sharded(t_blobs[:nb * BLOB], t_c[:nb * 48], t_p[:nb * 48], n_local, g, engine, exchange=mode_now[0], timings=exchange_acc, force_exchange=multi and world == 1)
             assert all(oks) and not any(sts), "a verification returned false on honest inputs"
+            last_step.update(rows=g, verdicts=oks, status=sts)
+
+    def step_outputs():
+        """what the latest step handed its caller, copied out of the reused buffers (--dump-outputs)"""
+        import numpy as np
+        n = last_step["rows"]
+        if "points" in last_step:
+            out = {"commitments" if args.op == "commit" else "proofs": np.frombuffer(last_step["points"].raw[:48 * n], dtype=np.uint8).reshape(n, 48)}
+        else:
+            out = {"verdicts": np.array(last_step["verdicts"][:n], dtype=np.uint8)}
+        out["status"] = np.array(last_step["status"][:n], dtype=np.int64)
+        return out
 
     def barrier():
         torch.cuda.synchronize()
@@ -423,6 +472,7 @@ def main():
         rc = L.kzg355_verify_collect(tk, slot[0], slot[1])
         assert rc == 0, rc
         assert bytes(slot[0])[:Cc] == b"\x01" * Cc, "a verification returned false on honest inputs"
+        last_step.update(rows=Cc, verdicts=slot[0], status=slot[1])
         free_slots.append(slot)
 
     def step_pipelined():
@@ -494,7 +544,7 @@ def main():
             if cnt.value:
                 stats[fam] = (tot.value, cnt.value)
         return {"mode": mode, "dt": dt, "step_ms": step_ms, "power": power, "exchange_stats": exchange_stats, "stats": stats,
-                "blobs_per_s": K * Cc * n_local * world / dt}
+                "blobs_per_s": K * Cc * n_local * world / dt, "outputs": step_outputs() if args.dump_outputs else None}
 
     sharded = multi or args.sharded_path
     modes = ["allgather", "allgather_split", "alltoall"] if (sharded and args.exchange == "both" and args.op == "verify") else [mode_now[0]]
@@ -518,6 +568,8 @@ def main():
     best = max(runs.values(), key=lambda r: r["blobs_per_s"])
     dt, step_ms, power, exchange_stats, stats = best["dt"], best["step_ms"], best["power"], best["exchange_stats"], best["stats"]
     value_exchange = best["mode"] if sharded else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, best["outputs"])
 
     blobs_total = K * Cc * n_local * world
     value = blobs_total / dt

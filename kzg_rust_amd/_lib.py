@@ -31,9 +31,7 @@ def load():
     # /opt/rocm).  If torch is going to be used in this process (device tensors handed to the *_device entry points,
     # torch.distributed for the sharded path) it must be imported BEFORE libkzg355.so so that both bind to the same
     # runtime; loading ours first leaves torch unable to see the GPU.  Pure C / Rust consumers simply get /opt/rocm.
-    # (24 hardware queues instead of the HIP runtime's 4: concurrent small calls are chains on several streams each, csrc/engine.h.  The variable
-    # belongs to the process, so it is set HERE, before the first HIP call -- the library itself no longer touches the environment)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+    # (The hardware-queue count of the HIP runtime belongs to the process that runs this: neither this loader nor the library sets it; csrc/engine.h)
     if os.environ.get("KZG355_NO_TORCH_PRELOAD") != "1":
         try:
             import torch  # noqa: F401

@@ -52,9 +52,9 @@ namespace kzg355_impl { bool debug_errors(); bool debug_pipe(); }
 // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share a queue run one
 // after the other.  A small call of this library is a chain on three streams, so the default lets one such call run at full speed and
 // serialises the streams of concurrent ones (threads of n = 64 calls on one handle, median ms per call at 1 / 2 / 4 / 8 threads: 2.2 / 3.0 / 5.0 / 6.9
-// with 4 queues, 2.2 / 2.3 / 2.9 / 3.3 with 24; profiles/r04/concurrent_small_calls.txt).  The variable belongs to the PROCESS: a host that serves
-// concurrent small calls exports GPU_MAX_HW_QUEUES=24 before its first HIP call (kzg_rust_amd/_lib.py and bench.py do).  The library
-// does not touch the environment (round 4 set it from a constructor: ADVICE r4); it reads the variable once per handle and otherwise assumes 4.
+// with 4 queues, 2.2 / 2.3 / 2.9 / 3.3 with 24; profiles/r04/concurrent_small_calls.txt).  The variable belongs to the PROCESS and to whoever runs it
+// (INTEGRATION.md); neither the library nor its Python loader sets it (round 4 set it from a constructor: ADVICE r4).  The library reads the variable
+// once per handle and otherwise assumes 4.
 
 
 namespace kzg355_impl {

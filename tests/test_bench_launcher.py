@@ -168,3 +168,87 @@ def test_an_interrupted_launcher_takes_its_ranks_with_it(tmp_path):
     assert p.returncode != 0
     for k in kids:                                                 # the torch.distributed.run child is gone when the launcher returns
         assert not os.path.exists(f"/proc/{k}") or open(f"/proc/{k}/stat").read().split()[2] == "Z", k
+
+
+def test_steps_below_one_is_an_error_not_a_silent_one():
+    """--steps sets the number of timed steps: a value it cannot honour is refused before anything runs"""
+    for args in (["--steps", "0"], ["--steps", "-2"], ["--warmup", "-1"]):
+        r = run(["--gpus", "1"] + args)
+        assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, (args, r.stderr[-1500:])
+        assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_reaches_the_ranks():
+    r = run(["--gpus", "2", "--steps", "2", "--dump-outputs", "out_dir"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip())
+    assert line["dump_outputs"] == "out_dir" and line["steps"] == 2
+
+
+def test_dump_outputs_writes_float32_arrays_exactly(tmp_path):
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    pts = rng.integers(0, 256, size=(300, 48), dtype=np.uint8)
+    status = rng.integers(0, 5, size=300)
+    (tmp_path / "sample_rows.npy").write_bytes(b"stale")
+    bench.dump_outputs(str(tmp_path / "d"), {"commitments": pts, "status": status})
+    bench.dump_outputs(str(tmp_path), {"commitments": pts, "status": status})
+    for d in (tmp_path / "d", tmp_path):
+        got = np.load(d / "commitments.npy"), np.load(d / "status.npy")
+        assert got[0].dtype == np.float32 and got[1].dtype == np.float32
+        assert np.array_equal(got[0], pts) and np.array_equal(got[1], status)
+    assert not (tmp_path / "sample_rows.npy").exists() and not (tmp_path / "d" / "sample_rows.npy").exists()
+
+
+def test_dump_outputs_of_a_large_step_is_a_fixed_sample_within_64_mb(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    pts = np.arange(1000 * 48).reshape(1000, 48) % 251
+    status = np.arange(1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"proofs": pts, "status": status})
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["proofs.npy", "sample_rows.npy", "status.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 4096 + 3 * 128      # (+ the .npy headers)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 4096 // (49 * 4 + 8) and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "proofs.npy"), pts[idx]) and np.array_equal(np.load(tmp_path / "a" / "status.npy"), status[idx])
+    for f in files:                                                # the same rows from run to run
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+def test_the_state_main_shares_with_its_steps_is_bound_once():
+    """main()'s nested functions (run_steps, collect_oldest, timed_region, ...) keep state in containers of main's scope and fill them through methods
+    (x.update / x.append / x.pop / x.clear).  Rebinding such a name anywhere else in main() hands the next step the new object instead -- and only runs
+    that time a second exchange form reach the next step after the loop that rebinds, so no single-form run would show it."""
+    import ast
+    import bench
+    main = next(n for n in ast.parse(open(bench.__file__).read()).body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    funcs = (ast.FunctionDef, ast.AsyncFunctionDef, ast.Lambda)
+
+    def own_nodes(fn):                                             # fn's body without the bodies of the functions nested in it
+        todo = list(ast.iter_child_nodes(fn))
+        while todo:
+            n = todo.pop()
+            yield n
+            if not isinstance(n, funcs):
+                todo.extend(ast.iter_child_nodes(n))
+
+    def stores(fn):
+        names = [n.id for n in own_nodes(fn) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Store)]
+        return names + [n.name for n in own_nodes(fn) if isinstance(n, funcs[:2])]
+
+    shared = set()
+    for fn in (n for n in ast.walk(main) if isinstance(n, funcs[:2]) and n is not main):
+        local = set(stores(fn)) | {a.arg for a in fn.args.args}
+        for n in own_nodes(fn):
+            if (isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and isinstance(n.func.value, ast.Name)
+                    and n.func.attr in ("update", "append", "pop", "clear", "extend", "setdefault") and n.func.value.id not in local):
+                shared.add(n.func.value.id)
+    in_main = stores(main)
+    assert {"last_step", "pending", "exchange_acc"} <= shared, shared
+    assert {name: in_main.count(name) for name in shared if in_main.count(name) != 1} == {}

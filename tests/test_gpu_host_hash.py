@@ -196,8 +196,12 @@ def test_four_threads_of_reference_shaped_calls_all_take_the_host_route(kz, sett
     """no concurrency cliff on the small-call route.  Four threads x 20 verify_blob_kzg_proof_batch(n = 64) calls on host
     slices (the reference bench's call shape, benches/kzg_benches.rs:113-120) on ONE handle: every call has its challenges hashed on the host
     (round 3: one hashing slot per handle -- the second simultaneous caller took the 3.7 ms device hash and a 6 ms call), every verdict is true,
-    and the median call of every thread stays below 3.5 ms (each call is a ~2.2 ms chain of small kernels on three streams of its own workspace; the
-    library asks the HIP runtime for 24 hardware queues instead of its default 4, so that the chains of concurrent calls do not queue behind each other).  z of a call made WHILE the other threads are hashing is byte-exact against the oracle."""
+    and the calls do not queue behind each other beyond what the process's hardware queues impose.  Each call is a ~2.2 ms chain of small kernels on
+    three streams of its own workspace, and the library gives a call its side streams only while the process's hardware queues (GPU_MAX_HW_QUEUES,
+    set by whoever starts the process, csrc/engine.h) leave room for them.  With room for all four calls (3 x 4 queues or more) the median call of every
+    thread stays below 3.5 ms; with fewer queues the runtime serialises the chains that share a queue, and the four threads together must still
+    finish their 80 calls in at most 0.8 of the time one thread takes for the same calls back to back on the same handle.  z of a call made WHILE the other threads are
+    hashing is byte-exact against the oracle."""
     import ctypes as C
     import time
     blobs, cs, ps = batch
@@ -207,8 +211,13 @@ def test_four_threads_of_reference_shaped_calls_all_take_the_host_route(kz, sett
     for _ in range(3):                                   # warm the workspaces of one call
         ok = C.c_bool()
         assert L.kzg355_verify_blob_kzg_proof_batch(C.byref(ok), flat_b, n, flat_c, n, flat_p, n, settings.handle) == 0 and ok.value
-    before = settings.host_hashed_calls
     T, R = 4, 20
+    one = []                                             # the same call back to back on one thread: the yardstick of the serialised case
+    for _ in range(R):
+        t0 = time.perf_counter()
+        assert L.kzg355_verify_blob_kzg_proof_batch(C.byref(ok), flat_b, n, flat_c, n, flat_p, n, settings.handle) == 0 and ok.value
+        one.append((time.perf_counter() - t0) * 1e3)
+    before = settings.host_hashed_calls
     times = [[] for _ in range(T)]
     errors = []
     gate = threading.Barrier(T + 1)
@@ -227,9 +236,11 @@ def test_four_threads_of_reference_shaped_calls_all_take_the_host_route(kz, sett
     for t in th:
         t.start()
     gate.wait()
+    t0 = time.perf_counter()
     rc, okl, st, rec = _records(kz, settings, blobs, cs, ps, 8, 1)      # a fifth caller in the middle of it, records read back
     for t in th:
         t.join()
+    wall_ms = (time.perf_counter() - t0) * 1e3
     assert not errors, errors
     assert settings.host_hashed_calls - before == T * R + 1, "a call fell back to the device hash"
     assert rc == 0 and okl == [True]
@@ -238,9 +249,17 @@ def test_four_threads_of_reference_shaped_calls_all_take_the_host_route(kz, sett
     med = [sorted(t)[len(t) // 2] for t in times]
     allt = sorted(x for t in times for x in t)
     p80 = allt[int(0.8 * len(allt))]                     # (a few calls create workspaces: the first time four calls really overlap)
-    print(f"4 threads x 20 calls of n = 64: median per thread {[round(m, 2) for m in med]} ms, 80th percentile of all calls {p80:.2f} ms")
-    assert max(med) <= 3.5, med                           # measured 2.4-2.5 (profiles/r04/concurrent_small_calls.txt); round 3: 6.8
-    assert p80 <= 4.5, p80
+    one_med = sorted(one)[len(one) // 2]
+    q = int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0)
+    queues = q if 1 <= q <= 128 else 4                   # as the library reads it (csrc/options.hip)
+    print(f"4 threads x 20 calls of n = 64 on {queues} hardware queues: median per thread {[round(m, 2) for m in med]} ms, 80th percentile of all calls "
+          f"{p80:.2f} ms, {wall_ms:.1f} ms in all; one thread: {one_med:.2f} ms per call")
+    if queues >= 3 * T:
+        assert max(med) <= 3.5, med                       # measured 2.4-2.5 with 24 queues (profiles/r04/concurrent_small_calls.txt); round 3: 6.8
+        assert p80 <= 4.5, p80
+    else:
+        # measured on 2 queues (MI355X): 158 ms for the 80 calls against 251 ms back to back (3.14 ms per call), 0.63 of it
+        assert wall_ms <= 0.8 * T * R * one_med, (wall_ms, T * R * one_med, med)
 
 
 def test_explicit_options_ignore_the_environment(kz, setup_bytes, batch, monkeypatch):

@@ -8,7 +8,6 @@ usage: exp_clock_per_kernel.py [steps]"""
 import ctypes as C, glob, os, statistics, sys, threading, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 import torch
 import kzg_rust_amd as kz
 from synth import random_blob

@@ -4,7 +4,6 @@ in HBM, with the blobs copied back and hashed on the host threads (host_hash_dev
 Median ms per call over 12 calls after 3 warm-ups.  usage: exp_device_host_hash_crossover.py"""
 import ctypes as C, os, statistics, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 import torch
 import kzg_rust_amd as kz
 from synth import random_blob
