@@ -39,6 +39,10 @@ extern "C" {
 #define KZG355_BYTES_PER_G2 96              /* src/consts.rs:34 */
 #define KZG355_NUM_G2_POINTS 65             /* src/consts.rs:37 */
 #define KZG355_BYTES_PER_RECORD 160         /* C(48) | z(32) | y(32) | proof(48): one r-transcript record, utils.rs:454-463 */
+/* EIP-7594 (PeerDAS) cells: 64 field elements of a blob's 2x Reed-Solomon extension */
+#define KZG355_BYTES_PER_CELL 2048
+#define KZG355_FIELD_ELEMENTS_PER_CELL 64
+#define KZG355_CELLS_PER_EXT_BLOB 128
 
 enum {
     KZG355_OK = 0,
@@ -328,6 +332,26 @@ int kzg355_debug_verify_host_records(uint8_t *records_out /* groups*n_per_group*
 int kzg355_debug_verify_sharded_intermediates(uint8_t *out /* groups*128, host */, bool *ok /* groups */, int *status /* groups or NULL */,
                                               const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t n_per_group, size_t groups,
                                               const kzg355_settings *s);
+/* ---- EIP-7594 cell proofs ---------------------------------------------------------------------------------------------------------------------
+ * verify_cell_kzg_proof_batch of the consensus specs (fulu/polynomial-commitments-sampling.md; c-kzg-4844 2.x): n cells, each with its commitment
+ * (48 bytes), cell index (< 128), cell (2048 bytes: 64 big-endian field elements) and proof (48 bytes).  n == 0 -> true.  A cell index >= 128, a
+ * commitment or proof that fails validate_kzg_g1 or a cell element >= r -> KZG355_BADARGS.  The challenge r hashes the domain
+ * "RCKZGCBATCH__V1_", u64be(4096), u64be(64), u64be(#unique commitments), u64be(n), the unique commitments (first-appearance order), then per cell
+ * u64be(commitment position), u64be(cell index), cell, proof -- on host threads; everything else runs on the device.  Mainnet handles only (a
+ * handle of another FIELD_ELEMENTS_PER_BLOB -> KZG355_BADARGS); a handle over several devices runs these calls on its first device.  The first
+ * cell call of a handle derives what the check needs from the setup (the 64 monomial points [tau^t]_1 and the lines of setup g2[64]). */
+int kzg355_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments /* n*48 */, const size_t *cell_indices /* n */, const uint8_t *cells /* n*2048 */,
+                                       const uint8_t *proofs /* n*48 */, size_t n, const kzg355_settings *s);
+/* `groups` independent calls of the above in one set of launches (one verdict per data-column sidecar): the four arrays group-major, n_per_group
+ * cells each.  ok[g] / status[g] per group; the return value is the first non-OK status.  A refusal of the call as a whole marks every group. */
+int kzg355_verify_cell_kzg_proof_batch_many(bool *ok /* groups */, int *status /* groups or NULL */, const uint8_t *commitments, const size_t *cell_indices,
+                                            const uint8_t *cells, const uint8_t *proofs, size_t n_per_group, size_t groups, const kzg355_settings *s);
+/* Test form of the _many call: out[176 g ..] receives r (32 bytes, big-endian) | [I(tau)]_1 | LL | RL (48 bytes each, compressed) of group g. */
+int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *ok /* groups */, int *status /* groups or NULL */, const uint8_t *commitments,
+                                          const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t n_per_group, size_t groups,
+                                          const kzg355_settings *s);
+/* The 64 monomial points [tau^t]_1 (t < 64) the handle derived from its Lagrange setup, compressed (building them first if no cell call has). */
+int kzg355_debug_cell_setup_monomial(uint8_t *out /* 64*48 */, const kzg355_settings *s);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

@@ -88,6 +88,7 @@ using Bytes48 = FixedBytes<48, Error::InvalidBytesLength>;              // kzg.r
 using Blob = FixedBytes<BYTES_PER_BLOB, Error::InvalidBytesLength>;     // kzg.rs:154-178
 using KzgCommitment = Bytes48;                                          // kzg.rs:180-191
 using KzgProof = Bytes48;                                               // kzg.rs:193-204
+using Cell = FixedBytes<KZG355_BYTES_PER_CELL, Error::InvalidBytesLength>;   // EIP-7594 cell: 64 field elements
 
 // KzgSettings (kzg.rs:28-40): opaque device-resident handle, Drop frees it, shareable between threads
 class KzgSettings {
@@ -159,6 +160,23 @@ struct Kzg {
         bool ok = false;
         int rc = kzg355_verify_blob_kzg_proof_batch(&ok, b.data(), blobs.size(), c.data(), cs.size(), p.data(), ps.size(), s.raw());
         if (rc) return from_status(rc, "verify_blob_kzg_proof_batch");
+        return ok;
+    }
+
+    // EIP-7594 verify_cell_kzg_proof_batch (consensus specs fulu/polynomial-commitments-sampling.md; no reference counterpart)
+    static Result<bool> verify_cell_kzg_proof_batch(const std::vector<KzgCommitment> &cs, const std::vector<size_t> &cell_indices,
+                                                    const std::vector<Cell> &cells, const std::vector<KzgProof> &ps, const KzgSettings &s) {
+        const size_t n = cs.size();
+        if (cell_indices.size() != n || cells.size() != n || ps.size() != n) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<uint8_t> c(n * 48), cl(n * KZG355_BYTES_PER_CELL), p(n * 48);
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(&c[i * 48], cs[i].data(), 48);
+            std::memcpy(&cl[i * KZG355_BYTES_PER_CELL], cells[i].data(), KZG355_BYTES_PER_CELL);
+            std::memcpy(&p[i * 48], ps[i].data(), 48);
+        }
+        bool ok = false;
+        int rc = kzg355_verify_cell_kzg_proof_batch(&ok, c.data(), cell_indices.data(), cl.data(), p.data(), n, s.raw());
+        if (rc) return from_status(rc, "verify_cell_kzg_proof_batch");
         return ok;
     }
 

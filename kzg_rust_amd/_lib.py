@@ -43,6 +43,7 @@ def load():
         raise KzgLibraryMissing(f"cannot load {LIB_PATH}: {e}") from e
     vp, sz, u8p, ip = C.c_void_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_int)
     bp = C.POINTER(C.c_bool)
+    szp = C.POINTER(C.c_size_t)
     sigs = {
         "kzg355_load_trusted_setup": [u8p, sz, u8p, sz, C.POINTER(vp)],
         "kzg355_load_trusted_setup_file": [u8p, C.POINTER(vp)],
@@ -90,6 +91,10 @@ def load():
         "kzg355_settings_build_msm_table": [vp],
         "kzg355_verify_shard_records_points_words_device": [vp, vp, vp, vp, vp, vp, sz, sz, vp],
         "kzg355_verify_records_points_words_device": [vp, vp, vp, sz, sz, vp],
+        "kzg355_verify_cell_kzg_proof_batch": [bp, u8p, szp, u8p, u8p, sz, vp],
+        "kzg355_verify_cell_kzg_proof_batch_many": [bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
+        "kzg355_debug_cell_batch_intermediates": [u8p, bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
+        "kzg355_debug_cell_setup_monomial": [u8p, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -129,4 +134,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_shard_records_points_words_device", "kzg355_verify_records_points_words_device",
     "kzg355_verify_kzg_proof_many", "kzg355_verify_blob_kzg_proof_many", "kzg355_compute_kzg_proof_many", "kzg355_verify_kzg_proof_many_device",
     "kzg355_compute_kzg_proof_many_device", "kzg355_settings_host_threads",
+    "kzg355_verify_cell_kzg_proof_batch", "kzg355_verify_cell_kzg_proof_batch_many", "kzg355_debug_cell_batch_intermediates",
+    "kzg355_debug_cell_setup_monomial",
 ]

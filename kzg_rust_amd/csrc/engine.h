@@ -221,6 +221,15 @@ struct kzg355_settings {
     WidePub wide_store{};
     std::atomic<const WidePub *> wide_pub{nullptr};
     int wide_rc = KZG355_OK;                  // what building it returned (msm_require_wide: a failure fails the calls that need it)
+    // EIP-7594 cell calls (cells.hip): setup g2[64] = [tau^64]_2 as loaded (load validated it); what the check needs beyond the blob path -- the
+    // constants, the 64 monomial points [tau^t]_1 and a line table whose slot 2 holds the lines of [tau^64]_2 -- is built on the first cell call,
+    // under cell_mu, and `cell_t` is then the handle's tables with that line table in place of the blob path's
+    uint8_t g2_tau64[96] = {};
+    std::mutex cell_mu;
+    bool cell_ready = false;
+    int cell_rc = KZG355_OK;
+    DeviceTables cell_t{};
+    DevBuf cell_consts, cell_mono, cell_mono48, cell_lines, cell_lines_w, cell_lines_inf;
     bool timing = false;
     struct KStat { double last = -1, total = 0; long count = 0; };
     std::map<std::string, KStat> last_ms;

@@ -1,0 +1,232 @@
+// k_cells.hip -- verify_cell_kzg_proof_batch (EIP-7594 / PeerDAS, consensus specs fulu/polynomial-commitments-sampling.md) on the device.
+//
+// A cell is 64 field elements of a blob's 2x Reed-Solomon extension (8192 points).  With w = 7^((r-1)/8192) and brp the 13-bit bit-reversal
+// permutation of [w^0 .. w^8191], cell k holds the blob polynomial at brp[64k .. 64k+63]: element j sits at h_k * w64^rev6(j), where the coset
+// shift is h_k = w^rev7(k) and w64 = w^128.  The batch check of n cells with weights r^0 .. r^(n-1) (r from a host-hashed transcript) is
+//     e(LL, [tau^64]_2) == e(RL, G2),   LL = sum_k r^k pi_k,   RL = sum_i w_i C_i - [I(tau)]_1 + sum_k r^k h_k^64 pi_k,
+// I = sum_k r^k I_k with I_k the degree < 64 interpolant of cell k on its coset, computed per column c (cell index): the weighted cells of the
+// column are summed, the bit reversal undone, a 64-point inverse DFT taken and coefficient t multiplied by h_c^-t.
+//
+// Launch order of one call (cells.hip): decode + subgroup (k_g1.hip) | k_cell_rpowers -> k_cell_weights, k_cell_columns -> k_cell_interp ->
+// k_cell_terms -> k_cell_sum -> k_cell_finish -> launch_pairing with the [tau^64]_2 line set.  The lincomb is one double-and-add scalar
+// multiplication per term (255-bit scalars) and a tree per group and side: the 4844 lincomb families have their scalar layout baked in.
+#define KZG_FP_MUL_NOINLINE 1
+#include "kernels.h"
+
+namespace kzg {
+
+__device__ __forceinline__ uint32_t rev6(uint32_t j) { return __brev(j) >> 26; }
+__device__ __forceinline__ uint32_t rev7(uint32_t j) { return __brev(j) >> 25; }
+
+__device__ __forceinline__ Fr fr_pow_small(const Fr &base, uint32_t e) {
+    Fr acc = fr_one();
+    for (int b = 31; b >= 0; b--) {
+        fr_sqr(acc, acc);
+        if ((e >> b) & 1u) fr_mul(acc, acc, base);
+    }
+    return acc;
+}
+__device__ __forceinline__ void fr_store_words(uint32_t *dst, const Fr &a) {
+    uint32_t w[8]; fr_to_words(w, a);
+#pragma unroll
+    for (int i = 0; i < 8; i++) dst[i] = w[i];
+}
+
+// ---- setup (once per handle, on the first cell call)
+// thread c < 128: h_c^64 and the shifts h_c^-t / 64; threads < 64 also the inverse-DFT twiddles w64^-j
+__global__ void __launch_bounds__(128) k_cell_consts(CellConsts *cc) {
+    const int c = threadIdx.x;
+    const uint32_t wc[8] = {0xc78c8967u, 0x6fdd00bfu, 0x434906acu, 0x146b58bcu, 0x972e89edu, 0x2ccddea2u, 0x37b1da3du, 0x485d5127u};   // 7^((r-1)/8192)
+    Fr w; fr_from_words(w, wc);
+    const Fr h = fr_pow_small(w, rev7((uint32_t)c));
+    Fr h64 = h;
+    for (int i = 0; i < 6; i++) fr_sqr(h64, h64);
+    cc->h64[c] = h64;
+    Fr hinv, s, n64 = fr_zero();
+    fr_inv_fermat(hinv, h);
+    const Fr one = fr_one();
+    for (int i = 0; i < 64; i++) fr_add(n64, n64, one);
+    fr_inv_fermat(s, n64);
+    for (int t = 0; t < CELL_FE; t++) { cc->shift[c][t] = s; fr_mul(s, s, hinv); }
+    if (c < CELL_FE) {
+        Fr w64 = w;
+        for (int i = 0; i < 7; i++) fr_sqr(w64, w64);
+        Fr w64inv; fr_inv_fermat(w64inv, w64);
+        cc->tw[c] = fr_pow_small(w64inv, (uint32_t)c);
+    }
+}
+// scalars of the 64 "blobs" (w_i^t)_i whose commitments are the monomial points [tau^t]_1: roots is the bit-reversed blob domain
+__global__ void __launch_bounds__(256) k_cell_mono_scalars(const Fr *roots, Fr *out) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= CELL_FE * N_FE) return;
+    out[gid] = fr_pow_small(roots[gid % N_FE], (uint32_t)(gid / N_FE));
+}
+__global__ void __launch_bounds__(64) k_cell_decode_mono(const uint8_t *in48, G1Affine *mono, int *err) {
+    const int t = threadIdx.x;
+    uint8_t b[48];
+    for (int k = 0; k < 48; k++) b[k] = in48[48 * t + k];
+    G1Affine p;
+    if (g1_decompress(p, b) != 0) { atomicOr(err, ERR_SETUP_POINT); p = g1a_inf(); }
+    mono[t] = p;
+}
+// Miller-loop lines of setup g2[64] = [tau^64]_2 into slot 2 of a three-slot line table (the slot the pairing kernels pair the first point with)
+__global__ void __launch_bounds__(64) k_cell_lines(const uint8_t *g2_bytes, LineCoeff *lines, int *lines_inf, int *err) {
+    if (threadIdx.x != 0) return;
+    uint8_t b[96];
+    for (int k = 0; k < 96; k++) b[k] = g2_bytes[k];
+    G2Affine q;
+    if (g2_decompress(q, b) != 0) { atomicOr(err, ERR_SETUP_POINT); q.x = fp2_zero(); q.y = fp2_zero(); }
+    const bool inf = g2a_is_inf(q);
+    lines_inf[2] = inf ? 1 : 0;
+    if (!inf) precompute_lines(lines + 2 * N_LINES, q);
+}
+
+// ---- per call
+// thread (g, k): r of group g from its digest, r^k, and the two proof scalars: r^k (LL) and r^k h_k^64 (RL)
+__global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, const int *cell_idx, int npg, int groups, const CellConsts *cc, Fr *rpow,
+                                                      uint32_t *scal, uint8_t *r_out) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npg * groups) return;
+    const int g = gid / npg, k = gid % npg;
+    const int T = cell_terms(npg);
+    uint32_t w[8]; be32_to_words(w, digests + 32 * (size_t)g);
+    Fr r; fr_from_words(r, w);                                    // int(digest) mod r_BLS
+    if (k == 0) fr_to_be32(r_out + 32 * (size_t)g, r);
+    const Fr p = fr_pow_small(r, (uint32_t)k);
+    rpow[gid] = p;
+    Fr q; fr_mul(q, p, cc->h64[cell_idx[gid]]);
+    fr_store_words(scal + 8 * ((size_t)g * T + npg + k), q);
+    fr_store_words(scal + 8 * ((size_t)g * T + 2 * npg + CELL_FE + k), p);
+}
+// thread (g, i): weight of unique commitment i = sum of r^k over the cells that carry it (0 for the padding slots)
+__global__ void __launch_bounds__(256) k_cell_weights(const int *cidx, const Fr *rpow, int npg, int groups, uint32_t *scal) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= npg * groups) return;
+    const int g = gid / npg, i = gid % npg;
+    const int *ci = cidx + (size_t)g * npg;
+    const Fr *rp = rpow + (size_t)g * npg;
+    Fr acc = fr_zero();
+    for (int k = 0; k < npg; k++) if (ci[k] == i) fr_add(acc, acc, rp[k]);
+    fr_store_words(scal + 8 * ((size_t)g * cell_terms(npg) + i), acc);
+}
+// One workgroup per (group, column) segment: lane j sums r^k cell_k[j] over the segment's cells (bytes_to_bls_field on every element read,
+// error into the group's word), the sum goes to LDS at rev6(j) (undoing the bit reversal), then lane t takes coefficient t of the inverse DFT
+// (64 products against the twiddle table) times h_c^-t / 64.
+__global__ void __launch_bounds__(CELL_FE) k_cell_columns(const uint8_t *cells, const int *perm, const int4 *segs, const Fr *rpow, const CellConsts *cc,
+                                                          Fr *coef, int *err) {
+    __shared__ Fr u[CELL_FE], tw[CELL_FE];
+    const int4 sg = segs[blockIdx.x];                             // group, column, start, count
+    const int j = threadIdx.x;
+    tw[j] = cc->tw[j];
+    Fr acc = fr_zero();
+    bool bad = false;
+    for (int m = 0; m < sg.w; m++) {
+        const int k = perm[sg.z + m];                             // global cell number
+        Fr v;
+        bad |= !fr_from_be32_checked(v, cells + (size_t)CELL_BYTES * k + 32 * j);
+        fr_mul(v, v, rpow[k]);
+        fr_add(acc, acc, v);
+    }
+    if (bad) atomicOr(&err[sg.x], ERR_NONCANONICAL_FR);
+    u[rev6((uint32_t)j)] = acc;
+    __syncthreads();
+    Fr q = fr_zero();
+    for (int i = 0; i < CELL_FE; i++) { Fr t; fr_mul(t, u[i], tw[(i * j) & (CELL_FE - 1)]); fr_add(q, q, t); }
+    fr_mul(q, q, cc->shift[sg.y][j]);
+    coef[(size_t)blockIdx.x * CELL_FE + j] = q;
+}
+// one workgroup per group: I_t = sum over the group's segments; the scalar of monomial point t is -I_t
+__global__ void __launch_bounds__(CELL_FE) k_cell_interp(const Fr *coef, const int *gseg, int npg, uint32_t *scal) {
+    const int g = blockIdx.x, t = threadIdx.x;
+    Fr acc = fr_zero();
+    for (int s = gseg[g]; s < gseg[g + 1]; s++) fr_add(acc, acc, coef[(size_t)s * CELL_FE + t]);
+    Fr neg; fr_sub(neg, fr_zero(), acc);
+    fr_store_words(scal + 8 * ((size_t)g * cell_terms(npg) + 2 * npg + t), neg);
+}
+// thread (g, term): [scalar] point.  Terms of a group: [0, n) unique commitments, [n, 2n) proofs (RL), [2n, 2n + 64) monomial points,
+// [2n + 64, 3n + 64) proofs (LL).  pts is [group][commitments | proofs] as launch_decompress_points writes it.
+__global__ void __launch_bounds__(64) k_cell_terms(const G1Affine *pts, const G1Affine *mono, const uint32_t *scal, int npg, int groups, G1Jac *partials) {
+    const int T = cell_terms(npg);
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (size_t)T * groups) return;
+    const int g = (int)(gid / T), e = (int)(gid % T);
+    const G1Affine *gp = pts + (size_t)g * 2 * npg;
+    const G1Affine p = e < 2 * npg ? gp[e] : e < 2 * npg + CELL_FE ? mono[e - 2 * npg] : gp[npg + (e - 2 * npg - CELL_FE)];
+    uint32_t k[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = scal[8 * gid + i];
+    G1Jac r; g1_mul_words(r, p, k, 8);
+    partials[gid] = r;
+}
+// workgroup (g, side): side 0 = terms [0, 2n) (commitments, RL proofs), 1 = [2n, 2n + 64) (= -[I(tau)]), 2 = [2n + 64, 3n + 64) (LL)
+constexpr int CELL_SUM_THREADS = 256;
+__global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum(const G1Jac *partials, int npg, G1Jac *sums) {
+    __shared__ G1Jac red[CELL_SUM_THREADS];
+    const int g = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
+    const int T = cell_terms(npg);
+    const int lo = side == 0 ? 0 : side == 1 ? 2 * npg : 2 * npg + CELL_FE;
+    const int hi = side == 0 ? 2 * npg : side == 1 ? 2 * npg + CELL_FE : T;
+    G1Jac acc = g1_inf();
+    for (int e = lo + tid; e < hi; e += CELL_SUM_THREADS) g1_add(acc, acc, partials[(size_t)g * T + e]);
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = CELL_SUM_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) { G1Jac a = red[tid], b = red[tid + s]; g1_add(a, a, b); red[tid] = a; }
+        __syncthreads();
+    }
+    if (tid == 0) sums[3 * (size_t)g + side] = red[0];
+}
+// thread g: the pairing arguments (-LL, RL) and, with dbg, r | [I(tau)]_1 | LL | RL compressed (CELL_DEBUG_BYTES per group)
+__global__ void __launch_bounds__(64) k_cell_finish(const G1Jac *sums, int groups, const uint8_t *r_be, PairPt *pair_pts, uint8_t *dbg) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= groups) return;
+    const G1Jac a = sums[3 * (size_t)g], b = sums[3 * (size_t)g + 1], ll = sums[3 * (size_t)g + 2];
+    G1Jac rl; g1_add(rl, a, b);
+    pairpt_from_jac(pair_pts[2 * (size_t)g], ll, true);
+    pairpt_from_jac(pair_pts[2 * (size_t)g + 1], rl, false);
+    if (!dbg) return;
+    uint8_t *o = dbg + (size_t)CELL_DEBUG_BYTES * g;
+    for (int i = 0; i < 32; i++) o[i] = r_be[32 * (size_t)g + i];
+    G1Jac itau; g1_neg(itau, b);
+    const G1Jac *pts[3] = {&itau, &ll, &rl};
+    for (int q = 0; q < 3; q++) {
+        G1Affine p; g1_to_affine(p, *pts[q]);
+        uint8_t c[48]; g1_compress_affine(c, p);
+        for (int i = 0; i < 48; i++) o[32 + 48 * q + i] = c[i];
+    }
+}
+
+// ---- launchers
+void launch_cell_setup(const uint8_t *d_g2_tau64, DeviceTables t, CellConsts *d_cc, Fr *d_mono_scal, uint8_t *d_digits, G1Jac *d_partials,
+                       uint8_t *d_mono48, G1Affine *d_mono, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st) {
+    hipLaunchKernelGGL(k_cell_consts, dim3(1), dim3(CELLS_PER_EXT_BLOB), 0, st, d_cc);
+    hipLaunchKernelGGL(k_cell_mono_scalars, dim3(CELL_FE * N_FE / 256), dim3(256), 0, st, t.roots, d_mono_scal);
+    launch_digits_from_fr(d_mono_scal, CELL_FE, d_digits, st);
+    launch_msm_bucket(d_digits, t, CELL_FE, d_partials, st);
+    launch_msm_finalize(d_partials, CELL_FE, d_mono48, st);
+    hipLaunchKernelGGL(k_cell_decode_mono, dim3(1), dim3(CELL_FE), 0, st, d_mono48, d_mono, d_err);
+    hipLaunchKernelGGL(k_cell_lines, dim3(1), dim3(64), 0, st, d_g2_tau64, d_lines, d_lines_inf, d_err);
+}
+void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,
+                         uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st) {
+    const int n = npg * groups;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_cell_rpowers, dim3((n + 255) / 256), dim3(256), 0, st, d_digests, d_cell_idx, npg, groups, d_cc, d_rpow, d_scal, d_r_be);
+    hipLaunchKernelGGL(k_cell_weights, dim3((n + 255) / 256), dim3(256), 0, st, d_cidx, d_rpow, npg, groups, d_scal);
+}
+void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg, const Fr *d_rpow, const CellConsts *d_cc,
+                        int npg, int groups, Fr *d_coef, uint32_t *d_scal, int *d_err, hipStream_t st) {
+    if (groups <= 0) return;
+    if (n_segs > 0) hipLaunchKernelGGL(k_cell_columns, dim3(n_segs), dim3(CELL_FE), 0, st, d_cells, d_perm, d_segs, d_rpow, d_cc, d_coef, d_err);
+    hipLaunchKernelGGL(k_cell_interp, dim3(groups), dim3(CELL_FE), 0, st, d_coef, d_gseg, npg, d_scal);
+}
+void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
+                         const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st) {
+    if (groups <= 0) return;
+    const size_t terms = (size_t)cell_terms(npg) * groups;
+    hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 63) / 64)), dim3(64), 0, st, d_pts, d_mono, d_scal, npg, groups, d_partials);
+    hipLaunchKernelGGL(k_cell_sum, dim3(groups, 3), dim3(CELL_SUM_THREADS), 0, st, d_partials, npg, d_sums);
+    hipLaunchKernelGGL(k_cell_finish, dim3((groups + 63) / 64), dim3(64), 0, st, d_sums, groups, d_r_be, d_pair_pts, d_dbg);
+}
+
+}  // namespace kzg

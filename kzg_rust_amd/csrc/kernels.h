@@ -174,4 +174,34 @@ void launch_fr_from_bytes(const uint8_t *d_in32, int n, Fr *d_out, int *d_err /*
 void launch_fr_to_bytes(const Fr *d_in, int n, uint8_t *d_out32, hipStream_t st);
 void launch_status_words(const int *d_err, const int *d_ok /* or null */, int32_t *d_words, int groups, hipStream_t st);
 
+// ---- k_cells.hip: verify_cell_kzg_proof_batch (EIP-7594 cells of the 2x extended blob; mainnet handles only)
+constexpr int CELL_FE = 64;                // FIELD_ELEMENTS_PER_CELL
+constexpr int CELL_BYTES = CELL_FE * 32;   // BYTES_PER_CELL
+constexpr int CELLS_PER_EXT_BLOB = 128;
+constexpr int CELL_DEBUG_BYTES = 32 + 3 * 48;   // r | [I(tau)]_1 | LL | RL per group
+// lincomb terms of a group of n cells: n unique-commitment slots (padded), n proofs (RL), 64 monomial points, n proofs (LL)
+KZG_HD int cell_terms(int npg) { return 3 * npg + CELL_FE; }
+struct CellConsts {
+    Fr h64[CELLS_PER_EXT_BLOB];                // h_c^64, h_c = w^rev7(c), w = 7^((r-1)/8192)
+    Fr shift[CELLS_PER_EXT_BLOB][CELL_FE];     // h_c^-t / 64
+    Fr tw[CELL_FE];                            // w64^-j, w64 = w^128
+};
+// once per handle: the constants, the 64 monomial points [tau^t]_1 (8-bit fixed-base MSM over the Lagrange table; d_mono48 compressed, d_mono affine)
+// and the Miller-loop lines of setup g2[64] into slot 2 of d_lines / d_lines_inf.  Scratch: d_mono_scal 64 * 4096 Fr, d_digits 64 * 32 * 4096 bytes,
+// d_partials 64 * 32 G1Jac.
+void launch_cell_setup(const uint8_t *d_g2_tau64, DeviceTables t, CellConsts *d_cc, Fr *d_mono_scal, uint8_t *d_digits, G1Jac *d_partials,
+                       uint8_t *d_mono48, G1Affine *d_mono, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st);
+// r per group (from the host digests), r^k (d_rpow: npg * groups), the proof scalars and the unique-commitment weights into d_scal
+// ([group][cell_terms(npg)][8 words]); d_r_be: 32 bytes of r per group
+void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,
+                         uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st);
+// column sums, inverse DFT and shift per (group, column) segment (d_segs: group, column, first entry of d_perm, count), then I per group into d_scal;
+// d_coef: n_segs * 64 Fr; non-canonical cell elements set ERR_NONCANONICAL_FR in their group's d_err
+void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg /* groups + 1 */, const Fr *d_rpow,
+                        const CellConsts *d_cc, int npg, int groups, Fr *d_coef, uint32_t *d_scal, int *d_err, hipStream_t st);
+// the two sums per group -> d_pair_pts (-LL, RL); d_partials: cell_terms(npg) * groups G1Jac, d_sums: 3 * groups G1Jac; d_dbg (or null): CELL_DEBUG_BYTES
+// per group
+void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
+                         const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st);
+
 }  // namespace kzg

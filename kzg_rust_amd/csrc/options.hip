@@ -126,6 +126,7 @@ int load_on_device(const uint8_t *g1_bytes, size_t n1, const uint8_t *g2_bytes, 
     s->submit_mode = opt.submit_sets >= 0 && opt.submit_sets <= 2 ? opt.submit_sets : 0;
     if (hipMemcpy(g1b.p, g1_bytes, 48 * n1, hipMemcpyHostToDevice) != hipSuccess) return fail(KZG355_DEVICE_ERROR);
     if (hipMemcpy(g2b.p, g2_bytes, 96 * n2, hipMemcpyHostToDevice) != hipSuccess) return fail(KZG355_DEVICE_ERROR);
+    memcpy(s->g2_tau64, g2_bytes + 96 * (size_t)CELL_FE, 96);          // [tau^64]_2: the point cell proofs pair against (cells.hip)
     if (hipMemset(err.p, 0, sizeof(int)) != hipSuccess) return fail(KZG355_DEVICE_ERROR);
     if (small) launch_setup_small(g1b.as<uint8_t>(), (int)n1, s->t, err.as<int>(), nullptr);
     if (launch_setup(g1b.as<uint8_t>(), g2b.as<uint8_t>(), s->t, err.as<int>(), nullptr)) return fail(KZG355_DEVICE_ERROR);
@@ -280,6 +281,7 @@ void free_single(kzg355_settings *s) {
     delete s->host_pool; s->host_pool = nullptr;
     s->roots.release(); s->eval_tab.release(); s->wide.release(); s->msm_table.release(); s->lines.release(); s->lines_inf.release(); s->g1_first2.release();
     s->lines_w.release(); s->frob.release(); s->prog.release(); s->scheds.release();
+    for (DevBuf *b : {&s->cell_consts, &s->cell_mono, &s->cell_mono48, &s->cell_lines, &s->cell_lines_w, &s->cell_lines_inf}) b->release();
     delete s;
 }
 

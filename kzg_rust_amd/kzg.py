@@ -19,6 +19,10 @@ BYTES_PER_BLOB = 131072           # consts.rs:16
 BYTES_PER_G1 = 48                 # consts.rs:31
 BYTES_PER_G2 = 96                 # consts.rs:34
 TRUSTED_SETUP_NUM_G2_POINTS = 65  # consts.rs:37
+# EIP-7594 (PeerDAS) cells: 64 field elements of a blob's 2x Reed-Solomon extension
+FIELD_ELEMENTS_PER_CELL = 64
+BYTES_PER_CELL = 2048
+CELLS_PER_EXT_BLOB = 128
 
 
 class Error(Exception):
@@ -133,6 +137,11 @@ class Bytes48(_Fixed):
 class Blob(_Fixed):
     """kzg.rs:154-178 (mainnet preset: 4096 field elements; kzg_rust_amd.kzg_minimal.Blob is the 4-element one)."""
     SIZE = BYTES_PER_BLOB
+
+
+class Cell(_Fixed):
+    """One EIP-7594 cell: 64 big-endian field elements (2048 bytes)."""
+    SIZE = BYTES_PER_CELL
 
 
 class KzgCommitment(Bytes48):
@@ -436,3 +445,70 @@ class Kzg:
             _check(rc, "compute_kzg_proof_many")
         return [(KzgProof(out.raw[48 * i:48 * i + 48]), Bytes32(ys.raw[32 * i:32 * i + 32])) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("proof")
                 for i in range(n)]
+
+    # ---- EIP-7594 cell proofs (consensus specs fulu/polynomial-commitments-sampling.md; no reference counterpart) ----
+    @staticmethod
+    def _cell_arrays(commitments, cell_indices, cells, proofs):
+        cs = [_b(x, KzgCommitment) for x in commitments]
+        ix = [int(i) for i in cell_indices]
+        cl = [_b(x, Cell) for x in cells]
+        ps = [_b(x, KzgProof) for x in proofs]
+        if not (len(cs) == len(ix) == len(cl) == len(ps)):
+            raise BadArgs("length mismatch")
+        if any(i < 0 or i >= 1 << 64 for i in ix):
+            raise BadArgs("cell index out of range")
+        return cs, ix, cl, ps
+
+    @staticmethod
+    def verify_cell_kzg_proof_batch(commitments, cell_indices, cells, proofs, s):
+        """verify_cell_kzg_proof_batch: one commitment, cell index (< 128), cell and proof per cell; True / False, BadArgs on bad input."""
+        cs, ix, cl, ps = Kzg._cell_arrays(commitments, cell_indices, cells, proofs)
+        n = len(cs)
+        ok = C.c_bool()
+        idx = (C.c_size_t * max(n, 1))(*ix)
+        _check(lib().kzg355_verify_cell_kzg_proof_batch(C.byref(ok), b"".join(cs), idx, b"".join(cl), b"".join(ps), n, s.handle),
+               "verify_cell_kzg_proof_batch")
+        return bool(ok.value)
+
+    @staticmethod
+    def _cell_many(groups, s, debug):
+        if not groups:
+            return [], b""
+        npg = len(groups[0][0])
+        flat = [[], [], [], []]
+        for grp in groups:
+            arrs = Kzg._cell_arrays(*grp)
+            if len(arrs[0]) != npg:
+                raise BadArgs("all groups must have the same size")
+            for f, a in zip(flat, arrs):
+                f += a
+        G = len(groups)
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        idx = (C.c_size_t * max(len(flat[1]), 1))(*flat[1])
+        args = (ok, st, b"".join(flat[0]), idx, b"".join(flat[2]), b"".join(flat[3]), npg, G, s.handle)
+        out = C.create_string_buffer(176 * G) if debug else None
+        rc = lib().kzg355_debug_cell_batch_intermediates(out, *args) if debug else lib().kzg355_verify_cell_kzg_proof_batch_many(*args)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_cell_kzg_proof_batch_many")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_cell") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_cell_kzg_proof_batch_many(groups, s):
+        """groups: list of (commitments, cell_indices, cells, proofs), every group the same number of cells; one independent
+        verify_cell_kzg_proof_batch per group in one call.  Returns a list of bool / Error."""
+        return Kzg._cell_many(groups, s, False)[0]
+
+    @staticmethod
+    def debug_cell_batch_intermediates(groups, s):
+        """(verdicts as verify_cell_kzg_proof_batch_many, [r (32) | [I(tau)]_1 | LL | RL (48 each) per group])."""
+        res, raw = Kzg._cell_many(groups, s, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
+    def debug_cell_setup_monomial(s):
+        """The 64 monomial points [tau^t]_1 the handle derived for the cell check, compressed."""
+        out = C.create_string_buffer(64 * 48)
+        _check(lib().kzg355_debug_cell_setup_monomial(out, s.handle), "debug_cell_setup_monomial")
+        return [out.raw[48 * i:48 * i + 48] for i in range(64)]

@@ -11,3 +11,7 @@ pub const BYTES_PER_BLOB: usize = FIELD_ELEMENTS_PER_BLOB * BYTES_PER_FIELD_ELEM
 pub const BYTES_PER_G1: usize = 48;
 pub const BYTES_PER_G2: usize = 96;
 pub const TRUSTED_SETUP_NUM_G2_POINTS: usize = 65;
+// EIP-7594 (PeerDAS) cells of the 2x extended blob
+pub const FIELD_ELEMENTS_PER_CELL: usize = 64;
+pub const BYTES_PER_CELL: usize = 2048;
+pub const CELLS_PER_EXT_BLOB: usize = 128;

@@ -83,6 +83,11 @@ extern "C" {
                                               s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_blob_kzg_proof_batch_many(ok: *mut bool, status: *mut c_int, blobs: *const u8, commitments: *const u8, proofs: *const u8,
                                                    n_per_group: usize, groups: usize, s: *const kzg355_settings) -> c_int;
+    // EIP-7594 cells: commitments n*48, cell_indices n, cells n*2048, proofs n*48
+    pub fn kzg355_verify_cell_kzg_proof_batch(ok: *mut bool, commitments: *const u8, cell_indices: *const usize, cells: *const u8, proofs: *const u8, n: usize,
+                                              s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_verify_cell_kzg_proof_batch_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, cell_indices: *const usize, cells: *const u8,
+                                                   proofs: *const u8, n_per_group: usize, groups: usize, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_kzg_proof_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize,
                                         s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_blob_kzg_proof_many(ok: *mut bool, status: *mut c_int, blobs: *const u8, commitments: *const u8, proofs: *const u8, n: usize,

@@ -197,6 +197,32 @@ impl From<[u8; BYTES_PER_BLOB]> for Blob {
     }
 }
 
+/// One EIP-7594 cell: 64 big-endian field elements of the 2x extended blob.
+#[derive(Debug, Clone, PartialEq)]
+pub struct Cell {
+    bytes: Box<[u8; BYTES_PER_CELL]>,
+}
+impl Cell {
+    pub fn from_bytes(bytes: &[u8]) -> Result<Self, Error> {
+        if bytes.len() != BYTES_PER_CELL {
+            return Err(Error::InvalidBytesLength(format!("Invalid byte length. Expected {} got {}", BYTES_PER_CELL, bytes.len())));
+        }
+        let mut v = vec![0u8; BYTES_PER_CELL].into_boxed_slice();
+        v.copy_from_slice(bytes);
+        let bytes: Box<[u8; BYTES_PER_CELL]> = v.try_into().map_err(|_| Error::InternalError)?;
+        Ok(Self { bytes })
+    }
+    pub fn from_hex(hex_str: &str) -> Result<Self, Error> {
+        Self::from_bytes(&hex_to_bytes(hex_str)?)
+    }
+}
+impl Deref for Cell {
+    type Target = [u8; BYTES_PER_CELL];
+    fn deref(&self) -> &Self::Target {
+        &self.bytes
+    }
+}
+
 macro_rules! g1_newtype {
     ($name:ident, $n:expr) => {
         #[derive(Debug, Copy, Clone, PartialEq)]
@@ -358,6 +384,57 @@ impl Kzg {
         };
         whole_call(rc, &st[..groups], "verify_blob_kzg_proof_batch_many")?;
         Ok((0..groups).map(|g| check(st[g], "verify").map(|_| ok[g])).collect())
+    }
+
+    /// EIP-7594 `verify_cell_kzg_proof_batch` (consensus specs fulu/polynomial-commitments-sampling.md): one commitment, cell index (< 128),
+    /// cell and proof per cell.
+    pub fn verify_cell_kzg_proof_batch(
+        commitments: &[KzgCommitment],
+        cell_indices: &[usize],
+        cells: &[Cell],
+        proofs: &[KzgProof],
+        s: &KzgSettings,
+    ) -> Result<bool, Error> {
+        let n = commitments.len();
+        if cell_indices.len() != n || cells.len() != n || proofs.len() != n {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let cl: Vec<u8> = cells.iter().flat_map(|x| x.iter().copied()).collect();
+        let p: Vec<u8> = proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = false;
+        check(
+            unsafe { ffi::kzg355_verify_cell_kzg_proof_batch(&mut ok, c.as_ptr(), cell_indices.as_ptr(), cl.as_ptr(), p.as_ptr(), n, s.raw) },
+            "verify_cell_kzg_proof_batch",
+        )?;
+        Ok(ok)
+    }
+
+    /// `groups` independent `verify_cell_kzg_proof_batch` calls of `n_per_group` cells each (inputs group-major): one verdict per sidecar.
+    pub fn verify_cell_kzg_proof_batch_many(
+        commitments: &[KzgCommitment],
+        cell_indices: &[usize],
+        cells: &[Cell],
+        proofs: &[KzgProof],
+        n_per_group: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let n = commitments.len();
+        if cell_indices.len() != n || cells.len() != n || proofs.len() != n || n_per_group == 0 || n % n_per_group != 0 {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let groups = n / n_per_group;
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let cl: Vec<u8> = cells.iter().flat_map(|x| x.iter().copied()).collect();
+        let p: Vec<u8> = proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_verify_cell_kzg_proof_batch_many(ok.as_mut_ptr(), st.as_mut_ptr(), c.as_ptr(), cell_indices.as_ptr(), cl.as_ptr(), p.as_ptr(),
+                                                         n_per_group, groups, s.raw)
+        };
+        whole_call(rc, &st[..groups], "verify_cell_kzg_proof_batch_many")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
     }
 
     /// `commitments.len()` independent `verify_kzg_proof` checks (one proof per call is what benches/kzg_benches.rs:70-81 times).
