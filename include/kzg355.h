@@ -352,6 +352,20 @@ int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *o
                                           const kzg355_settings *s);
 /* The 64 monomial points [tau^t]_1 (t < 64) the handle derived from its Lagrange setup, compressed (building them first if no cell call has). */
 int kzg355_debug_cell_setup_monomial(uint8_t *out /* 64*48 */, const kzg355_settings *s);
+/* compute_cells_and_kzg_proofs of the consensus specs: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their
+ * 128 proofs (FK20), in cell order.  Either output may be NULL (then that half is not computed; without proofs_out no proof setup is built),
+ * not both (KZG355_BADARGS).  A blob element >= r -> KZG355_BADARGS.  Mainnet handles only; a handle over several devices runs on its first
+ * device.  The first call that wants proofs derives the 4096 monomial points [tau^t]_1 and a fixed-base table (384 MiB) from the setup. */
+int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL */, uint8_t *proofs_out /* 128*48 or NULL */, const uint8_t *blob,
+                                        const kzg355_settings *s);
+/* n independent calls of the above (blobs n*131072 bytes): status[i] per blob; the return value is the first non-OK status.  n == 0 -> OK.  A
+ * refusal of the call as a whole marks every blob.  Large n runs in chunks inside the call. */
+int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out /* n*128*2048 or NULL */, uint8_t *proofs_out /* n*128*48 or NULL */,
+                                             int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
+/* Test form: the FK20 intermediates H_0 .. H_63 of each blob, compressed (H_e = sum_{m >= 64(e+1)} f_m [tau^(m - 64(e+1))]_1; H_63 = infinity). */
+int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
+/* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */
+int kzg355_debug_cell_setup_monomial_all(uint8_t *out /* 4096*48 */, const kzg355_settings *s);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

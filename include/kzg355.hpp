@@ -180,6 +180,19 @@ struct Kzg {
         return ok;
     }
 
+    // EIP-7594 compute_cells_and_kzg_proofs: the 128 cells of the blob's 2x extension and their 128 proofs, in cell order
+    static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cells_and_kzg_proofs(const Blob &blob, const KzgSettings &s) {
+        std::vector<uint8_t> c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48);
+        int rc = kzg355_compute_cells_and_kzg_proofs(c.data(), p.data(), blob.data(), s.raw());
+        if (rc) return from_status(rc, "compute_cells_and_kzg_proofs");
+        std::pair<std::vector<Cell>, std::vector<KzgProof>> out;
+        for (int k = 0; k < KZG355_CELLS_PER_EXT_BLOB; k++) {
+            out.first.push_back(Cell::from_bytes(&c[(size_t)k * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+            out.second.push_back(KzgProof::from_bytes(&p[(size_t)k * 48], 48).value());
+        }
+        return out;
+    }
+
     // ---- throughput extensions (no reference counterpart): many independent single-proof units per call; one Result per unit, an Err of the
     // call itself only for whole-call failures (no device, out of memory, a length mismatch)
     static bool whole_call_failed(int rc, const std::vector<int> &st) {

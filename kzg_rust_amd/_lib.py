@@ -95,6 +95,10 @@ def load():
         "kzg355_verify_cell_kzg_proof_batch_many": [bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
         "kzg355_debug_cell_batch_intermediates": [u8p, bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
         "kzg355_debug_cell_setup_monomial": [u8p, vp],
+        "kzg355_compute_cells_and_kzg_proofs": [u8p, u8p, u8p, vp],
+        "kzg355_compute_cells_and_kzg_proofs_many": [u8p, u8p, ip, u8p, sz, vp],
+        "kzg355_debug_cell_compute_h": [u8p, ip, u8p, sz, vp],
+        "kzg355_debug_cell_setup_monomial_all": [u8p, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -135,5 +139,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_kzg_proof_many", "kzg355_verify_blob_kzg_proof_many", "kzg355_compute_kzg_proof_many", "kzg355_verify_kzg_proof_many_device",
     "kzg355_compute_kzg_proof_many_device", "kzg355_settings_host_threads",
     "kzg355_verify_cell_kzg_proof_batch", "kzg355_verify_cell_kzg_proof_batch_many", "kzg355_debug_cell_batch_intermediates",
-    "kzg355_debug_cell_setup_monomial",
+    "kzg355_debug_cell_setup_monomial", "kzg355_compute_cells_and_kzg_proofs", "kzg355_compute_cells_and_kzg_proofs_many",
+    "kzg355_debug_cell_compute_h", "kzg355_debug_cell_setup_monomial_all",
 ]

@@ -1,0 +1,164 @@
+// cell_compute.hip -- the C entry points of compute_cells_and_kzg_proofs (EIP-7594 cells; include/kzg355.h) and the per-handle setup they need
+// (host side of libkzg355.so; see engine.h).  The host copies blobs in and cells / proofs out and sets the statuses; every field and group
+// operation runs in the kernels of k_cell_compute.hip, one set of launches per chunk of blobs.
+#include "engine.h"
+
+namespace kzg355_impl {
+
+static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
+
+// Constants of the field stage (w4096 powers, twiddle splits): the first compute call of a handle.  Under cc_mu.
+static int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
+    std::lock_guard<std::mutex> lk(s->cc_mu);
+    if (s->cc_consts_ready) return KZG355_OK;
+    int rc;
+    if ((rc = s->cc_consts.ensure(sizeof(CellComputeConsts)))) return rc;
+    launch_cc_consts(s->t.roots, s->cc_consts.as<CellComputeConsts>(), w->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(w->stream));
+    s->cc_consts_ready = true;
+    return KZG355_OK;
+}
+
+// The proof setup, on the first call that wants proofs (after ensure_cc_consts): the monomial points [tau^t]_1, t < 4096, as commitments of
+// the "blobs" (w_i^t)_i through the 8-bit fixed-base MSM, 64 at a time; X_r = NTT128(x_r) and their comb table.  Under cc_mu.
+static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
+    std::lock_guard<std::mutex> lk(s->cc_mu);
+    if (s->cc_proof_ready) return s->cc_proof_rc;
+    DevBuf scal, digits, partials, X, err;
+    auto done = [&](int rc) {
+        for (DevBuf *b : {&scal, &digits, &partials, &X, &err}) b->release();
+        if (rc == KZG355_NO_MEMORY) {                              // not remembered: a later call may find the memory
+            for (DevBuf *b : {&s->cc_mono48, &s->cc_mono, &s->cc_table}) b->release();
+            return rc;
+        }
+        s->cc_proof_ready = true;
+        s->cc_proof_rc = rc;
+        return rc;
+    };
+    int rc;
+    if ((rc = s->cc_mono48.ensure(48 * (size_t)N_FE)) || (rc = s->cc_mono.ensure(sizeof(G1Affine) * N_FE)) ||
+        (rc = s->cc_table.ensure(sizeof(G1Affine) * CC_TABLE_ENTRIES)) || (rc = scal.ensure(sizeof(Fr) * CELL_FE * N_FE)) ||
+        (rc = digits.ensure((size_t)CELL_FE * MSM_WINDOWS * N_FE)) || (rc = partials.ensure(sizeof(G1Jac) * CELL_FE * MSM_WINDOWS)) ||
+        (rc = X.ensure(sizeof(G1Jac) * CC_POINTS)) || (rc = err.ensure(sizeof(int))))
+        return done(rc);
+    hipStream_t st = w->stream;
+    auto hip_fail = [&]() { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return done(KZG355_DEVICE_ERROR); };
+    if (hipMemsetAsync(err.p, 0, sizeof(int), st) != hipSuccess) return hip_fail();
+    for (int t0 = 0; t0 < N_FE; t0 += CELL_FE)
+        launch_cc_monomial_chunk(s->t, t0, scal.as<Fr>(), digits.as<uint8_t>(), partials.as<G1Jac>(), s->cc_mono48.as<uint8_t>(), st);
+    launch_cc_setup_points(s->cc_mono48.as<uint8_t>(), s->cc_mono.as<G1Affine>(), s->cc_consts.as<CellComputeConsts>(), X.as<G1Jac>(),
+                           s->cc_table.as<G1Affine>(), err.as<int>(), st);
+    int herr = 0;
+    uint8_t first[48];
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(first, s->cc_mono48.p, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return hip_fail();
+    // [tau^0]_1 = sum_i [L_i(tau)]_1 = G1 whatever the ceremony
+    static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
+                                       0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
+                                       0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
+    if (herr || memcmp(first, G1_GEN, 48) != 0) return done(KZG355_INTERNAL);
+    return done(KZG355_OK);
+}
+
+// cells_out / proofs_out / h_dbg: host memory (any may be null, not all); status (or null): per blob.
+static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs) {
+    auto refuse = [&](int code) { if (status) for (size_t i = 0; i < n; i++) status[i] = code; return code; };
+    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return refuse(KZG355_BADARGS);
+    if (n == 0) return KZG355_OK;
+    if (!blobs) return refuse(KZG355_BADARGS);
+    if (n > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
+    if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
+    WsGuard g(cs);
+    if (!g.w) return refuse(KZG355_NO_DEVICE);
+    kzg355_settings *s = g.s; Workspace *w = g.w;
+    const bool want_proofs = proofs_out || h_dbg;
+    int rc;
+    if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
+    if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
+    const size_t CH = n < CC_CHUNK ? n : CC_CHUNK;
+    const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
+    // the workspace's buffers by role: blobs, y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H
+    if ((rc = w->blobs.ensure((size_t)BLOB_BYTES * CH)) || (rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
+        (cells_out && (rc = w->q.ensure(cell_bytes * CH))) ||
+        (want_proofs && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
+                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (rc = w->out48.ensure((size_t)48 * CC_FFT * CH)))) ||
+        (h_dbg && (rc = w->small.ensure((size_t)48 * CELL_FE * CH))))
+        return refuse(rc);
+    const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
+    hipStream_t st = w->stream;
+    Timed tm(s, w);
+    int first = KZG355_OK;
+    auto run = [&]() -> int {                                     // (HIPCHK returns from here: a failed chunk refuses the whole call)
+    for (size_t c0 = 0; c0 < n; c0 += CH) {
+        const int m = (int)(n - c0 < CH ? n - c0 : CH);
+        w->in_flight = true;
+        HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * m, st));
+        HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, st));
+        tm.begin("cc_field");
+        launch_cc_field(w->blobs.as<uint8_t>(), m, cc, want_proofs ? w->y.as<Fr>() : nullptr, cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), st);
+        tm.end();
+        if (want_proofs) {
+            tm.begin("cc_columns");
+            launch_cc_columns(w->y.as<Fr>(), m, cc, w->scal_a.as<uint32_t>(), st);
+            tm.end();
+            tm.begin("cc_msm");
+            launch_cc_msm(w->scal_a.as<uint32_t>(), m, s->cc_table.as<G1Affine>(), w->partials.as<G1Jac>(), st);
+            tm.end();
+            tm.begin("cc_proofs");
+            launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, w->out48.as<uint8_t>(), h_dbg ? w->small.as<uint8_t>() : nullptr, st);
+            tm.end();
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+        if (cells_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
+        if (proofs_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
+        if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        w->in_flight = false;
+        tm.collect();
+        for (int i = 0; i < m; i++) {
+            const int stt = status_from_err(w->h_err.as<int>()[i]);
+            if (status) status[c0 + i] = stt;
+            if (stt != KZG355_OK && first == KZG355_OK) first = stt;
+        }
+    }
+    return KZG355_OK;
+    };
+    if ((rc = run())) return refuse(rc);
+    return first;
+}
+
+}  // namespace kzg355_impl
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out, uint8_t *proofs_out, int *status, const uint8_t *blobs, size_t n,
+                                             const kzg355_settings *s) {
+    return cc_impl(cells_out, proofs_out, nullptr, status, blobs, n, s);
+}
+
+int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blob, const kzg355_settings *s) {
+    return cc_impl(cells_out, proofs_out, nullptr, nullptr, blob, 1, s);
+}
+
+int kzg355_debug_cell_compute_h(uint8_t *out, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *s) {
+    if (!out) return KZG355_BADARGS;
+    return cc_impl(nullptr, nullptr, out, status, blobs, n, s);
+}
+
+int kzg355_debug_cell_setup_monomial_all(uint8_t *out, const kzg355_settings *cs) {
+    if (!cs || !out) return KZG355_BADARGS;
+    if (is_small(cs)) return KZG355_BADARGS;
+    WsGuard g(cs);
+    if (!g.w) return KZG355_NO_DEVICE;
+    int rc;
+    if ((rc = ensure_cc_consts(g.s, g.w)) || (rc = ensure_cc_proof_setup(g.s, g.w))) return rc;
+    HIPCHK(hipMemcpy(out, g.s->cc_mono48.p, 48 * (size_t)N_FE, hipMemcpyDeviceToHost));
+    return KZG355_OK;
+}
+
+#pragma GCC visibility pop
+}  // extern "C"

@@ -230,6 +230,12 @@ struct kzg355_settings {
     int cell_rc = KZG355_OK;
     DeviceTables cell_t{};
     DevBuf cell_consts, cell_mono, cell_mono48, cell_lines, cell_lines_w, cell_lines_inf;
+    // compute_cells_and_kzg_proofs (cell_compute.hip): the field-stage constants, then -- first call that wants proofs -- the 4096 monomial points
+    // and the FK20 comb table (CC_TABLE_ENTRIES affine points), each built once under cc_mu; a NO_MEMORY failure is not remembered
+    std::mutex cc_mu;
+    bool cc_consts_ready = false, cc_proof_ready = false;
+    int cc_proof_rc = KZG355_OK;
+    DevBuf cc_consts, cc_mono48, cc_mono, cc_table;
     bool timing = false;
     struct KStat { double last = -1, total = 0; long count = 0; };
     std::map<std::string, KStat> last_ms;

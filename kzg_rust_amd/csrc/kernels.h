@@ -204,4 +204,29 @@ void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d
 void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
                          const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st);
 
+
+// ---- k_cell_compute.hip: compute_cells_and_kzg_proofs (the cells of the 2x extension and their proofs by FK20; mainnet handles only)
+constexpr int CC_FFT = 128;                                  // size of the circulant transforms (2 x 64)
+constexpr int CC_POINTS = CELL_FE * CC_FFT;                  // X_r[i]: the fixed-base points, 8192
+constexpr int CC_WINDOWS = 64, CC_DIGITS = 8;                // comb table: signed 4-bit digits, multiples 1..8 of 16^w X per window
+constexpr size_t CC_TABLE_ENTRIES = (size_t)CC_POINTS * CC_WINDOWS * CC_DIGITS;   // 4,194,304 affine points, 384 MiB
+struct CellComputeConsts {
+    Fr w4096[N_FE];                                          // w4096^e, natural order (w4096^-e = w4096[4096 - e])
+    Fr w8192, inv128, inv4096;                               // w = 7^((r-1)/8192), 1/128, 1/4096
+    uint32_t tw_a[CC_FFT][4], tw_b[CC_FFT][4];               // GLV halves of w128^e (w128 = w4096^32): w128^e = a + b x^2
+};
+void launch_cc_consts(const Fr *d_roots, CellComputeConsts *d_cc, hipStream_t st);
+// monomial points [tau^t]_1, t = t0 .. t0 + 63, compressed into d_out48 + 48 t0 (8-bit fixed-base MSM over the Lagrange table).  Scratch:
+// d_scal 64 * 4096 Fr, d_digits 64 * 32 * 4096 bytes, d_partials 64 * 32 G1Jac.
+void launch_cc_monomial_chunk(DeviceTables t, int t0, Fr *d_scal, uint8_t *d_digits, G1Jac *d_partials, uint8_t *d_out48, hipStream_t st);
+// the 4096 monomial points decoded (d_mono), X_r = NTT128(x_r) (d_X: CC_POINTS G1Jac) and the comb table (d_tab: CC_TABLE_ENTRIES)
+void launch_cc_setup_points(const uint8_t *d_mono48, G1Affine *d_mono, const CellComputeConsts *d_cc, G1Jac *d_X, G1Affine *d_tab, int *d_err,
+                            hipStream_t st);
+// per call: field stage (d_coef: n * 4096 Fr or null; d_cells: n * 128 * 2048 bytes or null; non-canonical elements -> ERR_NONCANONICAL_FR in d_err[blob]),
+// columns (d_scal: n * 128 * 64 * 8 words), fixed-base sums (d_Z: n * 128 G1Jac), G1 transforms (d_proofs48: n * 128 * 48; d_h_dbg: n * 64 * 48 or null)
+void launch_cc_field(const uint8_t *d_blobs, int n, const CellComputeConsts *d_cc, Fr *d_coef, uint8_t *d_cells, int *d_err, hipStream_t st);
+void launch_cc_columns(const Fr *d_coef, int n, const CellComputeConsts *d_cc, uint32_t *d_scal, hipStream_t st);
+void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *d_Z, hipStream_t st);
+void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
+
 }  // namespace kzg

@@ -282,6 +282,7 @@ void free_single(kzg355_settings *s) {
     s->roots.release(); s->eval_tab.release(); s->wide.release(); s->msm_table.release(); s->lines.release(); s->lines_inf.release(); s->g1_first2.release();
     s->lines_w.release(); s->frob.release(); s->prog.release(); s->scheds.release();
     for (DevBuf *b : {&s->cell_consts, &s->cell_mono, &s->cell_mono48, &s->cell_lines, &s->cell_lines_w, &s->cell_lines_inf}) b->release();
+    for (DevBuf *b : {&s->cc_consts, &s->cc_mono48, &s->cc_mono, &s->cc_table}) b->release();
     delete s;
 }
 

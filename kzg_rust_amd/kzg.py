@@ -512,3 +512,74 @@ class Kzg:
         out = C.create_string_buffer(64 * 48)
         _check(lib().kzg355_debug_cell_setup_monomial(out, s.handle), "debug_cell_setup_monomial")
         return [out.raw[48 * i:48 * i + 48] for i in range(64)]
+
+    # ---- EIP-7594 cells and cell proofs of a blob (compute_cells_and_kzg_proofs; FK20 on the device) ----
+    @staticmethod
+    def _compute_cells(blobs, s, cells, proofs):
+        bl = [_b(x, Blob) for x in blobs]
+        n = len(bl)
+        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(n, 1)) if cells else None
+        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1)) if proofs else None
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_compute_cells_and_kzg_proofs_many(c_out, p_out, st, b"".join(bl), n, s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "compute_cells_and_kzg_proofs")
+        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
+        praw = p_out.raw if proofs else b""
+        res = []
+        for i in range(n):
+            if st[i] != 0:
+                res.append(_ERRORS.get(st[i], InternalError)("compute_cells"))
+                continue
+            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
+            pb = 48 * CELLS_PER_EXT_BLOB * i
+            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
+                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
+        return res
+
+    @staticmethod
+    def _one(res):
+        if isinstance(res[0], Error):
+            raise res[0]
+        return res[0]
+
+    @staticmethod
+    def compute_cells(blob, s):
+        """The 128 cells of the blob's 2x extension (cells 0..63 are the blob itself); BadArgs on a field element >= r."""
+        return Kzg._one(Kzg._compute_cells([blob], s, True, False))[0]
+
+    @staticmethod
+    def compute_cells_and_kzg_proofs(blob, s):
+        """([Cell] * 128, [KzgProof] * 128) in cell order."""
+        return Kzg._one(Kzg._compute_cells([blob], s, True, True))
+
+    @staticmethod
+    def compute_kzg_cell_proofs(blob, s):
+        """The 128 cell proofs alone (the cells are not computed)."""
+        return Kzg._one(Kzg._compute_cells([blob], s, False, True))[1]
+
+    @staticmethod
+    def compute_cells_and_kzg_proofs_many(blobs, s):
+        """One independent compute_cells_and_kzg_proofs per blob in one call: a list of (cells, proofs) tuples or Error."""
+        return Kzg._compute_cells(blobs, s, True, True)
+
+    @staticmethod
+    def debug_cell_compute_h(blobs, s):
+        """FK20 intermediates per blob: H_0 .. H_63 compressed (H_63 is the point at infinity), or Error."""
+        bl = [_b(x, Blob) for x in blobs]
+        n = len(bl)
+        out = C.create_string_buffer(64 * 48 * max(n, 1))
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_debug_cell_compute_h(out, st, b"".join(bl), n, s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "debug_cell_compute_h")
+        raw = out.raw
+        return [[raw[48 * (64 * i + e):48 * (64 * i + e + 1)] for e in range(64)] if st[i] == 0 else _ERRORS.get(st[i], InternalError)("h")
+                for i in range(n)]
+
+    @staticmethod
+    def debug_cell_setup_monomial_all(s):
+        """The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed."""
+        out = C.create_string_buffer(4096 * 48)
+        _check(lib().kzg355_debug_cell_setup_monomial_all(out, s.handle), "debug_cell_setup_monomial_all")
+        return [out.raw[48 * i:48 * i + 48] for i in range(4096)]

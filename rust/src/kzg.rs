@@ -437,6 +437,40 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
     }
 
+    /// EIP-7594 `compute_cells_and_kzg_proofs`: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their 128 proofs,
+    /// in cell order (FK20 on the device).
+    pub fn compute_cells_and_kzg_proofs(blob: &Blob, s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
+        let mut res = Self::compute_cells_and_kzg_proofs_many(std::slice::from_ref(blob), s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// `blobs.len()` independent `compute_cells_and_kzg_proofs` calls in one set of launches; one `Result` per blob.
+    pub fn compute_cells_and_kzg_proofs_many(blobs: &[Blob], s: &KzgSettings) -> Result<Vec<Result<(Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let n = blobs.len();
+        let staged = stage_blobs(blobs);
+        let per_cells = BYTES_PER_CELL * CELLS_PER_EXT_BLOB;
+        let mut cells = vec![0u8; per_cells * n.max(1)];
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * n.max(1)];
+        let mut st = vec![0i32; n.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_compute_cells_and_kzg_proofs_many(cells.as_mut_ptr(), proofs.as_mut_ptr(), st.as_mut_ptr(), staged.as_ptr(), n, s.raw)
+        };
+        whole_call(rc, &st[..n], "compute_cells_and_kzg_proofs_many")?;
+        Ok((0..n)
+            .map(|i| {
+                check(st[i], "compute_cells")?;
+                let cs = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| Cell::from_bytes(&cells[per_cells * i + BYTES_PER_CELL * k..per_cells * i + BYTES_PER_CELL * (k + 1)]))
+                    .collect::<Result<Vec<_>, _>>()?;
+                let base = BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * i;
+                let ps = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[base + 48 * k..base + 48 * (k + 1)]).unwrap()))
+                    .collect();
+                Ok((cs, ps))
+            })
+            .collect())
+    }
+
     /// `commitments.len()` independent `verify_kzg_proof` checks (one proof per call is what benches/kzg_benches.rs:70-81 times).
     pub fn verify_kzg_proof_many(
         commitments: &[KzgCommitment],
