@@ -192,6 +192,12 @@ def test_chunked_many_matches_single_calls(kz, settings):
     for i in sorted(set([0, 511, 512, n - 1] + random.Random(3).sample(range(n), 4))):
         c, p = kz.Kzg.compute_cells_and_kzg_proofs(blobs[i], settings)
         assert (raw(res[i][0]), raw(res[i][1])) == (raw(c), raw(p)), i
+        assert raw(res[i][0]) == cs.compute_cells(blobs[i]), i
+    # every blob's 128 cells and proofs against its commitment (both calls are pinned to the oracle elsewhere)
+    coms = kz.Kzg.blob_to_kzg_commitment_many(blobs, settings)
+    assert not any(isinstance(c, kz.Error) for c in coms)
+    groups = [([coms[i]] * 128, list(range(128)), res[i][0], res[i][1]) for i in range(n)]
+    assert kz.Kzg.verify_cell_kzg_proof_batch_many(groups, settings) == [True] * n
 
 
 def test_concurrent_first_call_and_4844_after(kz, setup_bytes, fx, oracle, oracle_settings):
