@@ -10,12 +10,15 @@ Restates benches/kzg_benches.rs:93-126 (criterion group `verify_blob_kzg_proof_b
     64-blob batches (`--batches-per-step G`), submitted together through kzg355_verify_blob_kzg_proof_batch_many_device
     (or the two stage functions around the exchange for N > 1).  One 64-blob batch is a chain of latency-bound integer
     kernels that occupies a handful of the chip's 1024 SIMDs, so whole-job throughput needs many batches in flight;
-  * `value` is measured with the inputs resident in HBM when the timed region starts.  The same run also reports, in
-    `config.host_inputs`, what the reference's own bench shape gives (host slices through the drop-in C ABI, PCIe H2D
-    inside the call): one 64-blob call alone, and the streaming rate of a big call -- neither is ever `value`.
+  * `value` is measured with the inputs resident in HBM when the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (HBM bound of the dominant kernel plus
-`roofline.alu`, the integer-issue bound that actually binds this path) and `cpu_baseline` objects.
+A plain run does only what `value` needs: the untimed setup, the warm-up, the timed steps, `--dump-outputs` and the line, with `roofline`
+(HBM bound of the dominant kernel plus `roofline.alu`, the integer-issue bound that actually binds this path) from the HIP events of the
+timed steps.  `--full` adds every leg that is measured or checked beside it: the single-batch latency, `config.host_inputs` (what the
+reference's own bench shape gives: host slices through the drop-in C ABI, PCIe H2D inside the call), the mid-size and mixed legs, the
+commitment / proof legs, the measured stream-copy rate, `cpu_baseline` and, for N > 1, the parity gate and the in-library leg -- never `value`.
+
+Prints ONE JSON line on rank 0 (contract in the task statement).
 `--sweep` restates the criterion sweep n in {1,2,4,8,16,32,64} and the five single-op benches (kzg_benches.rs:46-126).
 """
 import argparse
@@ -240,10 +243,13 @@ def main():
                     help="verify = the headline metric; commit / proof = secondary single-GPU metrics (BASELINE.json configs[1], [2])")
     ap.add_argument("--host-inputs", action="store_true",
                     help="time the host-buffer drop-in entry point (H2D over PCIe inside the timed region); never the headline value")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the config.host_inputs measurements of the default run")
-    ap.add_argument("--no-msm-legs", action="store_true", help="skip the commitment / proof legs of the default run (BASELINE configs[1], [2])")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-batch latency calls (profiling runs: every launch is then a full-size one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: single-batch latency, host-input / mid-size / mixed legs, the commitment / proof legs, "
+                         "the stream-copy rate, the CPU baseline and, N > 1, the parity gate and the in-library leg (a plain run: setup, warm-up, timed steps, line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-host-leg", action="store_true", help="--full: skip the config.host_inputs measurements and the mid-size leg")
+    ap.add_argument("--no-msm-legs", action="store_true", help="--full: skip the commitment / proof legs and the mixed leg (BASELINE configs[1], [2])")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the single-batch latency calls (profiling runs: every launch is then a full-size one)")
     ap.add_argument("--no-kernel-timing", action="store_true", help="no HIP events around the kernels of the timed region (A/B of their cost; no roofline)")
     ap.add_argument("--sharded-path", action="store_true",
                     help="run the multi-GPU code path (two-stage HipEngine driver of sharded.py) even at world size 1")
@@ -254,8 +260,8 @@ def main():
                     help="N > 1: both (default) = K timed steps of EVERY form back to back, `value` = the best one (config.value_exchange names it); "
                          "alltoall = stage 2 split by batch; allgather = BASELINE north_star's single all-gather with stage 2 replicated; "
                          "allgather_split = the same all-gather with stage 2 split by batch")
-    ap.add_argument("--no-parity-gate", action="store_true", help="N > 1: skip the byte-exact check of the sharded path on the real ranks before the timed steps")
-    ap.add_argument("--no-in-library-leg", action="store_true", help="N > 1: skip the timing of the library's own multi-device handle (kzg355_load_trusted_setup_devices) on rank 0")
+    ap.add_argument("--no-parity-gate", action="store_true", help="N > 1, --full: skip the byte-exact check of the sharded path on the real ranks before the timed steps")
+    ap.add_argument("--no-in-library-leg", action="store_true", help="N > 1, --full: skip the timing of the library's own multi-device handle (kzg355_load_trusted_setup_devices) on rank 0")
     ap.add_argument("--max-seconds", type=float, default=480.0,
                     help="wall-clock budget of the whole run from process start (the driver allows 600 s): optional legs are DROPPED, not cut short, once the time "
                          "left does not cover them -- N > 1: first the in-library leg, then the exchange forms beyond the first (north_star's all-gather always "
@@ -289,7 +295,8 @@ def main():
         # test hook (tests/test_bench_launcher.py, no GPU): every rank reports how it was started; rank 0 prints the line
         if rank == 0:
             emit({"metric": "echo", "argv": sys.argv[1:], "world": world, "gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-                  "exchange": args.exchange, "master_addr": os.environ.get("MASTER_ADDR"), "dump_outputs": args.dump_outputs})
+                  "exchange": args.exchange, "master_addr": os.environ.get("MASTER_ADDR"), "dump_outputs": args.dump_outputs,
+                  "full": args.full})
         time.sleep(float(os.environ.get("KZG355_BENCH_ECHO_SLEEP", "0")))      # (test hook: ranks that stay up long enough to be interrupted)
         raise SystemExit(int(os.environ.get("KZG355_BENCH_ECHO_RC", "0")) if rank == world - 1 else 0)
     # Rehearsal hook (never set by the driver): KZG355_BENCH_FORCE_DIST=1 with one rank under torch.distributed.run makes the N = 1 run take the N > 1 code path --
@@ -453,9 +460,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # single-batch latency (reported, not the metric)
+    # single-batch latency (--full: reported, not the metric)
+    measure_latency = args.full and not args.no_latency
     lat = [float("nan")]
-    if not args.no_latency:
+    if measure_latency:
         run_steps(1)
         lat = []
         for _ in range(5):
@@ -490,7 +498,7 @@ def main():
             run_steps(Cc)                              # synchronous: returns when this step's verdicts are on the host
 
     parity = None
-    if multi and args.op == "verify" and not args.no_parity_gate:
+    if multi and args.op == "verify" and args.full and not args.no_parity_gate:
         # the only place real-xGMI parity can ever be checked: the sharded path on the real ranks against the committed fixture / the single-device run
         parity = parity_gate(kz, L, s, engine, dev, torch, dist, random_blob, rank, world, backend)
 
@@ -550,6 +558,7 @@ def main():
     modes = ["allgather", "allgather_split", "alltoall"] if (sharded and args.exchange == "both" and args.op == "verify") else [mode_now[0]]
     # (the same K and W for each form, back to back.  --max-seconds: a further form needs what the last one took, and the line, the parity of the exit and --
     # N > 1 -- the in-library leg's 20 s minimum still have to fit behind it; all ranks take the same decision from rank 0's clock)
+    setup_s = time.perf_counter() - T_PROCESS_START                 # start to the first warm-up step (config.setup_s)
     runs = {}
     for m in modes:
         if runs:
@@ -609,7 +618,7 @@ def main():
                                    for f, v in sorted(stats.items(), key=lambda kv: -kv[1][0]) if f in KERNEL_BYTES_PER_BLOB},
                     "path_bytes_per_blob": OP_BYTES_PER_BLOB[args.op],
                     "path_frac_of_hbm_peak": value * OP_BYTES_PER_BLOB[args.op] / (world * HBM_PEAK_GBPS * 1e9),
-                    "measured_stream_copy_gbps": stream_copy_peak(torch, dev) if rank == 0 else None,
+                    "measured_stream_copy_gbps": stream_copy_peak(torch, dev) if rank == 0 and args.full else None,
                     "alu": alu_roofline(stats, blobs_per_launch_of, value / world, insts_scale_of) if args.op == "verify" else None,      # (the committed SQ pass is over the verify bench)
                     "note": "integer-issue-bound path (~1e3 integer ops per byte): the HBM fraction is small by construction; roofline.alu is the bound that binds"}
         if args.op != "verify" and s.msm_form >= 10:
@@ -625,12 +634,12 @@ def main():
 
     host_inputs = None
     mid_size = None
-    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and not args.no_host_leg:
+    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and args.full and not args.no_host_leg:
         host_inputs = host_leg(L, s, t_blobs, commitments, proofs, n_local, min(Cc, 1024))
         if pipeline == 1 and Cc >= 1024 and not args.sharded_path:
             mid_size = mid_size_leg(L, s, t_blobs, t_c, t_p, n_local)
     cpu_baseline = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if rank == 0 and not multi and args.full and not args.no_cpu_baseline:
         cpu_baseline = time_cpu_baseline(args.op, commitments[:48 * n_local], proofs[:48 * n_local], host, n_local,
                                          match_threads=host_inputs.get("single_call_host_threads") if host_inputs else None,
                                          all_threads=time_left() > 200.0)
@@ -638,7 +647,7 @@ def main():
             skipped.append("CPU all-threads trials")
 
     coexist = None
-    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and not args.no_msm_legs and not args.sharded_path and pipeline == 1 and Cc >= 1024:
+    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and args.full and not args.no_msm_legs and not args.sharded_path and pipeline == 1 and Cc >= 1024:
         # what a drop-in KzgSettings serves -- verification AND commitments from ONE handle, nothing freed in between.  `s` is a default
         # handle: the untimed setup's commitments made it size its own table (from half of the HBM free at that moment), and the step's 69 GB of blobs are
         # still resident beside it.
@@ -649,7 +658,7 @@ def main():
 
     msm_form_at_end = s.msm_form
     msm_legs = None
-    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and not args.no_msm_legs and not args.sharded_path:
+    if rank == 0 and not multi and args.op == "verify" and not args.host_inputs and args.full and not args.no_msm_legs and not args.sharded_path:
         # BASELINE configs[1] and [2] in the same driver-timed run: the verify handle and its launch sets are released first (69 GB of blobs,
         # the table the untimed setup built), then a handle with the widest MSM table that fits serves both legs
         msm_form_verify_setup = s.msm_form
@@ -663,7 +672,7 @@ def main():
         s = None
 
     in_library = None
-    run_in_library = multi and args.op == "verify" and not args.no_in_library_leg
+    run_in_library = multi and args.op == "verify" and args.full and not args.no_in_library_leg
     if run_in_library:
         # the first leg to go when time is short (it loads N handles and makes 256 commitments and proofs before it times anything: ~60-100 s on 8 devices)
         go = time_left() > float(os.environ.get("KZG355_BENCH_IN_LIBRARY_NEEDS", "150"))
@@ -719,8 +728,8 @@ def main():
                        "field_elements_per_blob": 4096, "sets_in_flight": pipeline, "inputs": "host buffers (PCIe H2D inside the timed region)" if args.host_inputs else "resident in HBM",
                        "msm_form": msm_legs["verify_setup_msm_form"] if msm_legs else msm_form_at_end, **({"rehearsal": f"{world} rank(s) on ONE GPU, backend {backend}: code-path check, not a measurement"} if rehearsal and multi else {}),
                        "step_ms": {"median": round(statistics.median(step_ms), 4), "min": round(min(step_ms), 4), "mean": round(dt * 1e3 / K, 4)},
-                       "latency_ms_single_batch": None if args.no_latency else round(latency_ms, 3), "latency_ms_single_batch_min": None if args.no_latency else round(min(lat), 3),
-                       "host_inputs": host_inputs, "mid_size_sets": mid_size, "power": power},
+                       "latency_ms_single_batch": round(latency_ms, 3) if measure_latency else None, "latency_ms_single_batch_min": round(min(lat), 3) if measure_latency else None,
+                       "host_inputs": host_inputs, "mid_size_sets": mid_size, "power": power, "full": args.full},
             "roofline": roofline, "cpu_baseline": cpu_baseline,
         }
         if host_inputs:
@@ -751,6 +760,7 @@ def main():
             line["config"].update(in_library)
         line["config"]["skipped_for_time"] = "; ".join(skipped) if skipped else "nothing"
         line["config"]["wall_s"] = round(time.perf_counter() - T_PROCESS_START, 1)      # this process, start to line (the launcher of an N > 1 run adds its own start-up)
+        line["config"]["setup_s"] = round(setup_s, 1)
         flatten_scalars(line, host_inputs, mid_size, power, msm_legs, coexist, multi=multi)
         emit(line)
     if s is not None:

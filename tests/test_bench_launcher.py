@@ -252,3 +252,14 @@ def test_the_state_main_shares_with_its_steps_is_bound_once():
     in_main = stores(main)
     assert {"last_step", "pending", "exchange_acc"} <= shared, shared
     assert {name: in_main.count(name) for name in shared if in_main.count(name) != 1} == {}
+
+
+def test_full_reaches_the_ranks_and_is_off_by_default():
+    """--full (the legs beside the headline figure) is forwarded like every flag; a plain run leaves it off"""
+    r = run(["--gpus", "2", "--steps", "2", "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip())
+    assert line["argv"] == ["--gpus", "2", "--steps", "2", "--full"] and line["full"] is True
+    r = run(["--gpus", "1", "--steps", "2"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip())["full"] is False

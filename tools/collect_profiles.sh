@@ -37,11 +37,11 @@ for op in commit proof; do
 done
 for op in commit proof; do
   echo "== $op"
-  cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$op -- python3 $ROOT/bench.py --op $op --steps 6 --warmup 2 > $OUT/bench_${op}_$V.json 2> $OUT/$op.err; echo rc=$?
+  cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$op -- python3 $ROOT/bench.py --op $op --steps 6 --warmup 2 --full > $OUT/bench_${op}_$V.json 2> $OUT/$op.err; echo rc=$?
   cd $ROOT; find $OUT/trace_$op -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_bench_${op}_$V.csv \;
 done
 rm -rf $OUT/trace $OUT/trace_commit $OUT/trace_proof $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq      # the raw traces are large; the summaries are what is kept
 unset KZG355_SELFTEST
-echo "== default bench (un-profiled)"; python bench.py > $OUT/bench_default_$V.json 2> $OUT/bench_default.err; echo rc=$?
+echo "== full bench (un-profiled)"; python bench.py --full > $OUT/bench_default_$V.json 2> $OUT/bench_default.err; echo rc=$?
 echo "== sweep"; python bench.py --sweep > $OUT/bench_sweep_$V.json 2> $OUT/sweep.err; echo rc=$?
 ls -la $OUT
