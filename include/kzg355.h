@@ -362,6 +362,20 @@ int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL *
  * refusal of the call as a whole marks every blob.  Large n runs in chunks inside the call. */
 int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out /* n*128*2048 or NULL */, uint8_t *proofs_out /* n*128*48 or NULL */,
                                              int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
+/* recover_cells_and_kzg_proofs of the consensus specs: from n known cells of a blob's 2x extension (64 <= n <= 128; cell_indices strictly
+ * ascending and < 128, cells in the same order) all 128 cells and all 128 proofs, exactly what kzg355_compute_cells_and_kzg_proofs returns for
+ * the blob.  n outside 64..128, an index >= 128, indices not strictly ascending (so: any duplicate) or a cell element >= r -> KZG355_BADARGS.
+ * Either output may be NULL, with the meaning it has there; not both.  More than 64 cells that lie on no polynomial of degree < 4096 are no
+ * error, as in the specs and in c-kzg-4844: the result is the cells and proofs of the 4096 coefficients the specs' algorithm keeps.  Mainnet
+ * handles only; a handle over several devices runs on its first device. */
+int kzg355_recover_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL */, uint8_t *proofs_out /* 128*48 or NULL */,
+                                        const size_t *cell_indices /* n */, const uint8_t *cells /* n*2048 */, size_t n, const kzg355_settings *s);
+/* m blobs known at the SAME n cell indices (a node holds the same columns of every blob of a block) in one set of launches: cells holds blob
+ * after blob, n cells each.  status[i] per blob; the return value is the first non-OK status.  m == 0 -> OK.  A refusal of the call as a whole
+ * marks every blob.  Large m runs in chunks inside the call. */
+int kzg355_recover_cells_and_kzg_proofs_many(uint8_t *cells_out /* m*128*2048 or NULL */, uint8_t *proofs_out /* m*128*48 or NULL */,
+                                             int *status /* m or NULL */, const size_t *cell_indices /* n, shared by all blobs */,
+                                             const uint8_t *cells /* m*n*2048: blob after blob */, size_t n, size_t m, const kzg355_settings *s);
 /* Test form: the FK20 intermediates H_0 .. H_63 of each blob, compressed (H_e = sum_{m >= 64(e+1)} f_m [tau^(m - 64(e+1))]_1; H_63 = infinity). */
 int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
 /* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */

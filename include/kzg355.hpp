@@ -193,6 +193,24 @@ struct Kzg {
         return out;
     }
 
+    // EIP-7594 recover_cells_and_kzg_proofs: all 128 cells and proofs of a blob from 64..128 of its cells at strictly ascending indices
+    static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> recover_cells_and_kzg_proofs(const std::vector<size_t> &cell_indices,
+                                                                                                    const std::vector<Cell> &cells, const KzgSettings &s) {
+        const size_t n = cells.size();
+        if (cell_indices.size() != n) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<uint8_t> in(n * KZG355_BYTES_PER_CELL), c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL),
+            p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48);
+        for (size_t i = 0; i < n; i++) std::memcpy(&in[i * KZG355_BYTES_PER_CELL], cells[i].data(), KZG355_BYTES_PER_CELL);
+        int rc = kzg355_recover_cells_and_kzg_proofs(c.data(), p.data(), cell_indices.data(), in.data(), n, s.raw());
+        if (rc) return from_status(rc, "recover_cells_and_kzg_proofs");
+        std::pair<std::vector<Cell>, std::vector<KzgProof>> out;
+        for (int k = 0; k < KZG355_CELLS_PER_EXT_BLOB; k++) {
+            out.first.push_back(Cell::from_bytes(&c[(size_t)k * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+            out.second.push_back(KzgProof::from_bytes(&p[(size_t)k * 48], 48).value());
+        }
+        return out;
+    }
+
     // ---- throughput extensions (no reference counterpart): many independent single-proof units per call; one Result per unit, an Err of the
     // call itself only for whole-call failures (no device, out of memory, a length mismatch)
     static bool whole_call_failed(int rc, const std::vector<int> &st) {

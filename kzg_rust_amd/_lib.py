@@ -97,6 +97,8 @@ def load():
         "kzg355_debug_cell_setup_monomial": [u8p, vp],
         "kzg355_compute_cells_and_kzg_proofs": [u8p, u8p, u8p, vp],
         "kzg355_compute_cells_and_kzg_proofs_many": [u8p, u8p, ip, u8p, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs": [u8p, u8p, szp, u8p, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_many": [u8p, u8p, ip, szp, u8p, sz, sz, vp],
         "kzg355_debug_cell_compute_h": [u8p, ip, u8p, sz, vp],
         "kzg355_debug_cell_setup_monomial_all": [u8p, vp],
     }
@@ -141,4 +143,5 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_cell_kzg_proof_batch", "kzg355_verify_cell_kzg_proof_batch_many", "kzg355_debug_cell_batch_intermediates",
     "kzg355_debug_cell_setup_monomial", "kzg355_compute_cells_and_kzg_proofs", "kzg355_compute_cells_and_kzg_proofs_many",
     "kzg355_debug_cell_compute_h", "kzg355_debug_cell_setup_monomial_all",
+    "kzg355_recover_cells_and_kzg_proofs", "kzg355_recover_cells_and_kzg_proofs_many",
 ]

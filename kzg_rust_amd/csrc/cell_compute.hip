@@ -5,10 +5,8 @@
 
 namespace kzg355_impl {
 
-static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
-
 // Constants of the field stage (w4096 powers, twiddle splits): the first compute call of a handle.  Under cc_mu.
-static int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
+int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cc_mu);
     if (s->cc_consts_ready) return KZG355_OK;
     int rc;
@@ -22,7 +20,7 @@ static int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
 
 // The proof setup, on the first call that wants proofs (after ensure_cc_consts): the monomial points [tau^t]_1, t < 4096, as commitments of
 // the "blobs" (w_i^t)_i through the 8-bit fixed-base MSM, 64 at a time; X_r = NTT128(x_r) and their comb table.  Under cc_mu.
-static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
+int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cc_mu);
     if (s->cc_proof_ready) return s->cc_proof_rc;
     DevBuf scal, digits, partials, X, err;
@@ -62,6 +60,53 @@ static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
     return done(KZG355_OK);
 }
 
+// The device chain behind the field stage, shared with recover_cells_and_kzg_proofs (cell_recover.hip), whose field stage leaves the same two
+// things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role: y = coefficients, scal_a = column scalars,
+// partials = Z, q = cells, out48 = proofs, small = H.
+int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h) {
+    int rc;
+    if ((rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
+        (want_cells && (rc = w->q.ensure((size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * CH))) ||
+        (want_proofs && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
+                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (rc = w->out48.ensure((size_t)48 * CC_FFT * CH)))) ||
+        (want_h && (rc = w->small.ensure((size_t)48 * CELL_FE * CH))))
+        return rc;
+    return KZG355_OK;
+}
+// coefficients of m blobs in w->y -> proofs in w->out48 (and H in w->small), queued on w->stream
+void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h) {
+    const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
+    hipStream_t st = w->stream;
+    tm.begin("cc_columns");
+    launch_cc_columns(w->y.as<Fr>(), m, cc, w->scal_a.as<uint32_t>(), st);
+    tm.end();
+    tm.begin("cc_msm");
+    launch_cc_msm(w->scal_a.as<uint32_t>(), m, s->cc_table.as<G1Affine>(), w->partials.as<G1Jac>(), st);
+    tm.end();
+    tm.begin("cc_proofs");
+    launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, w->out48.as<uint8_t>(), want_h ? w->small.as<uint8_t>() : nullptr, st);
+    tm.end();
+}
+// the results of a chunk of m blobs (blob c0 onwards) back to the host, the wait, and the per-blob statuses
+int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first) {
+    const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
+    hipStream_t st = w->stream;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    if (cells_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
+    if (proofs_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
+    if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    w->in_flight = false;
+    tm.collect();
+    for (int i = 0; i < m; i++) {
+        const int stt = status_from_err(w->h_err.as<int>()[i]);
+        if (status) status[c0 + i] = stt;
+        if (stt != KZG355_OK && first == KZG355_OK) first = stt;
+    }
+    return KZG355_OK;
+}
+
 // cells_out / proofs_out / h_dbg: host memory (any may be null, not all); status (or null): per blob.
 static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs) {
     auto refuse = [&](int code) { if (status) for (size_t i = 0; i < n; i++) status[i] = code; return code; };
@@ -78,14 +123,7 @@ static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int 
     if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
     if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
     const size_t CH = n < CC_CHUNK ? n : CC_CHUNK;
-    const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
-    // the workspace's buffers by role: blobs, y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H
-    if ((rc = w->blobs.ensure((size_t)BLOB_BYTES * CH)) || (rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
-        (cells_out && (rc = w->q.ensure(cell_bytes * CH))) ||
-        (want_proofs && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
-                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (rc = w->out48.ensure((size_t)48 * CC_FFT * CH)))) ||
-        (h_dbg && (rc = w->small.ensure((size_t)48 * CELL_FE * CH))))
-        return refuse(rc);
+    if ((rc = w->blobs.ensure((size_t)BLOB_BYTES * CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg))) return refuse(rc);
     const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
     hipStream_t st = w->stream;
     Timed tm(s, w);
@@ -99,30 +137,9 @@ static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int 
         tm.begin("cc_field");
         launch_cc_field(w->blobs.as<uint8_t>(), m, cc, want_proofs ? w->y.as<Fr>() : nullptr, cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), st);
         tm.end();
-        if (want_proofs) {
-            tm.begin("cc_columns");
-            launch_cc_columns(w->y.as<Fr>(), m, cc, w->scal_a.as<uint32_t>(), st);
-            tm.end();
-            tm.begin("cc_msm");
-            launch_cc_msm(w->scal_a.as<uint32_t>(), m, s->cc_table.as<G1Affine>(), w->partials.as<G1Jac>(), st);
-            tm.end();
-            tm.begin("cc_proofs");
-            launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, w->out48.as<uint8_t>(), h_dbg ? w->small.as<uint8_t>() : nullptr, st);
-            tm.end();
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-        if (cells_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
-        if (proofs_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
-        if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        w->in_flight = false;
-        tm.collect();
-        for (int i = 0; i < m; i++) {
-            const int stt = status_from_err(w->h_err.as<int>()[i]);
-            if (status) status[c0 + i] = stt;
-            if (stt != KZG355_OK && first == KZG355_OK) first = stt;
-        }
+        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg);
+        int crc;
+        if ((crc = cc_collect_chunk(w, tm, cells_out, proofs_out, h_dbg, status, c0, m, first))) return crc;
     }
     return KZG355_OK;
     };

@@ -388,6 +388,13 @@ int msm_op_many_device_impl(uint8_t *out, int *status, const uint8_t *d_blobs, c
 int stage_to_device(Workspace *w, DevBuf &dst, const uint8_t *src, size_t bytes);
 int stage_via_pinned(kzg355_settings *s, Workspace *w, PinBuf &pin, size_t pin_off, DevBuf &dst, const uint8_t *src, size_t bytes);
 int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs);
+// compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_compute.hip; the second call's own stage: cell_recover.hip)
+static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
+int ensure_cc_consts(kzg355_settings *s, Workspace *w);
+int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w);
+int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h);
+void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h);
+int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first);
 
 }  // namespace kzg355_impl
 

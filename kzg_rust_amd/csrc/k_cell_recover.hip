@@ -1,0 +1,158 @@
+// k_cell_recover.hip -- the field stage of recover_cells_and_kzg_proofs (EIP-7594 / PeerDAS, consensus specs
+// fulu/polynomial-commitments-sampling.md) on the device: from 64..128 known cells of a blob's 2x extension to the blob polynomial's
+// coefficients and all 128 cells.  The proofs then come from the FK20 chain of k_cell_compute.hip (k_cc_columns, k_cc_msm, k_cc_proofs).
+//
+// The spec states recovery with 8192-point transforms; the cell structure makes every transform here one of 64 or 128 points.  Write
+// p(x) = sum_{r<64} x^r P_r(x^64), deg P_r < 64.  The 64 points of cell k share x^64 = a_k = w128^rev7(k) (w128 = w^64, w = 7^((r-1)/8192)),
+// so the degree < 64 interpolant of cell k on its coset h_k <w64> has the coefficients u_r(k) = P_r(a_k): 64 independent erasure-decoding
+// problems of length 128, one per column r, all with the same known positions.  With M the missing cells and S(y) = prod_{m in M} (y - a_m):
+//   (k_rc_interp)  per known cell: dit64 of its elements (root w64^-1), coefficient t times h_k^-t  -> u_t(k)
+//   (k_rc_vanish)  once per call: S(a_k) on the domain and 1 / S(g a_k) on the coset g <w128>, g = w (g^128 = w64 != 1)
+//   (k_rc_columns) per (blob, column r): E_r(a_k) S(a_k) (0 at the missing k) = (P_r S)(a_k), deg P_r S < 128: dit128 -> its coefficients c_i;
+//                  dif128 of c_i g^i -> (P_r S)(g a_k); times 1 / S(g a_k); dit128, times g^-i -> P_r.  f_(64u+r) = P_r[u] for u < 64 are the
+//                  blob's coefficients (columns are what k_cc_columns reads); dif128 of (P_r[0..63], 0^64) -> P_r(a_k) for all 128 cells
+//   (k_rc_cells)   per cell: coefficient r times h_k^r, dif64 (root w64) -> the cell's 64 elements in their order
+// Orders as in k_cell_compute.hip: "dif" natural in, bit-reversed out; "dit" bit-reversed in, natural out.  Cell order is the bit-reversed
+// order of the 128-point domain and element order that of the 64-point coset, so no permutation runs anywhere.  The factors 1/64 (dit64) and
+// 1/128 (each dit128) ride in the two tables of k_rc_vanish.  Coefficients 64..127 of P_r are zero exactly when the known cells lie on one
+// polynomial of degree < 4096; they are dropped, as the spec drops the upper half of its quotient.  tests/recover_spec.py restates the route.
+#define KZG_FP_MUL_NOINLINE 1
+#include "kernels.h"
+
+namespace kzg {
+
+__device__ __forceinline__ uint32_t rc_rev7(uint32_t j) { return __brev(j) >> 25; }
+// w^e for e < 8192 from the w4096 table
+__device__ __forceinline__ Fr rc_wpow(const CellComputeConsts *cc, uint32_t e) {
+    Fr v = cc->w4096[e >> 1];
+    if (e & 1u) fr_mul(v, v, cc->w8192);
+    return v;
+}
+// Transforms of N = 64 or 128 values in LDS by one wave: lane L < N / 2 takes one butterfly per stage (wN^e = w4096^(e 4096 / N)).
+// forward (root wN): natural in, bit-reversed out
+template <int N> __device__ void rc_dif(Fr *a, const CellComputeConsts *cc, int L) {
+    for (int h = N / 2; h >= 1; h >>= 1) {
+        if (L < N / 2) {
+            const int j = L % h, s = (L / h) * 2 * h, e = j * (N / 2 / h);
+            const Fr u = a[s + j], v = a[s + j + h];
+            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
+            if (e) fr_mul(y, y, cc->w4096[e * (N_FE / N)]);
+            a[s + j] = x; a[s + j + h] = y;
+        }
+        __syncthreads();
+    }
+}
+// inverse (root wN^-1, no 1/N): bit-reversed in, natural out
+template <int N> __device__ void rc_dit_inv(Fr *a, const CellComputeConsts *cc, int L) {
+    for (int h = 1; h < N; h <<= 1) {
+        if (L < N / 2) {
+            const int j = L % h, s = (L / h) * 2 * h, e = j * (N / 2 / h);
+            const Fr u = a[s + j];
+            Fr v = a[s + j + h];
+            if (e) fr_mul(v, v, cc->w4096[N_FE - e * (N_FE / N)]);
+            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
+            a[s + j] = x; a[s + j + h] = y;
+        }
+        __syncthreads();
+    }
+}
+
+// once per call, thread k < 128: sd[k] = S(a_k) / (64 * 128), sci[k] = 1 / (128 S(g a_k)); pos[k] < 0 marks the missing cells
+__global__ void __launch_bounds__(CELLS_PER_EXT_BLOB) k_rc_vanish(const CellComputeConsts *cc, RecoverTables *rt) {
+    __shared__ Fr a[CELLS_PER_EXT_BLOB];
+    __shared__ int missing[CELLS_PER_EXT_BLOB];
+    const int k = threadIdx.x;
+    a[k] = cc->w4096[(N_FE / CC_FFT) * rc_rev7((uint32_t)k)];
+    missing[k] = rt->pos[k] < 0;
+    __syncthreads();
+    Fr ga; fr_mul(ga, a[k], cc->w8192);
+    Fr sd = fr_one(), sc = fr_one();
+    for (int m = 0; m < CELLS_PER_EXT_BLOB; m++) {
+        if (!missing[m]) continue;
+        Fr d;
+        fr_sub(d, a[k], a[m]); fr_mul(sd, sd, d);
+        fr_sub(d, ga, a[m]); fr_mul(sc, sc, d);                    // never zero: g a_k is outside <w128>
+    }
+    Fr inv64; fr_add(inv64, cc->inv128, cc->inv128);
+    fr_mul(sd, sd, inv64); fr_mul(sd, sd, cc->inv128);
+    rt->sd[k] = sd;
+    Fr sci; fr_inv(sci, sc);
+    fr_mul(sci, sci, cc->inv128);
+    rt->sci[k] = sci;
+}
+// workgroup (blob, cell k): the 64 coefficients of the cell's interpolant, times 64, at u[blob][k][t]; nothing for a missing cell
+__global__ void __launch_bounds__(CELL_FE) k_rc_interp(const uint8_t *cells, int n, const CellComputeConsts *cc, const RecoverTables *rt, Fr *u, int *err) {
+    __shared__ Fr a[CELL_FE];
+    const int b = blockIdx.x / CELLS_PER_EXT_BLOB, k = blockIdx.x % CELLS_PER_EXT_BLOB, t = threadIdx.x;
+    const int p = rt->pos[k];
+    if (p < 0) return;
+    Fr v;
+    if (!fr_from_be32_checked(v, cells + ((size_t)b * n + p) * CELL_BYTES + 32 * t)) atomicOr(&err[b], ERR_NONCANONICAL_FR);
+    a[t] = v;                                                       // p(h_k w64^rev6(t)): bit-reversed order, as dit wants it
+    __syncthreads();
+    rc_dit_inv<CELL_FE>(a, cc, t);
+    const uint32_t e = (rc_rev7((uint32_t)k) * (uint32_t)t) & 8191u;   // h_k^-t = w^(8192 - e)
+    v = a[t];
+    if (e) { const Fr hp = rc_wpow(cc, 8192u - e); fr_mul(v, v, hp); }
+    u[((size_t)b * CELLS_PER_EXT_BLOB + k) * CELL_FE + t] = v;
+}
+// workgroup (blob, column r): see the head of the file.  u is read at [blob][k][r] for the known k and, when cells are wanted, written there
+// for all k; coef (or null) receives f_(64 i + r) for i < 64.
+__global__ void __launch_bounds__(CELL_FE) k_rc_columns(Fr *u, const CellComputeConsts *cc, const RecoverTables *rt, Fr *coef, int want_cells) {
+    __shared__ Fr a[CC_FFT];
+    const int b = blockIdx.x / CELL_FE, r = blockIdx.x % CELL_FE, L = threadIdx.x;
+    Fr *col = u + (size_t)b * CELLS_PER_EXT_BLOB * CELL_FE + r;
+    for (int k = L; k < CC_FFT; k += CC_FFT / 2) {
+        Fr v = fr_zero();
+        if (rt->pos[k] >= 0) fr_mul(v, col[(size_t)k * CELL_FE], rt->sd[k]);
+        a[k] = v;
+    }
+    __syncthreads();
+    rc_dit_inv<CC_FFT>(a, cc, L);                                   // coefficients of P_r S
+    for (int i = L; i < CC_FFT; i += CC_FFT / 2)
+        if (i) { Fr v; const Fr g = rc_wpow(cc, (uint32_t)i); fr_mul(v, a[i], g); a[i] = v; }
+    __syncthreads();
+    rc_dif<CC_FFT>(a, cc, L);                                       // (P_r S)(g a_k)
+    for (int k = L; k < CC_FFT; k += CC_FFT / 2) { Fr v; fr_mul(v, a[k], rt->sci[k]); a[k] = v; }
+    __syncthreads();
+    rc_dit_inv<CC_FFT>(a, cc, L);                                   // P_r[i] g^i
+    Fr f = a[L];
+    if (L) { const Fr g = rc_wpow(cc, 8192u - (uint32_t)L); fr_mul(f, f, g); }
+    if (coef) coef[(size_t)N_FE * b + CELL_FE * L + r] = f;
+    if (!want_cells) return;
+    __syncthreads();
+    a[L] = f;
+    a[L + CC_FFT / 2] = fr_zero();
+    __syncthreads();
+    rc_dif<CC_FFT>(a, cc, L);                                       // P_r(a_k), k in cell order
+    for (int k = L; k < CC_FFT; k += CC_FFT / 2) col[(size_t)k * CELL_FE] = a[k];
+}
+// workgroup (blob, cell k): the cell's elements from u[blob][k][r] = P_r(a_k)
+__global__ void __launch_bounds__(CELL_FE) k_rc_cells(const Fr *u, const CellComputeConsts *cc, uint8_t *cells) {
+    __shared__ Fr a[CELL_FE];
+    const int k = blockIdx.x % CELLS_PER_EXT_BLOB, r = threadIdx.x;
+    Fr v = u[(size_t)blockIdx.x * CELL_FE + r];
+    const uint32_t e = rc_rev7((uint32_t)k) * (uint32_t)r;          // h_k^r = w^e, e <= 127 * 63
+    if (e) { const Fr hp = rc_wpow(cc, e); fr_mul(v, v, hp); }
+    a[r] = v;
+    __syncthreads();
+    rc_dif<CELL_FE>(a, cc, r);
+    fr_to_be32(cells + (size_t)blockIdx.x * CELL_BYTES + 32 * r, a[r]);
+}
+
+// ---- launchers
+void launch_rc_vanish(const CellComputeConsts *d_cc, RecoverTables *d_rt, hipStream_t st) {
+    hipLaunchKernelGGL(k_rc_vanish, dim3(1), dim3(CELLS_PER_EXT_BLOB), 0, st, d_cc, d_rt);
+}
+void launch_rc_interp(const uint8_t *d_cells, int n_cells, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_u, int *d_err,
+                      hipStream_t st) {
+    if (m > 0) hipLaunchKernelGGL(k_rc_interp, dim3(m * CELLS_PER_EXT_BLOB), dim3(CELL_FE), 0, st, d_cells, n_cells, d_cc, d_rt, d_u, d_err);
+}
+void launch_rc_columns(Fr *d_u, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_coef, bool want_cells, hipStream_t st) {
+    if (m > 0) hipLaunchKernelGGL(k_rc_columns, dim3(m * CELL_FE), dim3(CELL_FE), 0, st, d_u, d_cc, d_rt, d_coef, want_cells ? 1 : 0);
+}
+void launch_rc_cells(const Fr *d_u, int m, const CellComputeConsts *d_cc, uint8_t *d_cells, hipStream_t st) {
+    if (m > 0) hipLaunchKernelGGL(k_rc_cells, dim3(m * CELLS_PER_EXT_BLOB), dim3(CELL_FE), 0, st, d_u, d_cc, d_cells);
+}
+
+}  // namespace kzg

@@ -229,4 +229,19 @@ void launch_cc_columns(const Fr *d_coef, int n, const CellComputeConsts *d_cc, u
 void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *d_Z, hipStream_t st);
 void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
 
+// ---- k_cell_recover.hip: the field stage of recover_cells_and_kzg_proofs (64..128 known cells -> coefficients and all 128 cells; mainnet handles only)
+struct RecoverTables {
+    Fr sd[CELLS_PER_EXT_BLOB];                               // S(a_k) / (64 * 128), S the vanishing polynomial of the missing cells' a_m
+    Fr sci[CELLS_PER_EXT_BLOB];                              // 1 / (128 S(w a_k))
+    int pos[CELLS_PER_EXT_BLOB];                             // cell k's place in the call's index list, -1 if missing (written by the host)
+};
+// once per call (the index set is shared by the call's blobs): sd and sci from pos
+void launch_rc_vanish(const CellComputeConsts *d_cc, RecoverTables *d_rt, hipStream_t st);
+// d_cells: m blobs of n_cells cells each; d_u: m * 128 * 64 Fr ([blob][cell][column]); non-canonical elements -> ERR_NONCANONICAL_FR in d_err[blob]
+void launch_rc_interp(const uint8_t *d_cells, int n_cells, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_u, int *d_err,
+                      hipStream_t st);
+// d_coef (or null): m * 4096 Fr, the layout launch_cc_columns reads; want_cells: d_u receives P_r(a_k) for all 128 cells
+void launch_rc_columns(Fr *d_u, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_coef, bool want_cells, hipStream_t st);
+void launch_rc_cells(const Fr *d_u, int m, const CellComputeConsts *d_cc, uint8_t *d_cells /* m * 128 * 2048 */, hipStream_t st);
+
 }  // namespace kzg

@@ -563,6 +563,56 @@ class Kzg:
         """One independent compute_cells_and_kzg_proofs per blob in one call: a list of (cells, proofs) tuples or Error."""
         return Kzg._compute_cells(blobs, s, True, True)
 
+    # ---- EIP-7594 recovery: all cells and proofs of a blob from at least half of its cells (recover_cells_and_kzg_proofs) ----
+    @staticmethod
+    def _recover(cell_indices, rows, s, cells, proofs):
+        ix = [int(i) for i in cell_indices]
+        rw = [[_b(x, Cell) for x in row] for row in rows]
+        n, m = len(ix), len(rw)
+        if any(len(row) != n for row in rw):
+            raise BadArgs("length mismatch")
+        if any(i < 0 or i >= 1 << 64 for i in ix):
+            raise BadArgs("cell index out of range")
+        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(m, 1)) if cells else None
+        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1)) if proofs else None
+        st = (C.c_int * max(m, 1))()
+        idx = (C.c_size_t * max(n, 1))(*ix)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_many(c_out, p_out, st, idx, b"".join(b"".join(row) for row in rw), n, m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs")
+        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
+        praw = p_out.raw if proofs else b""
+        res = []
+        for i in range(m):
+            if st[i] != 0:
+                res.append(_ERRORS.get(st[i], InternalError)("recover_cells"))
+                continue
+            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
+            pb = 48 * CELLS_PER_EXT_BLOB * i
+            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
+                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
+        return res
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs(cell_indices, cells, s):
+        """([Cell] * 128, [KzgProof] * 128) of the blob from 64..128 of its cells at the strictly ascending cell_indices; BadArgs on anything else."""
+        if len(cell_indices) != len(cells):
+            raise BadArgs("length mismatch")
+        return Kzg._one(Kzg._recover(cell_indices, [cells], s, True, True))
+
+    @staticmethod
+    def recover_cells(cell_indices, cells, s):
+        """The 128 cells alone (no proof is computed and no proof setup built)."""
+        if len(cell_indices) != len(cells):
+            raise BadArgs("length mismatch")
+        return Kzg._one(Kzg._recover(cell_indices, [cells], s, True, False))[0]
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_many(cell_indices, rows, s):
+        """rows: one list of cells per blob, every blob known at the same cell_indices; one independent recover_cells_and_kzg_proofs per blob in
+        one call.  Returns a list of (cells, proofs) tuples or Error."""
+        return Kzg._recover(cell_indices, rows, s, True, True)
+
     @staticmethod
     def debug_cell_compute_h(blobs, s):
         """FK20 intermediates per blob: H_0 .. H_63 compressed (H_63 is the point at infinity), or Error."""

@@ -92,6 +92,11 @@ extern "C" {
     pub fn kzg355_compute_cells_and_kzg_proofs(cells_out: *mut u8, proofs_out: *mut u8, blob: *const u8, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_compute_cells_and_kzg_proofs_many(cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int, blobs: *const u8, n: usize,
                                                     s: *const kzg355_settings) -> c_int;
+    // EIP-7594 recovery: cell_indices n (64..128, strictly ascending), cells n*2048 (m*n*2048, blob after blob, one index set for all blobs)
+    pub fn kzg355_recover_cells_and_kzg_proofs(cells_out: *mut u8, proofs_out: *mut u8, cell_indices: *const usize, cells: *const u8, n: usize,
+                                               s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_cells_and_kzg_proofs_many(cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int, cell_indices: *const usize, cells: *const u8,
+                                                    n: usize, m: usize, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_kzg_proof_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize,
                                         s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_blob_kzg_proof_many(ok: *mut bool, status: *mut c_int, blobs: *const u8, commitments: *const u8, proofs: *const u8, n: usize,

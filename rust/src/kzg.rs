@@ -471,6 +471,52 @@ impl Kzg {
             .collect())
     }
 
+    /// EIP-7594 `recover_cells_and_kzg_proofs`: all 128 cells and proofs of a blob from 64..128 of its cells at strictly ascending `cell_indices`.
+    pub fn recover_cells_and_kzg_proofs(cell_indices: &[usize], cells: &[Cell], s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
+        if cell_indices.len() != cells.len() {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let mut res = Self::recover_cells_and_kzg_proofs_many(cell_indices, cells, 1, s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// `m` blobs known at the same `cell_indices` (`cells`: blob after blob, `cell_indices.len()` cells each) in one set of launches; one `Result`
+    /// per blob.
+    pub fn recover_cells_and_kzg_proofs_many(
+        cell_indices: &[usize],
+        cells: &[Cell],
+        m: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let n = cell_indices.len();
+        if cells.len() != n * m {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let input: Vec<u8> = cells.iter().flat_map(|x| x.iter().copied()).collect();
+        let per_cells = BYTES_PER_CELL * CELLS_PER_EXT_BLOB;
+        let mut out_cells = vec![0u8; per_cells * m.max(1)];
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * m.max(1)];
+        let mut st = vec![0i32; m.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_recover_cells_and_kzg_proofs_many(out_cells.as_mut_ptr(), proofs.as_mut_ptr(), st.as_mut_ptr(), cell_indices.as_ptr(),
+                                                          input.as_ptr(), n, m, s.raw)
+        };
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_many")?;
+        Ok((0..m)
+            .map(|i| {
+                check(st[i], "recover_cells")?;
+                let cs = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| Cell::from_bytes(&out_cells[per_cells * i + BYTES_PER_CELL * k..per_cells * i + BYTES_PER_CELL * (k + 1)]))
+                    .collect::<Result<Vec<_>, _>>()?;
+                let base = BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * i;
+                let ps = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[base + 48 * k..base + 48 * (k + 1)]).unwrap()))
+                    .collect();
+                Ok((cs, ps))
+            })
+            .collect())
+    }
+
     /// `commitments.len()` independent `verify_kzg_proof` checks (one proof per call is what benches/kzg_benches.rs:70-81 times).
     pub fn verify_kzg_proof_many(
         commitments: &[KzgCommitment],
