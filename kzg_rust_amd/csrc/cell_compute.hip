@@ -1,12 +1,13 @@
 // cell_compute.hip -- the C entry points of compute_cells_and_kzg_proofs (EIP-7594 cells; include/kzg355.h) and the per-handle setup they need
 // (host side of libkzg355.so; see engine.h).  The host copies blobs in and cells / proofs out and sets the statuses; every field and group
-// operation runs in the kernels of k_cell_compute.hip, one set of launches per chunk of blobs.
+// operation runs in the kernels of k_cell_compute.hip, one set of launches per chunk of blobs.  The chunk loop (cc_run) also serves
+// recover_cells_and_kzg_proofs (cell_recover.hip), and the builder of the monomial points the setup of verify_cell_kzg_proof_batch (cells.hip).
 #include "engine.h"
 
 namespace kzg355_impl {
 
 // Constants of the field stage (w4096 powers, twiddle splits): the first compute call of a handle.  Under cc_mu.
-int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
+static int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cc_mu);
     if (s->cc_consts_ready) return KZG355_OK;
     int rc;
@@ -18,52 +19,68 @@ int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
     return KZG355_OK;
 }
 
-// The proof setup, on the first call that wants proofs (after ensure_cc_consts): the monomial points [tau^t]_1, t < 4096, as commitments of
-// the "blobs" (w_i^t)_i through the 8-bit fixed-base MSM, 64 at a time; X_r = NTT128(x_r) and their comb table.  Under cc_mu.
-int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
+// The monomial points [tau^t]_1 = sum_i w_i^t [L_i(tau)]_1, t < count (a multiple of 64), for the setups of the cell paths: the commitments of the
+// "blobs" (w_i^t)_i through the 8-bit fixed-base MSM of the commitment path, 64 at a time, compressed into d_mono48 and decoded into d_mono.  The
+// scratch is this function's own and is released on every path; the caller holds its setup mutex and owns the two buffers.
+int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono) {
+    DevBuf scal, digits, partials, err;
+    auto done = [&](int rc) { for (DevBuf *b : {&scal, &digits, &partials, &err}) b->release(); return rc; };
+    int rc;
+    if ((rc = scal.ensure(sizeof(Fr) * CELL_FE * N_FE)) || (rc = digits.ensure((size_t)CELL_FE * MSM_WINDOWS * N_FE)) ||
+        (rc = partials.ensure(sizeof(G1Jac) * CELL_FE * MSM_WINDOWS)) || (rc = err.ensure(sizeof(int))))
+        return done(rc);
+    hipStream_t st = w->stream;
+    auto hip_fail = [&]() { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return done(KZG355_DEVICE_ERROR); };
+    if (hipMemsetAsync(err.p, 0, sizeof(int), st) != hipSuccess) return hip_fail();
+    for (int t0 = 0; t0 < count; t0 += CELL_FE) launch_monomial_chunk(s->t, t0, scal.as<Fr>(), digits.as<uint8_t>(), partials.as<G1Jac>(), d_mono48, st);
+    launch_monomial_decode(d_mono48, count, d_mono, err.as<int>(), st);
+    int herr = 0;
+    uint8_t first[48];
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(first, d_mono48, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return hip_fail();
+    // [tau^0]_1 = sum_i [L_i(tau)]_1 = G1: the derived points start at the generator whatever the ceremony
+    if (herr || memcmp(first, G1_GEN, 48) != 0) return done(KZG355_INTERNAL);
+    return done(KZG355_OK);
+}
+
+// The proof setup, on the first call that wants proofs (after ensure_cc_consts): the 4096 monomial points, X_r = NTT128(x_r) and their comb table.
+// Under cc_mu.  A failure releases what was being filled; every failure but NO_MEMORY is remembered (engine.h, at cc_mu).
+static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cc_mu);
     if (s->cc_proof_ready) return s->cc_proof_rc;
-    DevBuf scal, digits, partials, X, err;
+    DevBuf X;
     auto done = [&](int rc) {
-        for (DevBuf *b : {&scal, &digits, &partials, &X, &err}) b->release();
-        if (rc == KZG355_NO_MEMORY) {                              // not remembered: a later call may find the memory
-            for (DevBuf *b : {&s->cc_mono48, &s->cc_mono, &s->cc_table}) b->release();
-            return rc;
-        }
+        X.release();
+        if (rc != KZG355_OK) for (DevBuf *b : {&s->cc_mono48, &s->cc_mono, &s->cc_table}) b->release();
+        if (rc == KZG355_NO_MEMORY) return rc;                     // not remembered: a later call may find the memory
         s->cc_proof_ready = true;
         s->cc_proof_rc = rc;
         return rc;
     };
     int rc;
     if ((rc = s->cc_mono48.ensure(48 * (size_t)N_FE)) || (rc = s->cc_mono.ensure(sizeof(G1Affine) * N_FE)) ||
-        (rc = s->cc_table.ensure(sizeof(G1Affine) * CC_TABLE_ENTRIES)) || (rc = scal.ensure(sizeof(Fr) * CELL_FE * N_FE)) ||
-        (rc = digits.ensure((size_t)CELL_FE * MSM_WINDOWS * N_FE)) || (rc = partials.ensure(sizeof(G1Jac) * CELL_FE * MSM_WINDOWS)) ||
-        (rc = X.ensure(sizeof(G1Jac) * CC_POINTS)) || (rc = err.ensure(sizeof(int))))
+        (rc = s->cc_table.ensure(sizeof(G1Affine) * CC_TABLE_ENTRIES)) || (rc = X.ensure(sizeof(G1Jac) * CC_POINTS)) ||
+        (rc = build_monomial_points(s, w, N_FE, s->cc_mono48.as<uint8_t>(), s->cc_mono.as<G1Affine>())))
         return done(rc);
-    hipStream_t st = w->stream;
-    auto hip_fail = [&]() { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return done(KZG355_DEVICE_ERROR); };
-    if (hipMemsetAsync(err.p, 0, sizeof(int), st) != hipSuccess) return hip_fail();
-    for (int t0 = 0; t0 < N_FE; t0 += CELL_FE)
-        launch_cc_monomial_chunk(s->t, t0, scal.as<Fr>(), digits.as<uint8_t>(), partials.as<G1Jac>(), s->cc_mono48.as<uint8_t>(), st);
-    launch_cc_setup_points(s->cc_mono48.as<uint8_t>(), s->cc_mono.as<G1Affine>(), s->cc_consts.as<CellComputeConsts>(), X.as<G1Jac>(),
-                           s->cc_table.as<G1Affine>(), err.as<int>(), st);
-    int herr = 0;
-    uint8_t first[48];
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(first, s->cc_mono48.p, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return hip_fail();
-    // [tau^0]_1 = sum_i [L_i(tau)]_1 = G1 whatever the ceremony
-    static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
-                                       0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
-                                       0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
-    if (herr || memcmp(first, G1_GEN, 48) != 0) return done(KZG355_INTERNAL);
+    launch_cc_setup_points(s->cc_mono.as<G1Affine>(), s->cc_consts.as<CellComputeConsts>(), X.as<G1Jac>(), s->cc_table.as<G1Affine>(), w->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(w->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(w->stream); (void)hipGetLastError();
+        return done(KZG355_DEVICE_ERROR);
+    }
     return done(KZG355_OK);
 }
 
-// The device chain behind the field stage, shared with recover_cells_and_kzg_proofs (cell_recover.hip), whose field stage leaves the same two
-// things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role: y = coefficients, scal_a = column scalars,
-// partials = Z, q = cells, out48 = proofs, small = H.
-int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h) {
+// a call refused as a whole: every unit gets the code the call returns
+int cc_refuse(int *status, size_t units, int code) {
+    if (status) for (size_t i = 0; i < units; i++) status[i] = code;
+    return code;
+}
+
+// The device chain behind the field stage.  compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_recover.hip) differ in their field
+// stage only, and both leave the same two things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role:
+// y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H.
+static int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h) {
     int rc;
     if ((rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
         (want_cells && (rc = w->q.ensure((size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * CH))) ||
@@ -74,7 +91,7 @@ int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs,
     return KZG355_OK;
 }
 // coefficients of m blobs in w->y -> proofs in w->out48 (and H in w->small), queued on w->stream
-void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h) {
+static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h) {
     const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
     hipStream_t st = w->stream;
     tm.begin("cc_columns");
@@ -88,7 +105,7 @@ void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool wan
     tm.end();
 }
 // the results of a chunk of m blobs (blob c0 onwards) back to the host, the wait, and the per-blob statuses
-int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first) {
+static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first) {
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     hipStream_t st = w->stream;
     HIPCHK(hipGetLastError());
@@ -107,13 +124,14 @@ int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proof
     return KZG355_OK;
 }
 
+// What the two calls share once the caller has checked its own arguments (`units` > 0 blobs, some output wanted): the remaining refusals, the
+// setups, and the chunk loop.  `reserve` sizes the caller's own workspace buffers for CH blobs; `stage` copies the input of blobs c0 .. c0 + m - 1
+// in and queues the kernels that leave their coefficients in w->y (when proofs or H are wanted) and their cells in w->q (when cells are).
 // cells_out / proofs_out / h_dbg: host memory (any may be null, not all); status (or null): per blob.
-static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs) {
-    auto refuse = [&](int code) { if (status) for (size_t i = 0; i < n; i++) status[i] = code; return code; };
-    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return refuse(KZG355_BADARGS);
-    if (n == 0) return KZG355_OK;
-    if (!blobs) return refuse(KZG355_BADARGS);
-    if (n > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
+int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
+           const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int)> &stage) {
+    auto refuse = [&](int code) { return cc_refuse(status, units, code); };
+    if (units > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
     if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
     WsGuard g(cs);
     if (!g.w) return refuse(KZG355_NO_DEVICE);
@@ -122,29 +140,40 @@ static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int 
     int rc;
     if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
     if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
-    const size_t CH = n < CC_CHUNK ? n : CC_CHUNK;
-    if ((rc = w->blobs.ensure((size_t)BLOB_BYTES * CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg))) return refuse(rc);
-    const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
-    hipStream_t st = w->stream;
+    const size_t CH = units < CC_CHUNK ? units : CC_CHUNK;
+    if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg))) return refuse(rc);
     Timed tm(s, w);
     int first = KZG355_OK;
     auto run = [&]() -> int {                                     // (HIPCHK returns from here: a failed chunk refuses the whole call)
-    for (size_t c0 = 0; c0 < n; c0 += CH) {
-        const int m = (int)(n - c0 < CH ? n - c0 : CH);
+    for (size_t c0 = 0; c0 < units; c0 += CH) {
+        const int m = (int)(units - c0 < CH ? units - c0 : CH);
         w->in_flight = true;
-        HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * m, st));
-        HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, st));
-        tm.begin("cc_field");
-        launch_cc_field(w->blobs.as<uint8_t>(), m, cc, want_proofs ? w->y.as<Fr>() : nullptr, cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), st);
-        tm.end();
-        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg);
+        HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * m, w->stream));
         int crc;
+        if ((crc = stage(w, tm, c0, m))) return crc;
+        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg);
         if ((crc = cc_collect_chunk(w, tm, cells_out, proofs_out, h_dbg, status, c0, m, first))) return crc;
     }
     return KZG355_OK;
     };
     if ((rc = run())) return refuse(rc);
     return first;
+}
+
+static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs) {
+    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return cc_refuse(status, n, KZG355_BADARGS);
+    if (n == 0) return KZG355_OK;
+    if (!blobs) return cc_refuse(status, n, KZG355_BADARGS);
+    return cc_run(cs, n, cells_out, proofs_out, h_dbg, status,
+        [](Workspace *w, size_t CH) { return w->blobs.ensure((size_t)BLOB_BYTES * CH); },
+        [&](Workspace *w, Timed &tm, size_t c0, int m) -> int {
+            HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, w->stream));
+            tm.begin("cc_field");
+            launch_cc_field(w->blobs.as<uint8_t>(), m, cs->cc_consts.as<CellComputeConsts>(), proofs_out || h_dbg ? w->y.as<Fr>() : nullptr,
+                            cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), w->stream);
+            tm.end();
+            return KZG355_OK;
+        });
 }
 
 }  // namespace kzg355_impl

@@ -13,25 +13,26 @@ static const size_t CELL_MAX_CELLS = (size_t)1 << 18;   // cells per call (512 M
 
 static void put_u64be(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (56 - 8 * i)); }
 
-// The first cell call of a handle: constants, the 64 monomial points [tau^t]_1 = sum_i w_i^t [L_i(tau)]_1 (the commitments of the "blobs" of the
-// domain points' t-th powers, through the 8-bit fixed-base MSM of the commitment path), and the line table of [tau^64]_2.  Under cell_mu.
+// The first cell call of a handle: constants, the 64 monomial points [tau^t]_1 (build_monomial_points, cell_compute.hip) and the line table of
+// [tau^64]_2.  Under cell_mu.  A failure releases what was being filled and is not remembered: the next call tries again (engine.h, at cell_mu).
 static int ensure_cell_setup(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cell_mu);
-    if (s->cell_ready) return s->cell_rc;
-    DevBuf mono_scal, digits, partials, err, g2b;
+    if (s->cell_ready) return KZG355_OK;
+    DevBuf err, g2b;
     auto done = [&](int rc) {
-        for (DevBuf *b : {&mono_scal, &digits, &partials, &err, &g2b}) b->release();
-        if (rc == KZG355_OK) s->cell_ready = true;
-        s->cell_rc = rc;
+        for (DevBuf *b : {&err, &g2b}) b->release();
+        if (rc != KZG355_OK)
+            for (DevBuf *b : {&s->cell_consts, &s->cell_mono, &s->cell_mono48, &s->cell_lines, &s->cell_lines_w, &s->cell_lines_inf}) b->release();
+        s->cell_ready = rc == KZG355_OK;
         return rc;
     };
     int rc;
     if ((rc = s->cell_consts.ensure(sizeof(CellConsts))) || (rc = s->cell_mono.ensure(sizeof(G1Affine) * CELL_FE)) ||
         (rc = s->cell_mono48.ensure(48 * CELL_FE)) || (rc = s->cell_lines.ensure(sizeof(LineCoeff) * 3 * N_LINES)) ||
         (rc = s->cell_lines_w.ensure(sizeof(LineW) * 3 * N_LINES)) || (rc = s->cell_lines_inf.ensure(sizeof(int) * 3)) ||
-        (rc = mono_scal.ensure(sizeof(Fr) * CELL_FE * N_FE)) || (rc = digits.ensure((size_t)CELL_FE * MSM_WINDOWS * N_FE)) ||
-        (rc = partials.ensure(sizeof(G1Jac) * CELL_FE * MSM_WINDOWS)) || (rc = err.ensure(sizeof(int))) || (rc = g2b.ensure(96)))
-        return rc;                                               // (not remembered: a later call may find the memory)
+        (rc = err.ensure(sizeof(int))) || (rc = g2b.ensure(96)) ||
+        (rc = build_monomial_points(s, w, CELL_FE, s->cell_mono48.as<uint8_t>(), s->cell_mono.as<G1Affine>())))
+        return done(rc);
     hipStream_t st = w->stream;
     auto hip_fail = [&]() { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return done(KZG355_DEVICE_ERROR); };
     // slots 0 and 1 as the blob path has them (slot 0: G2 generator), slot 2 rebuilt from g2[64]
@@ -43,20 +44,13 @@ static int ensure_cell_setup(kzg355_settings *s, Workspace *w) {
     ct.lines = s->cell_lines.as<LineCoeff>();
     ct.lines_w = s->cell_lines_w.as<LineW>();
     ct.lines_inf = s->cell_lines_inf.as<int>();
-    launch_cell_setup(g2b.as<uint8_t>(), s->t, s->cell_consts.as<CellConsts>(), mono_scal.as<Fr>(), digits.as<uint8_t>(), partials.as<G1Jac>(),
-                      s->cell_mono48.as<uint8_t>(), s->cell_mono.as<G1Affine>(), ct.lines, ct.lines_inf, err.as<int>(), st);
+    launch_cell_setup(g2b.as<uint8_t>(), s->cell_consts.as<CellConsts>(), ct.lines, ct.lines_inf, err.as<int>(), st);
     launch_lines_to_w(ct, st);
     int herr = 0;
-    uint8_t first[48];
-    if (hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(first, s->cell_mono48.p, 48, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+    if (hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
         hipGetLastError() != hipSuccess)
         return hip_fail();
-    // [tau^0]_1 = sum_i [L_i(tau)]_1 = G1: the derived prefix starts at the generator whatever the ceremony
-    static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
-                                       0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
-                                       0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
-    if (herr || memcmp(first, G1_GEN, 48) != 0) return done(KZG355_INTERNAL);
+    if (herr) return done(KZG355_INTERNAL);                        // (load validated g2[64]: its bytes decode)
     s->cell_t = ct;
     return done(KZG355_OK);
 }

@@ -223,15 +223,17 @@ struct kzg355_settings {
     int wide_rc = KZG355_OK;                  // what building it returned (msm_require_wide: a failure fails the calls that need it)
     // EIP-7594 cell calls (cells.hip): setup g2[64] = [tau^64]_2 as loaded (load validated it); what the check needs beyond the blob path -- the
     // constants, the 64 monomial points [tau^t]_1 and a line table whose slot 2 holds the lines of [tau^64]_2 -- is built on the first cell call,
-    // under cell_mu, and `cell_t` is then the handle's tables with that line table in place of the blob path's
+    // under cell_mu, and `cell_t` is then the handle's tables with that line table in place of the blob path's.  A setup that fails releases the
+    // buffers it was filling and is not remembered: cell_ready stays unset and the next cell call tries again.
     uint8_t g2_tau64[96] = {};
     std::mutex cell_mu;
     bool cell_ready = false;
-    int cell_rc = KZG355_OK;
     DeviceTables cell_t{};
     DevBuf cell_consts, cell_mono, cell_mono48, cell_lines, cell_lines_w, cell_lines_inf;
     // compute_cells_and_kzg_proofs (cell_compute.hip): the field-stage constants, then -- first call that wants proofs -- the 4096 monomial points
-    // and the FK20 comb table (CC_TABLE_ENTRIES affine points), each built once under cc_mu; a NO_MEMORY failure is not remembered
+    // and the FK20 comb table (CC_TABLE_ENTRIES affine points), each built once under cc_mu.  A failed proof setup releases its buffers like the
+    // one above, but is remembered in cc_proof_rc unless it was NO_MEMORY (a later call may find the memory).  The two setups came with different
+    // rules for what they remember; folding their point builder into one kept each rule as it was, on purpose, so that no caller sees another status.
     std::mutex cc_mu;
     bool cc_consts_ready = false, cc_proof_ready = false;
     int cc_proof_rc = KZG355_OK;
@@ -345,6 +347,11 @@ struct HostCall {
     uint8_t *ys_out = nullptr;       // kind 3: units x 32 bytes, y = p(z) of every unit whose status is OK
 };
 
+// the G1 generator, compressed: what every setup's derived points are checked against (the load-time self-test, the cell setups)
+static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
+                                   0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
+                                   0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
+
 // ---- shared functions (definitions: see the file list at the top)
 extern thread_local bool tl_msm_inner;      // this thread is inside the table build (or the load-time self-test): its MSM calls take the handle as it is
 extern thread_local const kzg355_settings::WidePub *tl_wide_candidate;   // ... and, while the builder checks it, the table that is not published yet
@@ -388,13 +395,13 @@ int msm_op_many_device_impl(uint8_t *out, int *status, const uint8_t *d_blobs, c
 int stage_to_device(Workspace *w, DevBuf &dst, const uint8_t *src, size_t bytes);
 int stage_via_pinned(kzg355_settings *s, Workspace *w, PinBuf &pin, size_t pin_off, DevBuf &dst, const uint8_t *src, size_t bytes);
 int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs);
-// compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_compute.hip; the second call's own stage: cell_recover.hip)
+// cell_compute.hip: the monomial points of the cell setups (also cells.hip), and what compute_cells_and_kzg_proofs and
+// recover_cells_and_kzg_proofs (cell_recover.hip: its own field stage) share
 static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
-int ensure_cc_consts(kzg355_settings *s, Workspace *w);
-int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w);
-int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h);
-void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h);
-int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first);
+int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
+int cc_refuse(int *status, size_t units, int code);
+int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
+           const std::function<int(Workspace *, size_t CH)> &reserve, const std::function<int(Workspace *, Timed &, size_t c0, int m)> &stage);
 
 }  // namespace kzg355_impl
 

@@ -15,17 +15,16 @@
 // the proofs come out of the last dif in cell order.  tests/fk20_spec.py restates this route over Fr.
 #define KZG_FP_MUL_NOINLINE 1
 #include "kernels.h"
+#include "cell_domain.h"
 
 namespace kzg {
-
-__device__ __forceinline__ uint32_t cc_rev12(uint32_t j) { return __brev(j) >> 20; }
 
 // ---- setup: constants
 // thread e < 4096: w4096^e from the handle's bit-reversed root table; threads e < 128 also the GLV halves of w128^e; thread 0 the scalars
 __global__ void __launch_bounds__(256) k_cc_consts(const Fr *roots, CellComputeConsts *cc) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N_FE) return;
-    const Fr v = roots[cc_rev12((uint32_t)e)];                       // roots[brp12(i)] = w4096^i
+    const Fr v = roots[rev<12>((uint32_t)e)];                      // roots[brp12(i)] = w4096^i
     cc->w4096[e] = v;
     if (e % (N_FE / CC_FFT) == 0) {
         uint32_t k[8]; fr_to_words(k, v);
@@ -33,7 +32,7 @@ __global__ void __launch_bounds__(256) k_cc_consts(const Fr *roots, CellComputeC
         glv_split_fast(cc->tw_a[t], cc->tw_b[t], k);
     }
     if (e == 0) {
-        const uint32_t wc[8] = {0xc78c8967u, 0x6fdd00bfu, 0x434906acu, 0x146b58bcu, 0x972e89edu, 0x2ccddea2u, 0x37b1da3du, 0x485d5127u};   // 7^((r-1)/8192)
+        const uint32_t wc[8] = FR_W8192_INIT;
         fr_from_words(cc->w8192, wc);
         Fr n = fr_zero(); const Fr one = fr_one();
         for (int i = 0; i < CC_FFT; i++) fr_add(n, n, one);
@@ -155,40 +154,16 @@ __global__ void __launch_bounds__(CC_FIELD_THREADS) k_cc_field(const uint8_t *bl
     if (bad) atomicOr(&err[b], ERR_NONCANONICAL_FR);
     __syncthreads();
     // inverse NTT (dit, root w4096^-1): natural-order coefficients times 4096
-    for (int h = 1; h < N_FE; h <<= 1) {
-        for (int q = tid; q < N_FE / 2; q += CC_FIELD_THREADS) {
-            const int j = q % h, s = (q / h) * 2 * h;
-            const int e = j * (N_FE / 2 / h);
-            Fr u = a[s + j], v = a[s + j + h];
-            if (e) fr_mul(v, v, cc->w4096[N_FE - e]);
-            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
-            a[s + j] = x; a[s + j + h] = y;
-        }
-        __syncthreads();
-    }
+    fr_dit_inv<N_FE, CC_FIELD_THREADS>(a, cc, tid);
     for (int m = tid; m < N_FE; m += CC_FIELD_THREADS) {
         Fr f; fr_mul(f, a[m], cc->inv4096);
         if (coef) coef[(size_t)N_FE * b + m] = f;
-        if (cells) {                                                  // f_m w^m, w^m = w4096^(m/2) (w if m is odd)
-            Fr t; fr_mul(t, f, cc->w4096[m >> 1]);
-            if (m & 1) fr_mul(t, t, cc->w8192);
-            a[m] = t;
-        }
+        if (cells) { Fr t; fr_mul(t, f, cell_wpow(cc, (uint32_t)m)); a[m] = t; }    // f_m w^m
     }
     if (!cells) return;
     __syncthreads();
     // coset NTT (dif, root w4096): position i holds p(w w4096^rev12(i)), i.e. element i of cells 64..127 read as one array
-    for (int h = N_FE / 2; h >= 1; h >>= 1) {
-        for (int q = tid; q < N_FE / 2; q += CC_FIELD_THREADS) {
-            const int j = q % h, s = (q / h) * 2 * h;
-            const int e = j * (N_FE / 2 / h);
-            Fr u = a[s + j], v = a[s + j + h];
-            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
-            if (e) fr_mul(y, y, cc->w4096[e]);
-            a[s + j] = x; a[s + j + h] = y;
-        }
-        __syncthreads();
-    }
+    fr_dif<N_FE, CC_FIELD_THREADS>(a, cc, tid);
     uint8_t *out = cells + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * b;
     const uint4 *src = reinterpret_cast<const uint4 *>(blob);         // cells 0..63: the blob itself
     uint4 *dst = reinterpret_cast<uint4 *>(out);
@@ -203,21 +178,8 @@ __global__ void __launch_bounds__(64) k_cc_columns(const Fr *coef, const CellCom
     a[L] = v;
     a[L + CC_FFT / 2] = fr_zero();
     __syncthreads();
-    for (int h = CC_FFT / 2; h >= 1; h >>= 1) {
-        const int j = L % h, s = (L / h) * 2 * h, e = j * (CC_FFT / 2 / h);
-        Fr u = a[s + j], w = a[s + j + h];
-        Fr x, y; fr_add(x, u, w); fr_sub(y, u, w);
-        if (e) fr_mul(y, y, cc->w4096[e * (N_FE / CC_FFT)]);
-        __syncthreads();
-        a[s + j] = x; a[s + j + h] = y;
-        __syncthreads();
-    }
-    for (int i = L; i < CC_FFT; i += CC_FFT / 2) {
-        uint32_t w[8]; fr_to_words(w, a[i]);
-        uint32_t *o = scal + 8 * (((size_t)b * CC_FFT + i) * CELL_FE + r);
-#pragma unroll
-        for (int k = 0; k < 8; k++) o[k] = w[k];
-    }
+    fr_dif<CC_FFT, CC_FFT / 2>(a, cc, L);
+    for (int i = L; i < CC_FFT; i += CC_FFT / 2) fr_store_words(scal + 8 * (((size_t)b * CC_FFT + i) * CELL_FE + r), a[i]);
 }
 // workgroup (blob, i), lane r: [C_r[i]] X_r[i] from the comb table (64 signed 4-bit digits in [-8, 7], one mixed addition each), then the
 // 64 lanes' sum -> Z[blob][i]
@@ -279,15 +241,16 @@ __global__ void __launch_bounds__(64) k_cc_proofs(const G1Jac *Z, const CellComp
 void launch_cc_consts(const Fr *d_roots, CellComputeConsts *d_cc, hipStream_t st) {
     hipLaunchKernelGGL(k_cc_consts, dim3(N_FE / 256), dim3(256), 0, st, d_roots, d_cc);
 }
-void launch_cc_monomial_chunk(DeviceTables t, int t0, Fr *d_scal, uint8_t *d_digits, G1Jac *d_partials, uint8_t *d_out48, hipStream_t st) {
+void launch_monomial_chunk(DeviceTables t, int t0, Fr *d_scal, uint8_t *d_digits, G1Jac *d_partials, uint8_t *d_out48, hipStream_t st) {
     hipLaunchKernelGGL(k_cc_mono_scalars, dim3(CELL_FE * N_FE / 256), dim3(256), 0, st, t.roots, t0, d_scal);
     launch_digits_from_fr(d_scal, CELL_FE, d_digits, st);
     launch_msm_bucket(d_digits, t, CELL_FE, d_partials, st);
     launch_msm_finalize(d_partials, CELL_FE, d_out48 + 48 * (size_t)t0, st);
 }
-void launch_cc_setup_points(const uint8_t *d_mono48, G1Affine *d_mono, const CellComputeConsts *d_cc, G1Jac *d_X, G1Affine *d_tab, int *d_err,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(k_cc_decode, dim3(N_FE / 64), dim3(64), 0, st, d_mono48, N_FE, d_mono, d_err);
+void launch_monomial_decode(const uint8_t *d_mono48, int count, G1Affine *d_mono, int *d_err, hipStream_t st) {
+    hipLaunchKernelGGL(k_cc_decode, dim3((count + 63) / 64), dim3(64), 0, st, d_mono48, count, d_mono, d_err);
+}
+void launch_cc_setup_points(const G1Affine *d_mono, const CellComputeConsts *d_cc, G1Jac *d_X, G1Affine *d_tab, hipStream_t st) {
     hipLaunchKernelGGL(k_cc_setup_fft, dim3(CELL_FE), dim3(64), 0, st, d_mono, d_cc, d_X);
     hipLaunchKernelGGL(k_cc_table, dim3(CC_POINTS * CC_WINDOWS / 64), dim3(64), 0, st, d_X, d_tab);
 }

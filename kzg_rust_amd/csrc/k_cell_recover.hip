@@ -18,51 +18,16 @@
 // polynomial of degree < 4096; they are dropped, as the spec drops the upper half of its quotient.  tests/recover_spec.py restates the route.
 #define KZG_FP_MUL_NOINLINE 1
 #include "kernels.h"
+#include "cell_domain.h"
 
 namespace kzg {
-
-__device__ __forceinline__ uint32_t rc_rev7(uint32_t j) { return __brev(j) >> 25; }
-// w^e for e < 8192 from the w4096 table
-__device__ __forceinline__ Fr rc_wpow(const CellComputeConsts *cc, uint32_t e) {
-    Fr v = cc->w4096[e >> 1];
-    if (e & 1u) fr_mul(v, v, cc->w8192);
-    return v;
-}
-// Transforms of N = 64 or 128 values in LDS by one wave: lane L < N / 2 takes one butterfly per stage (wN^e = w4096^(e 4096 / N)).
-// forward (root wN): natural in, bit-reversed out
-template <int N> __device__ void rc_dif(Fr *a, const CellComputeConsts *cc, int L) {
-    for (int h = N / 2; h >= 1; h >>= 1) {
-        if (L < N / 2) {
-            const int j = L % h, s = (L / h) * 2 * h, e = j * (N / 2 / h);
-            const Fr u = a[s + j], v = a[s + j + h];
-            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
-            if (e) fr_mul(y, y, cc->w4096[e * (N_FE / N)]);
-            a[s + j] = x; a[s + j + h] = y;
-        }
-        __syncthreads();
-    }
-}
-// inverse (root wN^-1, no 1/N): bit-reversed in, natural out
-template <int N> __device__ void rc_dit_inv(Fr *a, const CellComputeConsts *cc, int L) {
-    for (int h = 1; h < N; h <<= 1) {
-        if (L < N / 2) {
-            const int j = L % h, s = (L / h) * 2 * h, e = j * (N / 2 / h);
-            const Fr u = a[s + j];
-            Fr v = a[s + j + h];
-            if (e) fr_mul(v, v, cc->w4096[N_FE - e * (N_FE / N)]);
-            Fr x, y; fr_add(x, u, v); fr_sub(y, u, v);
-            a[s + j] = x; a[s + j + h] = y;
-        }
-        __syncthreads();
-    }
-}
 
 // once per call, thread k < 128: sd[k] = S(a_k) / (64 * 128), sci[k] = 1 / (128 S(g a_k)); pos[k] < 0 marks the missing cells
 __global__ void __launch_bounds__(CELLS_PER_EXT_BLOB) k_rc_vanish(const CellComputeConsts *cc, RecoverTables *rt) {
     __shared__ Fr a[CELLS_PER_EXT_BLOB];
     __shared__ int missing[CELLS_PER_EXT_BLOB];
     const int k = threadIdx.x;
-    a[k] = cc->w4096[(N_FE / CC_FFT) * rc_rev7((uint32_t)k)];
+    a[k] = cc->w4096[(N_FE / CC_FFT) * rev<7>((uint32_t)k)];
     missing[k] = rt->pos[k] < 0;
     __syncthreads();
     Fr ga; fr_mul(ga, a[k], cc->w8192);
@@ -90,10 +55,10 @@ __global__ void __launch_bounds__(CELL_FE) k_rc_interp(const uint8_t *cells, int
     if (!fr_from_be32_checked(v, cells + ((size_t)b * n + p) * CELL_BYTES + 32 * t)) atomicOr(&err[b], ERR_NONCANONICAL_FR);
     a[t] = v;                                                       // p(h_k w64^rev6(t)): bit-reversed order, as dit wants it
     __syncthreads();
-    rc_dit_inv<CELL_FE>(a, cc, t);
-    const uint32_t e = (rc_rev7((uint32_t)k) * (uint32_t)t) & 8191u;   // h_k^-t = w^(8192 - e)
+    fr_dit_inv<CELL_FE, CELL_FE>(a, cc, t);
+    const uint32_t e = (rev<7>((uint32_t)k) * (uint32_t)t) & 8191u;   // h_k^-t = w^(8192 - e)
     v = a[t];
-    if (e) { const Fr hp = rc_wpow(cc, 8192u - e); fr_mul(v, v, hp); }
+    if (e) { const Fr hp = cell_wpow(cc, 8192u - e); fr_mul(v, v, hp); }
     u[((size_t)b * CELLS_PER_EXT_BLOB + k) * CELL_FE + t] = v;
 }
 // workgroup (blob, column r): see the head of the file.  u is read at [blob][k][r] for the known k and, when cells are wanted, written there
@@ -108,23 +73,23 @@ __global__ void __launch_bounds__(CELL_FE) k_rc_columns(Fr *u, const CellCompute
         a[k] = v;
     }
     __syncthreads();
-    rc_dit_inv<CC_FFT>(a, cc, L);                                   // coefficients of P_r S
+    fr_dit_inv<CC_FFT, CC_FFT / 2>(a, cc, L);                                   // coefficients of P_r S
     for (int i = L; i < CC_FFT; i += CC_FFT / 2)
-        if (i) { Fr v; const Fr g = rc_wpow(cc, (uint32_t)i); fr_mul(v, a[i], g); a[i] = v; }
+        if (i) { Fr v; const Fr g = cell_wpow(cc, (uint32_t)i); fr_mul(v, a[i], g); a[i] = v; }
     __syncthreads();
-    rc_dif<CC_FFT>(a, cc, L);                                       // (P_r S)(g a_k)
+    fr_dif<CC_FFT, CC_FFT / 2>(a, cc, L);                                       // (P_r S)(g a_k)
     for (int k = L; k < CC_FFT; k += CC_FFT / 2) { Fr v; fr_mul(v, a[k], rt->sci[k]); a[k] = v; }
     __syncthreads();
-    rc_dit_inv<CC_FFT>(a, cc, L);                                   // P_r[i] g^i
+    fr_dit_inv<CC_FFT, CC_FFT / 2>(a, cc, L);                                   // P_r[i] g^i
     Fr f = a[L];
-    if (L) { const Fr g = rc_wpow(cc, 8192u - (uint32_t)L); fr_mul(f, f, g); }
+    if (L) { const Fr g = cell_wpow(cc, 8192u - (uint32_t)L); fr_mul(f, f, g); }
     if (coef) coef[(size_t)N_FE * b + CELL_FE * L + r] = f;
     if (!want_cells) return;
     __syncthreads();
     a[L] = f;
     a[L + CC_FFT / 2] = fr_zero();
     __syncthreads();
-    rc_dif<CC_FFT>(a, cc, L);                                       // P_r(a_k), k in cell order
+    fr_dif<CC_FFT, CC_FFT / 2>(a, cc, L);                                       // P_r(a_k), k in cell order
     for (int k = L; k < CC_FFT; k += CC_FFT / 2) col[(size_t)k * CELL_FE] = a[k];
 }
 // workgroup (blob, cell k): the cell's elements from u[blob][k][r] = P_r(a_k)
@@ -132,11 +97,11 @@ __global__ void __launch_bounds__(CELL_FE) k_rc_cells(const Fr *u, const CellCom
     __shared__ Fr a[CELL_FE];
     const int k = blockIdx.x % CELLS_PER_EXT_BLOB, r = threadIdx.x;
     Fr v = u[(size_t)blockIdx.x * CELL_FE + r];
-    const uint32_t e = rc_rev7((uint32_t)k) * (uint32_t)r;          // h_k^r = w^e, e <= 127 * 63
-    if (e) { const Fr hp = rc_wpow(cc, e); fr_mul(v, v, hp); }
+    const uint32_t e = rev<7>((uint32_t)k) * (uint32_t)r;          // h_k^r = w^e, e <= 127 * 63
+    if (e) { const Fr hp = cell_wpow(cc, e); fr_mul(v, v, hp); }
     a[r] = v;
     __syncthreads();
-    rc_dif<CELL_FE>(a, cc, r);
+    fr_dif<CELL_FE, CELL_FE>(a, cc, r);
     fr_to_be32(cells + (size_t)blockIdx.x * CELL_BYTES + 32 * r, a[r]);
 }
 

@@ -12,11 +12,9 @@
 // multiplication per term (255-bit scalars) and a tree per group and side: the 4844 lincomb families have their scalar layout baked in.
 #define KZG_FP_MUL_NOINLINE 1
 #include "kernels.h"
+#include "cell_domain.h"
 
 namespace kzg {
-
-__device__ __forceinline__ uint32_t rev6(uint32_t j) { return __brev(j) >> 26; }
-__device__ __forceinline__ uint32_t rev7(uint32_t j) { return __brev(j) >> 25; }
 
 __device__ __forceinline__ Fr fr_pow_small(const Fr &base, uint32_t e) {
     Fr acc = fr_one();
@@ -26,19 +24,14 @@ __device__ __forceinline__ Fr fr_pow_small(const Fr &base, uint32_t e) {
     }
     return acc;
 }
-__device__ __forceinline__ void fr_store_words(uint32_t *dst, const Fr &a) {
-    uint32_t w[8]; fr_to_words(w, a);
-#pragma unroll
-    for (int i = 0; i < 8; i++) dst[i] = w[i];
-}
 
 // ---- setup (once per handle, on the first cell call)
 // thread c < 128: h_c^64 and the shifts h_c^-t / 64; threads < 64 also the inverse-DFT twiddles w64^-j
 __global__ void __launch_bounds__(128) k_cell_consts(CellConsts *cc) {
     const int c = threadIdx.x;
-    const uint32_t wc[8] = {0xc78c8967u, 0x6fdd00bfu, 0x434906acu, 0x146b58bcu, 0x972e89edu, 0x2ccddea2u, 0x37b1da3du, 0x485d5127u};   // 7^((r-1)/8192)
+    const uint32_t wc[8] = FR_W8192_INIT;
     Fr w; fr_from_words(w, wc);
-    const Fr h = fr_pow_small(w, rev7((uint32_t)c));
+    const Fr h = fr_pow_small(w, rev<7>((uint32_t)c));
     Fr h64 = h;
     for (int i = 0; i < 6; i++) fr_sqr(h64, h64);
     cc->h64[c] = h64;
@@ -54,20 +47,6 @@ __global__ void __launch_bounds__(128) k_cell_consts(CellConsts *cc) {
         Fr w64inv; fr_inv_fermat(w64inv, w64);
         cc->tw[c] = fr_pow_small(w64inv, (uint32_t)c);
     }
-}
-// scalars of the 64 "blobs" (w_i^t)_i whose commitments are the monomial points [tau^t]_1: roots is the bit-reversed blob domain
-__global__ void __launch_bounds__(256) k_cell_mono_scalars(const Fr *roots, Fr *out) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= CELL_FE * N_FE) return;
-    out[gid] = fr_pow_small(roots[gid % N_FE], (uint32_t)(gid / N_FE));
-}
-__global__ void __launch_bounds__(64) k_cell_decode_mono(const uint8_t *in48, G1Affine *mono, int *err) {
-    const int t = threadIdx.x;
-    uint8_t b[48];
-    for (int k = 0; k < 48; k++) b[k] = in48[48 * t + k];
-    G1Affine p;
-    if (g1_decompress(p, b) != 0) { atomicOr(err, ERR_SETUP_POINT); p = g1a_inf(); }
-    mono[t] = p;
 }
 // Miller-loop lines of setup g2[64] = [tau^64]_2 into slot 2 of a three-slot line table (the slot the pairing kernels pair the first point with)
 __global__ void __launch_bounds__(64) k_cell_lines(const uint8_t *g2_bytes, LineCoeff *lines, int *lines_inf, int *err) {
@@ -128,7 +107,7 @@ __global__ void __launch_bounds__(CELL_FE) k_cell_columns(const uint8_t *cells, 
         fr_add(acc, acc, v);
     }
     if (bad) atomicOr(&err[sg.x], ERR_NONCANONICAL_FR);
-    u[rev6((uint32_t)j)] = acc;
+    u[rev<6>((uint32_t)j)] = acc;
     __syncthreads();
     Fr q = fr_zero();
     for (int i = 0; i < CELL_FE; i++) { Fr t; fr_mul(t, u[i], tw[(i * j) & (CELL_FE - 1)]); fr_add(q, q, t); }
@@ -197,14 +176,8 @@ __global__ void __launch_bounds__(64) k_cell_finish(const G1Jac *sums, int group
 }
 
 // ---- launchers
-void launch_cell_setup(const uint8_t *d_g2_tau64, DeviceTables t, CellConsts *d_cc, Fr *d_mono_scal, uint8_t *d_digits, G1Jac *d_partials,
-                       uint8_t *d_mono48, G1Affine *d_mono, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st) {
+void launch_cell_setup(const uint8_t *d_g2_tau64, CellConsts *d_cc, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st) {
     hipLaunchKernelGGL(k_cell_consts, dim3(1), dim3(CELLS_PER_EXT_BLOB), 0, st, d_cc);
-    hipLaunchKernelGGL(k_cell_mono_scalars, dim3(CELL_FE * N_FE / 256), dim3(256), 0, st, t.roots, d_mono_scal);
-    launch_digits_from_fr(d_mono_scal, CELL_FE, d_digits, st);
-    launch_msm_bucket(d_digits, t, CELL_FE, d_partials, st);
-    launch_msm_finalize(d_partials, CELL_FE, d_mono48, st);
-    hipLaunchKernelGGL(k_cell_decode_mono, dim3(1), dim3(CELL_FE), 0, st, d_mono48, d_mono, d_err);
     hipLaunchKernelGGL(k_cell_lines, dim3(1), dim3(64), 0, st, d_g2_tau64, d_lines, d_lines_inf, d_err);
 }
 void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,

@@ -186,11 +186,8 @@ struct CellConsts {
     Fr shift[CELLS_PER_EXT_BLOB][CELL_FE];     // h_c^-t / 64
     Fr tw[CELL_FE];                            // w64^-j, w64 = w^128
 };
-// once per handle: the constants, the 64 monomial points [tau^t]_1 (8-bit fixed-base MSM over the Lagrange table; d_mono48 compressed, d_mono affine)
-// and the Miller-loop lines of setup g2[64] into slot 2 of d_lines / d_lines_inf.  Scratch: d_mono_scal 64 * 4096 Fr, d_digits 64 * 32 * 4096 bytes,
-// d_partials 64 * 32 G1Jac.
-void launch_cell_setup(const uint8_t *d_g2_tau64, DeviceTables t, CellConsts *d_cc, Fr *d_mono_scal, uint8_t *d_digits, G1Jac *d_partials,
-                       uint8_t *d_mono48, G1Affine *d_mono, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st);
+// once per handle: the constants and the Miller-loop lines of setup g2[64] into slot 2 of d_lines / d_lines_inf (bad g2 bytes: ERR_SETUP_POINT in d_err)
+void launch_cell_setup(const uint8_t *d_g2_tau64, CellConsts *d_cc, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st);
 // r per group (from the host digests), r^k (d_rpow: npg * groups), the proof scalars and the unique-commitment weights into d_scal
 // ([group][cell_terms(npg)][8 words]); d_r_be: 32 bytes of r per group
 void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,
@@ -216,12 +213,13 @@ struct CellComputeConsts {
     uint32_t tw_a[CC_FFT][4], tw_b[CC_FFT][4];               // GLV halves of w128^e (w128 = w4096^32): w128^e = a + b x^2
 };
 void launch_cc_consts(const Fr *d_roots, CellComputeConsts *d_cc, hipStream_t st);
-// monomial points [tau^t]_1, t = t0 .. t0 + 63, compressed into d_out48 + 48 t0 (8-bit fixed-base MSM over the Lagrange table).  Scratch:
-// d_scal 64 * 4096 Fr, d_digits 64 * 32 * 4096 bytes, d_partials 64 * 32 G1Jac.
-void launch_cc_monomial_chunk(DeviceTables t, int t0, Fr *d_scal, uint8_t *d_digits, G1Jac *d_partials, uint8_t *d_out48, hipStream_t st);
-// the 4096 monomial points decoded (d_mono), X_r = NTT128(x_r) (d_X: CC_POINTS G1Jac) and the comb table (d_tab: CC_TABLE_ENTRIES)
-void launch_cc_setup_points(const uint8_t *d_mono48, G1Affine *d_mono, const CellComputeConsts *d_cc, G1Jac *d_X, G1Affine *d_tab, int *d_err,
-                            hipStream_t st);
+// monomial points [tau^t]_1, t = t0 .. t0 + 63, compressed into d_out48 + 48 t0 (8-bit fixed-base MSM over the Lagrange table), for the setups of
+// all three cell paths.  Scratch: d_scal 64 * 4096 Fr, d_digits 64 * 32 * 4096 bytes, d_partials 64 * 32 G1Jac.
+void launch_monomial_chunk(DeviceTables t, int t0, Fr *d_scal, uint8_t *d_digits, G1Jac *d_partials, uint8_t *d_out48, hipStream_t st);
+// count compressed points -> affine (a point that does not decode: infinity and ERR_SETUP_POINT in d_err)
+void launch_monomial_decode(const uint8_t *d_mono48, int count, G1Affine *d_mono, int *d_err, hipStream_t st);
+// from the 4096 monomial points: X_r = NTT128(x_r) (d_X: CC_POINTS G1Jac) and the comb table (d_tab: CC_TABLE_ENTRIES)
+void launch_cc_setup_points(const G1Affine *d_mono, const CellComputeConsts *d_cc, G1Jac *d_X, G1Affine *d_tab, hipStream_t st);
 // per call: field stage (d_coef: n * 4096 Fr or null; d_cells: n * 128 * 2048 bytes or null; non-canonical elements -> ERR_NONCANONICAL_FR in d_err[blob]),
 // columns (d_scal: n * 128 * 64 * 8 words), fixed-base sums (d_Z: n * 128 G1Jac), G1 transforms (d_proofs48: n * 128 * 48; d_h_dbg: n * 64 * 48 or null)
 void launch_cc_field(const uint8_t *d_blobs, int n, const CellComputeConsts *d_cc, Fr *d_coef, uint8_t *d_cells, int *d_err, hipStream_t st);

@@ -166,10 +166,6 @@ int load_on_device(const uint8_t *g1_bytes, size_t n1, const uint8_t *g2_bytes, 
 // miscompiles one of them (DESIGN.md section 4
 // records such a case with hipcc 7.2 and four inlined G1 routines) into a load error instead of wrong verdicts.
 static int device_self_test(kzg355_settings *s) {
-    static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f,
-            0x97, 0x74, 0xb9, 0x05,
-                                       0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a,
-                                               0xdb, 0x22, 0xc6, 0xbb};
     const size_t n = (size_t)s->t.n_fe, BB = 32 * n;
     DevBuf blobs;
     int rc = blobs.ensure(2 * BB);
