@@ -380,6 +380,39 @@ int kzg355_recover_cells_and_kzg_proofs_many(uint8_t *cells_out /* m*128*2048 or
 int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
 /* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */
 int kzg355_debug_cell_setup_monomial_all(uint8_t *out /* 4096*48 */, const kzg355_settings *s);
+/* ---- EIP-7594 cell calls on device-resident data -------------------------------------------------------------------------------------------
+ * The three *_many cell calls with their bulk arguments in HBM: every d_* argument is a DEVICE pointer on the handle's device (its first device,
+ * for a handle over several), ok / status are host pointers, and the calls are synchronous like the other *_device calls.  Layouts, NULL-output
+ * meanings, per-unit status, "a refusal of the whole call marks every unit", the n == 0 / m == 0 / groups == 0 / n_per_group == 0 cases and every
+ * KZG355_BADARGS rule are those of the host forms above.  Device byte buffers (commitments, cells, proofs, blobs, outputs) must be 16-byte
+ * aligned and device cell indices 8-byte aligned (hipMalloc and torch allocations are); a misaligned pointer is KZG355_BADARGS.  Output buffers
+ * must not overlap the inputs.  Nothing but the 4-byte status words (and the verdicts) crosses PCIe, except as the next paragraph says.
+ *
+ * Verification prepares a batch -- commitment deduplication, the column sort and the transcript SHA-256 -- on the device, reading the caller's
+ * buffers where they are.  A transcript is one serial hash chain per group, so a call of few groups with long transcripts is quicker when the
+ * four arrays are copied back and the host prepares them as it does for the host form: the call chooses by shape (bytes of transcript per group
+ * and groups per compute unit), and the answer is the same either way.  The device preparation takes up to 16384 cells
+ * per group (128 blobs x 128 cells: a whole block as one batch); a call with more per group (up to the host form's limit) always takes the
+ * host preparation. */
+int kzg355_verify_cell_kzg_proof_batch_many_device(bool *ok /* host, groups */, int *status /* host, groups or NULL */, const uint8_t *d_commitments,
+                                                   const size_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs, size_t n_per_group,
+                                                   size_t groups, const kzg355_settings *s);
+/* compute_cells_and_kzg_proofs of n resident blobs; the cells and proofs are written straight into the caller's device buffers (either may be
+ * NULL, not both).  The output slots of a blob whose status is not KZG355_OK are unspecified. */
+int kzg355_compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out /* n*128*2048 or NULL */, uint8_t *d_proofs_out /* n*128*48 or NULL */,
+                                                    int *status /* host, n or NULL */, const uint8_t *d_blobs, size_t n, const kzg355_settings *s);
+/* recover_cells_and_kzg_proofs of m resident blobs known at the same n cell indices.  The index set stays a HOST argument (at most 128 values,
+ * checked before any device work); outputs as in the call above. */
+int kzg355_recover_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out /* m*128*2048 or NULL */, uint8_t *d_proofs_out /* m*128*48 or NULL */,
+                                                    int *status /* host, m or NULL */, const size_t *cell_indices /* HOST, n, shared by all blobs */,
+                                                    const uint8_t *d_cells /* m*n*2048: blob after blob */, size_t n, size_t m, const kzg355_settings *s);
+/* Test form of the device verify call: the 176 bytes per group of kzg355_debug_cell_batch_intermediates, with the preparation pinned by
+ * prep_form: 0 by shape (what the call above does), 1 on the device, 2 copy back and prepare on the host; anything else is KZG355_BADARGS. */
+int kzg355_debug_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,
+                                                 const uint8_t *d_commitments, const size_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs,
+                                                 size_t n_per_group, size_t groups, int prep_form, const kzg355_settings *s);
+/* How many device-resident cell verify calls on this handle were prepared on the device so far (the others took the host preparation). */
+long kzg355_settings_cell_device_prep_calls(const kzg355_settings *s);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

@@ -211,6 +211,43 @@ struct Kzg {
         return out;
     }
 
+    // ---- the three cell calls on device-resident data (kzg355.h: pointer and alignment rules).  The d_* arguments are device pointers on the
+    // handle's device; one Result per unit, an Err of the call itself only for whole-call failures (whole_call_failed, below).
+    static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_device(const uint8_t *d_commitments, const size_t *d_cell_indices,
+                                                                                     const uint8_t *d_cells, const uint8_t *d_proofs, size_t n_per_group,
+                                                                                     size_t groups, const KzgSettings &s) {
+        std::unique_ptr<bool[]> ok(new bool[groups + 1]());
+        std::vector<int> st(groups + 1, 0);
+        int rc = kzg355_verify_cell_kzg_proof_batch_many_device(ok.get(), st.data(), d_commitments, d_cell_indices, d_cells, d_proofs, n_per_group, groups,
+                                                                s.raw());
+        st.resize(groups);
+        if (whole_call_failed(rc, st)) return from_status(rc, "verify_cell_kzg_proof_batch_many_device");
+        std::vector<Result<bool>> out;
+        for (size_t g = 0; g < groups; g++) {
+            if (st[g]) out.push_back(from_status(st[g], "verify_cell")); else out.push_back(bool(ok[g]));
+        }
+        return out;
+    }
+    // statuses per blob (KZG355_OK or that blob's error); cells and proofs land in the caller's device buffers (either may be null, not both)
+    static Result<std::vector<int>> compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, const uint8_t *d_blobs, size_t n,
+                                                                             const KzgSettings &s) {
+        std::vector<int> st(n + 1, 0);
+        int rc = kzg355_compute_cells_and_kzg_proofs_many_device(d_cells_out, d_proofs_out, st.data(), d_blobs, n, s.raw());
+        st.resize(n);
+        if (whole_call_failed(rc, st)) return from_status(rc, "compute_cells_and_kzg_proofs_many_device");
+        return st;
+    }
+    static Result<std::vector<int>> recover_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out,
+                                                                             const std::vector<size_t> &cell_indices, const uint8_t *d_cells, size_t m,
+                                                                             const KzgSettings &s) {
+        std::vector<int> st(m + 1, 0);
+        int rc = kzg355_recover_cells_and_kzg_proofs_many_device(d_cells_out, d_proofs_out, st.data(), cell_indices.data(), d_cells, cell_indices.size(), m,
+                                                                 s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_many_device");
+        return st;
+    }
+
     // ---- throughput extensions (no reference counterpart): many independent single-proof units per call; one Result per unit, an Err of the
     // call itself only for whole-call failures (no device, out of memory, a length mismatch)
     static bool whole_call_failed(int rc, const std::vector<int> &st) {

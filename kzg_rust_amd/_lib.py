@@ -101,6 +101,10 @@ def load():
         "kzg355_recover_cells_and_kzg_proofs_many": [u8p, u8p, ip, szp, u8p, sz, sz, vp],
         "kzg355_debug_cell_compute_h": [u8p, ip, u8p, sz, vp],
         "kzg355_debug_cell_setup_monomial_all": [u8p, vp],
+        "kzg355_verify_cell_kzg_proof_batch_many_device": [bp, ip, vp, vp, vp, vp, sz, sz, vp],
+        "kzg355_compute_cells_and_kzg_proofs_many_device": [vp, vp, ip, vp, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_many_device": [vp, vp, ip, szp, vp, sz, sz, vp],
+        "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -121,6 +125,8 @@ def load():
         getattr(lib, name).restype = None
     lib.kzg355_settings_host_hashed_calls.argtypes = [vp]
     lib.kzg355_settings_host_hashed_calls.restype = C.c_long
+    lib.kzg355_settings_cell_device_prep_calls.argtypes = [vp]
+    lib.kzg355_settings_cell_device_prep_calls.restype = C.c_long
     return lib
 
 
@@ -144,4 +150,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_debug_cell_setup_monomial", "kzg355_compute_cells_and_kzg_proofs", "kzg355_compute_cells_and_kzg_proofs_many",
     "kzg355_debug_cell_compute_h", "kzg355_debug_cell_setup_monomial_all",
     "kzg355_recover_cells_and_kzg_proofs", "kzg355_recover_cells_and_kzg_proofs_many",
+    "kzg355_verify_cell_kzg_proof_batch_many_device", "kzg355_compute_cells_and_kzg_proofs_many_device",
+    "kzg355_recover_cells_and_kzg_proofs_many_device", "kzg355_debug_cell_batch_intermediates_device", "kzg355_settings_cell_device_prep_calls",
 ]

@@ -80,18 +80,21 @@ int cc_refuse(int *status, size_t units, int code) {
 // The device chain behind the field stage.  compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_recover.hip) differ in their field
 // stage only, and both leave the same two things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role:
 // y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H.
-static int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h) {
+// With dev_out the cells and proofs go straight into the caller's device buffers: q is not needed, nor out48 when the caller takes the proofs
+// (dev_proofs; H alone leaves them in out48).
+static int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h, bool dev_out, bool dev_proofs) {
     int rc;
     if ((rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
-        (want_cells && (rc = w->q.ensure((size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * CH))) ||
+        (want_cells && !dev_out && (rc = w->q.ensure((size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * CH))) ||
         (want_proofs && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
-                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (rc = w->out48.ensure((size_t)48 * CC_FFT * CH)))) ||
+                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (!dev_proofs && (rc = w->out48.ensure((size_t)48 * CC_FFT * CH))))) ||
         (want_h && (rc = w->small.ensure((size_t)48 * CELL_FE * CH))))
         return rc;
     return KZG355_OK;
 }
-// coefficients of m blobs in w->y -> proofs in w->out48 (and H in w->small), queued on w->stream
-static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h) {
+// coefficients of m blobs in w->y -> proofs in d_proofs (w->out48, or the caller's device buffer at the chunk's offset; and H in w->small), queued
+// on w->stream
+static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h, uint8_t *d_proofs) {
     const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
     hipStream_t st = w->stream;
     tm.begin("cc_columns");
@@ -101,17 +104,19 @@ static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, b
     launch_cc_msm(w->scal_a.as<uint32_t>(), m, s->cc_table.as<G1Affine>(), w->partials.as<G1Jac>(), st);
     tm.end();
     tm.begin("cc_proofs");
-    launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, w->out48.as<uint8_t>(), want_h ? w->small.as<uint8_t>() : nullptr, st);
+    launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, d_proofs, want_h ? w->small.as<uint8_t>() : nullptr, st);
     tm.end();
 }
-// the results of a chunk of m blobs (blob c0 onwards) back to the host, the wait, and the per-blob statuses
-static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first) {
+// the results of a chunk of m blobs (blob c0 onwards) back to the host (dev_out: they are in the caller's device buffers already), the wait, and
+// the per-blob statuses
+static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first,
+                            bool dev_out) {
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     hipStream_t st = w->stream;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-    if (cells_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
-    if (proofs_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
+    if (cells_out && !dev_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
+    if (proofs_out && !dev_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
     if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     w->in_flight = false;
@@ -126,10 +131,13 @@ static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t
 
 // What the two calls share once the caller has checked its own arguments (`units` > 0 blobs, some output wanted): the remaining refusals, the
 // setups, and the chunk loop.  `reserve` sizes the caller's own workspace buffers for CH blobs; `stage` copies the input of blobs c0 .. c0 + m - 1
-// in and queues the kernels that leave their coefficients in w->y (when proofs or H are wanted) and their cells in w->q (when cells are).
-// cells_out / proofs_out / h_dbg: host memory (any may be null, not all); status (or null): per blob.
+// in (or reads it where it is, for device-resident input) and queues the kernels that leave their coefficients in w->y (when proofs or H are
+// wanted) and their cells in the d_cells it is handed (when cells are; null otherwise).
+// cells_out / proofs_out: host memory, or with dev_out device memory on the handle's device, 16-byte aligned (the kernels then write there at
+// the chunk's offset: no copy); h_dbg: host memory (any of the three may be null, not all); status (or null): per blob, host.
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
-           const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int)> &stage) {
+           const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int, uint8_t *)> &stage,
+           bool dev_out) {
     auto refuse = [&](int code) { return cc_refuse(status, units, code); };
     if (units > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
     if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
@@ -141,7 +149,8 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
     if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
     if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
     const size_t CH = units < CC_CHUNK ? units : CC_CHUNK;
-    if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg))) return refuse(rc);
+    if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg, dev_out, dev_out && proofs_out))) return refuse(rc);
+    const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     Timed tm(s, w);
     int first = KZG355_OK;
     auto run = [&]() -> int {                                     // (HIPCHK returns from here: a failed chunk refuses the whole call)
@@ -150,9 +159,11 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
         w->in_flight = true;
         HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * m, w->stream));
         int crc;
-        if ((crc = stage(w, tm, c0, m))) return crc;
-        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg);
-        if ((crc = cc_collect_chunk(w, tm, cells_out, proofs_out, h_dbg, status, c0, m, first))) return crc;
+        uint8_t *d_cells = !cells_out ? nullptr : dev_out ? cells_out + cell_bytes * c0 : w->q.as<uint8_t>();
+        uint8_t *d_proofs = dev_out && proofs_out ? proofs_out + (size_t)48 * CC_FFT * c0 : w->out48.as<uint8_t>();
+        if ((crc = stage(w, tm, c0, m, d_cells))) return crc;
+        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg, d_proofs);
+        if ((crc = cc_collect_chunk(w, tm, cells_out, proofs_out, h_dbg, status, c0, m, first, dev_out))) return crc;
     }
     return KZG355_OK;
     };
@@ -160,20 +171,24 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
     return first;
 }
 
-static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs) {
+// device: blobs, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are
+static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
+                   bool device = false) {
     if (!cs || (!cells_out && !proofs_out && !h_dbg)) return cc_refuse(status, n, KZG355_BADARGS);
     if (n == 0) return KZG355_OK;
     if (!blobs) return cc_refuse(status, n, KZG355_BADARGS);
+    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return cc_refuse(status, n, KZG355_BADARGS);
     return cc_run(cs, n, cells_out, proofs_out, h_dbg, status,
-        [](Workspace *w, size_t CH) { return w->blobs.ensure((size_t)BLOB_BYTES * CH); },
-        [&](Workspace *w, Timed &tm, size_t c0, int m) -> int {
-            HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, w->stream));
+        [&](Workspace *w, size_t CH) { return device ? KZG355_OK : w->blobs.ensure((size_t)BLOB_BYTES * CH); },
+        [&](Workspace *w, Timed &tm, size_t c0, int m, uint8_t *d_cells) -> int {
+            const uint8_t *d_blobs = device ? blobs + (size_t)BLOB_BYTES * c0 : w->blobs.as<uint8_t>();
+            if (!device) HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, w->stream));
             tm.begin("cc_field");
-            launch_cc_field(w->blobs.as<uint8_t>(), m, cs->cc_consts.as<CellComputeConsts>(), proofs_out || h_dbg ? w->y.as<Fr>() : nullptr,
-                            cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), w->stream);
+            launch_cc_field(d_blobs, m, cs->cc_consts.as<CellComputeConsts>(), proofs_out || h_dbg ? w->y.as<Fr>() : nullptr, d_cells, w->err.as<int>(),
+                            w->stream);
             tm.end();
             return KZG355_OK;
-        });
+        }, device);
 }
 
 }  // namespace kzg355_impl
@@ -184,6 +199,11 @@ extern "C" {
 int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out, uint8_t *proofs_out, int *status, const uint8_t *blobs, size_t n,
                                              const kzg355_settings *s) {
     return cc_impl(cells_out, proofs_out, nullptr, status, blobs, n, s);
+}
+
+int kzg355_compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const uint8_t *d_blobs, size_t n,
+                                                    const kzg355_settings *s) {
+    return cc_impl(d_cells_out, d_proofs_out, nullptr, status, d_blobs, n, s, true);
 }
 
 int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blob, const kzg355_settings *s) {

@@ -13,6 +13,7 @@
 // group element, so the same boolean.
 #define KZG_FP_MUL_NOINLINE 1
 #include "kernels.h"
+#include "sha256_rounds.h"
 #include "fr_block.h"
 
 namespace kzg {
@@ -27,10 +28,7 @@ namespace kzg {
 // runs the 64 rounds of block b from LDS (ds_read_b128, [t/4][lane][4] layout: conflict-free).  One barrier per block.
 // Rounds use v_alignbit (rotates), v_bitop3 (3-input xor / ch / maj) and v_add3.  Also assembles the record's
 // C / z / proof fields.
-__device__ __forceinline__ uint32_t ror(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
-__device__ __forceinline__ uint32_t ch3(uint32_t e, uint32_t f, uint32_t g) { return __builtin_amdgcn_bitop3_b32(e, f, g, 0xca); }   // e ? f : g
-__device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xe8); }
+// (ror, xor3, ch3, maj3: sha256_rounds.h)
 
 constexpr int CH_BLOCKS = 2050;
 // The hashed message puts the blob at offset 32, so compression b covers blob[64b-32, 64b+32): every block straddles two
@@ -416,15 +414,7 @@ __global__ void __launch_bounds__(64 * EVAL_WAVES, 2) k_eval(const uint8_t *blob
 // The hash is one serial chain per batch, but the message schedule of a block does not depend on the chaining state: the 64
 // lanes expand 64 blocks at once (W[t] + K[t] to LDS), then lane 0 runs the rounds of those blocks (~930 instructions each,
 // the irreducible chain).  The powers are spread over the lanes: lane l starts at r^l and steps by r^64.
-__constant__ uint32_t SHA_K[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+// (SHA_K: sha256_rounds.h)
 // Many batches: the same transcript hash with one LANE per batch (schedule and rounds in the lane's registers), 64 batches per
 // wave.  The one-wave-per-batch form above keeps 63 lanes idle during the rounds: fine while every wave has a SIMD to itself,
 // 64x the issue slots once the batches outnumber the SIMDs.  Writes the digest words (as fr_from_words takes them) to
@@ -484,8 +474,7 @@ __global__ void __launch_bounds__(64) k_rhash_lanes(const uint8_t *records, int 
 
 // Four batches (waves) per workgroup, one per SIMD of the CU it lands on (one-wave workgroups of long chains are placed
 // unevenly); the waves share nothing: each keeps to its own LDS slice behind wave-local fences.
-#define RP_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); \
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
+// (SHA_WAVE_SYNC: sha256_rounds.h)
 __global__ void __launch_bounds__(256) k_rpowers(const uint8_t *records, int n, int groups, int check_zy, uint32_t *scal_a, uint32_t *scal_b,
                                                   uint32_t *scal_c, int *err, int n_fe, int have_digest) {
     __shared__ uint32_t wk_all[4][64][64];           // per wave: [t][block of the chunk]
@@ -538,7 +527,7 @@ __global__ void __launch_bounds__(256) k_rpowers(const uint8_t *records, int n, 
                     wk[t][lane] = w[t & 15] + SHA_K[t];
                 }
             }
-            RP_WAVE_SYNC();
+            SHA_WAVE_SYNC();
             if (lane == 0) {
                 const uint32_t cnt = nblocks - b0 < 64u ? nblocks - b0 : 64u;
 #pragma unroll 1
@@ -553,10 +542,10 @@ __global__ void __launch_bounds__(256) k_rpowers(const uint8_t *records, int n, 
                     h0 += a; h1 += bb; h2 += c; h3 += d; h4 += e; h5 += f; h6 += gg; h7 += h;
                 }
             }
-            RP_WAVE_SYNC();
+            SHA_WAVE_SYNC();
         }
         if (lane == 0) { digest[0] = h7; digest[1] = h6; digest[2] = h5; digest[3] = h4; digest[4] = h3; digest[5] = h2; digest[6] = h1; digest[7] = h0; }
-        RP_WAVE_SYNC();
+        SHA_WAVE_SYNC();
         uint32_t dw[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) dw[k] = digest[k];

@@ -47,6 +47,7 @@ constexpr int ERR_BAD_POINT = 1;           // validate_kzg_g1 failed (utils.rs:2
 constexpr int ERR_NONCANONICAL_FR = 2;     // bytes_to_bls_field failed (utils.rs:262-275)
 constexpr int ERR_SETUP_POINT = 4;         // load_trusted_setup: bad g1/g2 bytes (kzg.rs:863, 878)
 constexpr int ERR_SETUP_MONOMIAL = 8;      // is_trusted_setup_in_lagrange_form (kzg.rs:823-826)
+constexpr int ERR_CELL_INDEX = 16;         // a cell index >= CELLS_PER_EXT_BLOB, found by the device preparation (k_cell_prep.hip)
 
 struct alignas(128) WideRow { Fp x, y; uint32_t pad[4]; };       // one affine point per 128-byte line
 
@@ -200,6 +201,21 @@ void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d
 // per group
 void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
                          const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st);
+// ---- k_cell_prep.hip: what the host prepares per group of a cell batch, from inputs that are in HBM already (the *_device entry points)
+constexpr int CELL_PREP_LDS_SLOTS = 8192;      // slots of the dedup table k_cell_prep keeps in LDS; a larger table lives in d_gtab
+constexpr int CELL_PREP_MAX_CELLS = 16384;     // cells per group up to which the device prepares (128 blobs x 128 cells: a block as one batch)
+// slots of a group's dedup table: a power of two >= 2 npg
+inline int cell_prep_table_slots(int npg) { int t = 2; while (t < 2 * npg) t <<= 1; return t; }
+// d_commitments / d_indices: the caller's (16- / 8-byte aligned).  Out: d_uc (unique commitments per group in first-appearance order, padded to npg
+// with the encoding of infinity), d_ucount[g], d_cell (clamped indices; an index >= 128 sets ERR_CELL_INDEX in d_err[g]), d_cidx, d_perm, and
+// the segment list with a fixed min(npg, 128) slots per group (d_gseg[g] = g * that; empty segments have count 0).  d_gtab: groups * tab_size
+// ints when tab_size > CELL_PREP_LDS_SLOTS, unused otherwise.
+void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int npg, int groups, int tab_size, int *d_gtab, uint8_t *d_uc, int4 *d_segs,
+                      int *d_gseg, int *d_cell, int *d_cidx, int *d_perm, int *d_ucount, int *d_err, hipStream_t st);
+// the transcript digests (32 bytes per group, as launch_cell_scalars takes them), gathered from the caller's buffers; lanes: one lane per group
+// (many groups), else one wave per group
+void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx, const int *d_ucount,
+                       int npg, int groups, bool lanes, uint8_t *d_digests, hipStream_t st);
 
 
 // ---- k_cell_compute.hip: compute_cells_and_kzg_proofs (the cells of the 2x extension and their proofs by FK20; mainnet handles only)

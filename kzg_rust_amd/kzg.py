@@ -261,6 +261,11 @@ class KzgSettings:
         return lib().kzg355_settings_host_hashed_calls(self.handle)
 
     @property
+    def cell_device_prep_calls(self):
+        """Device-resident cell verify calls on this handle that were prepared on the device so far."""
+        return lib().kzg355_settings_cell_device_prep_calls(self.handle)
+
+    @property
     def host_threads(self):
         """host threads that hash for one call on this handle (its workers + the calling thread)"""
         return lib().kzg355_settings_host_threads(self.handle)
@@ -633,3 +638,100 @@ class Kzg:
         out = C.create_string_buffer(4096 * 48)
         _check(lib().kzg355_debug_cell_setup_monomial_all(out, s.handle), "debug_cell_setup_monomial_all")
         return [out.raw[48 * i:48 * i + 48] for i in range(4096)]
+
+    # ---- the three cell calls on device-resident data.  A device argument is an object with data_ptr() (a torch uint8 / int64 tensor on the
+    # handle's device) or a plain integer address; sizes and dtypes are checked where the object offers them, before any FFI call ----
+    @staticmethod
+    def _dev(x, what, numel, dtype="uint8", optional=False):
+        if x is None:
+            if optional:
+                return None
+            raise BadArgs(f"{what}: missing")
+        if isinstance(x, int):
+            return x
+        if not hasattr(x, "data_ptr"):
+            raise BadArgs(f"{what}: neither an address nor an object with data_ptr()")
+        if hasattr(x, "dtype") and str(x.dtype).rsplit(".", 1)[-1] != dtype:
+            raise BadArgs(f"{what}: dtype {x.dtype}, expected {dtype}")
+        if hasattr(x, "numel") and x.numel() != numel:
+            raise BadArgs(f"{what}: {x.numel()} elements, expected {numel}")
+        if hasattr(x, "is_contiguous") and not x.is_contiguous():
+            raise BadArgs(f"{what}: not contiguous")
+        return x.data_ptr()
+
+    @staticmethod
+    def _cell_many_device(commitments, cell_indices, cells, proofs, n_per_group, groups, s, prep_form, debug):
+        npg, G = int(n_per_group), int(groups)
+        if npg < 0 or G < 0 or prep_form not in (0, 1, 2):
+            raise BadArgs("n_per_group, groups or prep_form out of range")
+        N = npg * G
+        ptrs = (Kzg._dev(commitments, "commitments", 48 * N, optional=N == 0), Kzg._dev(cell_indices, "cell_indices", N, "int64", optional=N == 0),
+                Kzg._dev(cells, "cells", BYTES_PER_CELL * N, optional=N == 0), Kzg._dev(proofs, "proofs", 48 * N, optional=N == 0))
+        if G == 0:
+            return [], b""
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        if debug:
+            out = C.create_string_buffer(176 * G)
+            rc = lib().kzg355_debug_cell_batch_intermediates_device(out, ok, st, *ptrs, npg, G, prep_form, s.handle)
+        else:
+            if prep_form != 0:
+                raise BadArgs("prep_form is pinned through debug_cell_batch_intermediates_device only")
+            rc = lib().kzg355_verify_cell_kzg_proof_batch_many_device(ok, st, *ptrs, npg, G, s.handle)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_cell_kzg_proof_batch_many_device")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_cell") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_cell_kzg_proof_batch_many_device(commitments, cell_indices, cells, proofs, n_per_group, groups, s):
+        """verify_cell_kzg_proof_batch_many on device memory: commitments (groups * n_per_group * 48 bytes, uint8), cell_indices (int64), cells
+        (* 2048) and proofs (* 48), group-major.  Returns a list of bool / Error, one per group, as the host form does."""
+        return Kzg._cell_many_device(commitments, cell_indices, cells, proofs, n_per_group, groups, s, 0, False)[0]
+
+    @staticmethod
+    def debug_cell_batch_intermediates_device(commitments, cell_indices, cells, proofs, n_per_group, groups, s, prep_form=0):
+        """(verdicts, [176 bytes per group]) as debug_cell_batch_intermediates; prep_form 0 by shape, 1 device preparation, 2 host preparation."""
+        res, raw = Kzg._cell_many_device(commitments, cell_indices, cells, proofs, n_per_group, groups, s, prep_form, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
+    def _cell_outputs(cells_out, proofs_out, units):
+        if cells_out is None and proofs_out is None:
+            raise BadArgs("cells_out and proofs_out are both missing")
+        return (Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * CELLS_PER_EXT_BLOB * units, optional=True),
+                Kzg._dev(proofs_out, "proofs_out", 48 * CELLS_PER_EXT_BLOB * units, optional=True))
+
+    @staticmethod
+    def compute_cells_and_kzg_proofs_many_device(blobs, n, s, cells_out=None, proofs_out=None):
+        """compute_cells_and_kzg_proofs of n resident blobs (n * 131072 bytes) into the caller's device tensors cells_out (n * 128 * 2048 bytes)
+        and proofs_out (n * 128 * 48); either may be None, not both.  Returns one entry per blob: None, or the Error of that blob (its output
+        slots are then unspecified)."""
+        n = int(n)
+        if n < 0:
+            raise BadArgs("n out of range")
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, n)
+        d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_compute_cells_and_kzg_proofs_many_device(c_out, p_out, st, d_blobs, n, s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "compute_cells_and_kzg_proofs_many_device")
+        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("compute_cells") for i in range(n)]
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_many_device(cell_indices, cells, m, s, cells_out=None, proofs_out=None):
+        """recover_cells_and_kzg_proofs of m resident blobs known at the same cell_indices (a host sequence of 64..128 strictly ascending
+        indices): cells holds m * len(cell_indices) * 2048 bytes, blob after blob.  Outputs and return value as
+        compute_cells_and_kzg_proofs_many_device."""
+        ix = [int(i) for i in cell_indices]
+        n, m = len(ix), int(m)
+        if m < 0 or any(i < 0 or i >= 1 << 64 for i in ix):
+            raise BadArgs("m or a cell index out of range")
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, m)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * n * m, optional=m == 0)
+        st = (C.c_int * max(m, 1))()
+        idx = (C.c_size_t * max(n, 1))(*ix)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_many_device(c_out, p_out, st, idx, d_cells, n, m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs_many_device")
+        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]

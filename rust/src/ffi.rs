@@ -97,6 +97,18 @@ extern "C" {
                                                s: *const kzg355_settings) -> c_int;
     pub fn kzg355_recover_cells_and_kzg_proofs_many(cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int, cell_indices: *const usize, cells: *const u8,
                                                     n: usize, m: usize, s: *const kzg355_settings) -> c_int;
+    // the three cell calls on device-resident data: d_* are device pointers (byte buffers 16-byte aligned, indices 8-byte aligned); the index set
+    // of the recovery stays in host memory; prep_form: 0 by shape, 1 device preparation, 2 host preparation
+    pub fn kzg355_verify_cell_kzg_proof_batch_many_device(ok: *mut bool, status: *mut c_int, d_commitments: *const u8, d_cell_indices: *const usize,
+                                                          d_cells: *const u8, d_proofs: *const u8, n_per_group: usize, groups: usize,
+                                                          s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_compute_cells_and_kzg_proofs_many_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int, d_blobs: *const u8, n: usize,
+                                                           s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_cells_and_kzg_proofs_many_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int, cell_indices: *const usize,
+                                                           d_cells: *const u8, n: usize, m: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_debug_cell_batch_intermediates_device(out: *mut u8, ok: *mut bool, status: *mut c_int, d_commitments: *const u8,
+                                                        d_cell_indices: *const usize, d_cells: *const u8, d_proofs: *const u8, n_per_group: usize,
+                                                        groups: usize, prep_form: c_int, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_kzg_proof_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize,
                                         s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_blob_kzg_proof_many(ok: *mut bool, status: *mut c_int, blobs: *const u8, commitments: *const u8, proofs: *const u8, n: usize,
@@ -113,6 +125,7 @@ extern "C" {
     pub fn kzg355_settings_exchange_stats(s: *const kzg355_settings, allgathers: *mut c_long, peer_exchanges: *mut c_long) -> c_int;
     pub fn kzg355_settings_set_host_hash(s: *mut kzg355_settings, mode: c_int, max_blobs: c_int) -> c_int;
     pub fn kzg355_settings_host_hashed_calls(s: *const kzg355_settings) -> c_long;
+    pub fn kzg355_settings_cell_device_prep_calls(s: *const kzg355_settings) -> c_long;
     pub fn kzg355_settings_host_threads(s: *const kzg355_settings) -> c_int;
     pub fn kzg355_version() -> *const c_char;
 }

@@ -517,6 +517,65 @@ impl Kzg {
             .collect())
     }
 
+    /// `verify_cell_kzg_proof_batch_many` on device-resident data: the four pointers are DEVICE pointers on the handle's device (byte buffers
+    /// 16-byte aligned, the indices 8-byte aligned), group-major, `n_per_group` cells per group; only the verdicts cross PCIe.
+    ///
+    /// # Safety
+    /// The pointers must be valid device allocations of `groups * n_per_group` entries each, untouched until the call returns.
+    pub unsafe fn verify_cell_kzg_proof_batch_many_device(
+        d_commitments: *const u8,
+        d_cell_indices: *const usize,
+        d_cells: *const u8,
+        d_proofs: *const u8,
+        n_per_group: usize,
+        groups: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = ffi::kzg355_verify_cell_kzg_proof_batch_many_device(ok.as_mut_ptr(), st.as_mut_ptr(), d_commitments, d_cell_indices, d_cells, d_proofs,
+                                                                     n_per_group, groups, s.raw);
+        whole_call(rc, &st[..groups], "verify_cell_kzg_proof_batch_many_device")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
+    }
+
+    /// `compute_cells_and_kzg_proofs` of `n` resident blobs into the caller's device buffers (either may be null, not both); one `Result` per
+    /// blob, the output slots of a failed blob unspecified.
+    ///
+    /// # Safety
+    /// Device pointers on the handle's device, 16-byte aligned, of `n` blobs / `n * 128` cells / `n * 128` proofs; outputs must not overlap the input.
+    pub unsafe fn compute_cells_and_kzg_proofs_many_device(
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        d_blobs: *const u8,
+        n: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let mut st = vec![0i32; n.max(1)];
+        let rc = ffi::kzg355_compute_cells_and_kzg_proofs_many_device(d_cells_out, d_proofs_out, st.as_mut_ptr(), d_blobs, n, s.raw);
+        whole_call(rc, &st[..n], "compute_cells_and_kzg_proofs_many_device")?;
+        Ok((0..n).map(|i| check(st[i], "compute_cells")).collect())
+    }
+
+    /// `recover_cells_and_kzg_proofs` of `m` resident blobs known at the same `cell_indices` (host memory); outputs as above.
+    ///
+    /// # Safety
+    /// `d_cells` holds `m * cell_indices.len()` cells on the handle's device; the outputs `m * 128` cells / proofs; all 16-byte aligned.
+    pub unsafe fn recover_cells_and_kzg_proofs_many_device(
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        cell_indices: &[usize],
+        d_cells: *const u8,
+        m: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let mut st = vec![0i32; m.max(1)];
+        let rc = ffi::kzg355_recover_cells_and_kzg_proofs_many_device(d_cells_out, d_proofs_out, st.as_mut_ptr(), cell_indices.as_ptr(), d_cells,
+                                                                      cell_indices.len(), m, s.raw);
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_many_device")?;
+        Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
+    }
+
     /// `commitments.len()` independent `verify_kzg_proof` checks (one proof per call is what benches/kzg_benches.rs:70-81 times).
     pub fn verify_kzg_proof_many(
         commitments: &[KzgCommitment],
