@@ -232,6 +232,49 @@ template <int N> KZG_HD void mont_mul2_lazy(uint32_t *r, const uint32_t *a, cons
         cy >>= LB;
     }
 }
+// r = (a*b + 2 c^2) / R, lazily: a product and a (doubled) square share one Montgomery reduction -- N^2 + N(N+1)/2 + N^2 limb products
+// (Fp: 196 + 105 + 196 = 497) against 2N^2 + N(N+1)/2 + N^2 (693) for fp_mul_lz and fp_sqr_lz apart.  The doubled square is taken with
+// half-products as in mont_sqr: 2 c^2 = sum_i (2 c_i) c_i + sum_{i<j} (4 c_i) c_j, into the 2N column accumulators that also take a_j b_i;
+// then the same word-by-word reduction.  (The doubling chain needs 8 B^2: it passes c = 2B, normalised, so that the factor sits in the
+// VALUE spread over the limbs and not in every limb product.)
+// Operands: normalised lazy values (every limb below the top one < 2^29, the top one smaller still) with a*b + 2 c^2 < 2^12 m^2; result
+// < m (1 + 2^-13), limbs normalised.  Column k of the 2N holds at most
+//     N full products a_j b_i < 2^58,  N/2 cross products (4 c_i) c_j < 2^60 (the pairs i < j with i + j = k),  one diagonal (2 c_i) c_i < 2^59,
+//     N reduction terms q_i m_j < 2^58,  and the carry of the column below < 2^35:
+// (2N + 4 (N/2) + 2) 2^58 + 2^35 = 58 * 2^58 + 2^35 < 2^64 for N = 14 -- asserted below; not true of 15 limbs.
+template <int N> KZG_HD void mont_mulsqr2_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *m, const uint32_t inv) {
+    static_assert(2 * N + 4 * (N / 2) + 2 < 64,
+                  "column accumulators: N full, N/2 quadrupled cross, one doubled diagonal and N reduction products must stay below 2^64");
+    uint64_t acc[2 * N];
+    uint32_t c2[N], c4[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) { c2[j] = c[j] << 1; c4[j] = c[j] << 2; }
+#pragma unroll
+    for (int k = 0; k < 2 * N; k++) acc[k] = 0;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const uint32_t bi = b[i];
+#pragma unroll
+        for (int j = 0; j < N; j++) acc[i + j] += (uint64_t)a[j] * bi;
+        acc[2 * i] += (uint64_t)c2[i] * c[i];
+#pragma unroll
+        for (int j = i + 1; j < N; j++) acc[i + j] += (uint64_t)c4[i] * c[j];
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const uint32_t q = ((uint32_t)acc[i] * inv) & LMASK;
+#pragma unroll
+        for (int j = 0; j < N; j++) acc[i + j] += (uint64_t)q * m[j];
+        acc[i + 1] += acc[i] >> LB;
+    }
+    uint64_t cy = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        cy += acc[N + j];
+        r[j] = j < N - 1 ? ((uint32_t)cy & LMASK) : (uint32_t)cy;
+        cy >>= LB;
+    }
+}
 // 32-bit word array (little-endian words, NW of them) -> N 29-bit limbs
 template <int N, int NW> KZG_HD void words_to_limbs(uint32_t *l, const uint32_t *w) {
 #pragma unroll
@@ -314,7 +357,11 @@ KZG_HD void fp_sqr_lz(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP, true>(r.
 // with a b + c d < 2^12 p^2 (e.g. a < 6p, b < 10p, c < 4p, d < 2p in the point additions); result < p (1 + 2^-13).
 KZG_HD void fp_mul2_lz(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d) { KZG_FP_CONSTS mont_mul2_lazy<NFP>(r.l, a.l, b.l, c.l, d.l, FP_MOD,
         FP_INVW); }
-// r = a + (kp - b), kp a multiple of p above b: limbs normalised (signed carries), the top limb keeps the excess
+// r = (a b + 2 c^2) / R, lazily, ONE Montgomery reduction for a product and a doubled square (497 limb products instead of 693).  Operands normalised
+// lazy values with a b + 2 c^2 < 2^12 p^2 (the doubling: a = E < 4p, b < 16p, c = 2B < 4p); result < p (1 + 2^-13).
+KZG_HD void fp_mulsqr2_lz(Fp &r, const Fp &a, const Fp &b, const Fp &c) { KZG_FP_CONSTS mont_mulsqr2_lazy<NFP>(r.l, a.l, b.l, c.l, FP_MOD, FP_INVW); }
+// r = a + kp - b, kp a multiple of p with a + kp - b >= 0 (kp >= b is enough; g1_dbl_lazy passes a smaller kp where a's own bias covers the
+// rest): limbs normalised (signed carries), the top limb keeps the excess
 KZG_HD void fp_sub_lz(Fp &r, const Fp &a, const Fp &b, const uint32_t *kp) {
     int32_t c = 0;
 #pragma unroll

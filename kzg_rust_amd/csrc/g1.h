@@ -199,7 +199,7 @@ KZG_G1_MID void g1x_to_jac(G1Jac &r, const G1X &a) {
 // XYZZ + XYZZ on lazy coordinates (add-2008-s, 12M + 2S), both operands within the accumulator invariant above (X < 8p, Y < 4p,
 // ZZ, ZZZ < 2p) and the result within it again:
 //   U1 = X1 ZZ2, U2 = X2 ZZ1, S1 = Y1 ZZZ2, S2 = Y2 ZZZ1 < 2p;  P = U2 + 2p - U1, R = S2 + 2p - S1 in (0, 4p);  PP, PPP, Q < 2p
-//   X3 = R^2 + (2p - PPP) + 2 (2p - Q) in (0, 8p);  Y3 = R (Q + 8p - X3) + (2p - S1 PPP) in (0, 4p);  ZZ3, ZZZ3 < 2p
+//   X3 = R^2 + (2p - PPP) + 2 (2p - Q) in (0, 8p);  Y3 = R (Q + 8p - X3) + (2p - S1) PPP, one reduction for both products, < 2p;  ZZ3, ZZZ3 < 2p
 // An operand at infinity (ZZ = 0 mod p) or P possibly = 0 mod p (exact low-limb filters) goes through the canonical Jacobian addition.
 KZG_G1_MID void g1x_add_lazy2(G1X &r, const G1X &a, const G1X &b) {
     const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
@@ -224,9 +224,8 @@ KZG_G1_MID void g1x_add_lazy2(G1X &r, const G1X &a, const G1X &b) {
     fp_sub_lz(u, t, Q, m2);                                       // in (0, 6p)
     fp_sub_lz(X3, u, Q, m2);                                      // in (0, 8p)
     fp_sub_lz(t, Q, X3, m8);                                      // in (0, 10p)
-    fp_mul_lz(Y3, R, t);
-    fp_mul_lz(t, S1, PPP);
-    fp_sub_lz(Y3, Y3, t, m2);                                     // in (0, 4p)
+    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }          // 2p - S1: in (0, 2p]
+    fp_mul2_lz(Y3, R, t, u, PPP);                                 // R (Q - X3) - S1 PPP under one reduction: < 2p  (k_lc_wsum is issue-bound)
     fp_mul_lz(r.zz, ZZ12, PP);
     fp_mul_lz(r.zzz, ZZZ12, PPP);
     r.x = X3; r.y = Y3;
@@ -280,29 +279,32 @@ KZG_HD void g1_mul_words(G1Jac &r, const G1Affine &p, const uint32_t *k, int nwo
 // ---- lazy (unreduced) Jacobian doubling / addition for the dependent chains (subgroup test, Horner, window ladders): no
 // reduction below p after any product, sum or difference; every routine states the bounds it needs and restores
 // (in units of p, limbs normalised).  Multiples of p are added before differences; products tolerate operands up to 64p.
-//   g1_dbl_lazy : in  X, Y, Z < 32p                      out X < 26p, Y < 18p, Z < 4p     (infinity stays Z = 0 mod p)
-//   g1_add_lazy : in  acc X, Y, Z < 32p, b canonical     out X < 8p,  Y < 4p,  Z < 2p
+//   g1_dbl_lazy : in  X, Y, Z < 32p                      out X < 12p, Y <= 2p, Z < 3p     (infinity stays Z = 0 mod p)
+//   g1_add_lazy : in  acc X, Y, Z < 32p, b canonical     out X < 8p,  Y < 2p,  Z < 2p
 //                 acc possibly at infinity / b = +-acc are caught by exact low-limb filters and redone canonically.
 KZG_G1_MID void g1_dbl_lazy(G1Jac &r, const G1Jac &p) {
-    const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT, m16[NFP] = FP_MOD16_INIT, m32[NFP] = FP_MOD32_INIT;
-    Fp A, B, C, D, E, F, t, u;
-    fp_sqr_lz(A, p.x);
-    fp_sqr_lz(B, p.y);
-    fp_sqr_lz(C, B);
-    fp_add_lz(t, p.x, B); fp_sqr_lz(t, t);                       // (X + B)^2                      < 2p
-    fp_sub_lz(u, t, A, m2); fp_sub_lz(t, u, C, m2);              //  ... - A - C + 4p              in (0, 6p)
-    fp_add_lz(D, t, t);                                          // D                              < 12p
-    fp_add_lz(E, A, A); fp_add_lz(E, E, A);                      // E = 3A                         < 6p
-    fp_sqr_lz(F, E);
+    // dbl-2009-l with C = B^2 never formed on its own: D = 2 ((X + B)^2 - A - C) is 4 X B, one product in place of a square, and C is then
+    // only needed in Y3 = E (D - X3) - 8C, a product and a square under ONE reduction (fp_mulsqr2_lz).  3S + 2M + the fused pair: 2184 limb
+    // products and 6 reductions, against 2289 and 7 for 5S + 2M.  Signs: W = E (X3 - D + 4p) + 8 B^2 is formed in unsigned columns, Y3 = 2p - W.
+    // (every lazy product or square below: operands < 32p, so the result is < p (1 + 2^-15), written "< 1.01p")
+    const uint32_t m2[NFP] = FP_MOD2_INIT, m4[NFP] = FP_MOD4_INIT, m8[NFP] = FP_MOD8_INIT;
+    Fp A, B, D, E, F, t, u, c;
+    fp_sqr_lz(A, p.x);                                           // A = X^2                        < 1.01p
+    fp_sqr_lz(B, p.y);                                           // B = Y^2                        < 1.01p
+    fp_mul_lz(t, p.x, B);                                        // X B                            < 1.01p
+    fp_add_lz(D, t, t); fp_add_lz(D, D, D);                      // D = 4 X B                      < 4.04p
+    fp_add_lz(E, A, A); fp_add_lz(E, E, A);                      // E = 3A                         < 3.03p
+    fp_sqr_lz(F, E);                                             // F                              < 1.01p
     fp_mul_lz(u, p.y, p.z);                                      // before x, y are overwritten (r may alias p)
-    Fp X3, Y3;
-    fp_sub_lz(t, F, D, m16); fp_sub_lz(X3, t, D, m8);            // F - 2D + 24p                   in (0, 26p)
-    fp_sub_lz(t, D, X3, m32);                                    // D - X3 + 32p                   in (6p, 44p)
-    fp_mul_lz(Y3, E, t);
-    fp_add_lz(C, C, C); fp_add_lz(C, C, C); fp_add_lz(C, C, C);  // 8C                             < 16p
-    fp_sub_lz(r.y, Y3, C, m16);                                  //                                in (0, 18p)
+    Fp X3, W;
+    fp_sub_lz(t, F, D, m8); fp_sub_lz(X3, t, D, m2);             // F - D + 8p in (3.96p, 9.01p);  X3 = F - 2D + 10p in (1.92p, 11.01p)
+                                                                 // (2p < D: t carries 8p of bias, t - D > -0.08p, so t + 2p - D stays positive)
+    fp_sub_lz(t, X3, D, m4);                                     // X3 - D + 4p                    in (1.88p, 15.01p)
+    fp_add_lz(c, B, B);                                          // 2B                             < 2.02p
+    fp_mulsqr2_lz(W, E, t, c);                                   // E (X3 - D) + 8 B^2: E t + 2 c^2 < (45.5 + 8.2) p^2, W < 1.01p
+    { const Fp z = fp_zero(); fp_sub_lz(r.y, z, W, m2); }        // Y3 = 2p - W                    in (0.99p, 2p]
     r.x = X3;
-    fp_add_lz(r.z, u, u);                                        //                                < 4p
+    fp_add_lz(r.z, u, u);                                        // Z3 = 2 Y Z                     < 2.02p
 }
 KZG_G1_MID void g1_add_lazy(G1Jac &r, const G1Jac &a, const G1Jac &b) {
     const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
@@ -324,8 +326,8 @@ KZG_G1_MID void g1_add_lazy(G1Jac &r, const G1Jac &a, const G1Jac &b) {
     fp_sqr_lz(X3, R);
     fp_sub_lz(t, X3, HHH, m2); fp_sub_lz(u, t, V, m2); fp_sub_lz(X3, u, V, m2);        // in (0, 8p)
     fp_sub_lz(t, V, X3, m8);                                                            // in (0, 10p)
-    fp_mul_lz(Y3, R, t);
-    fp_mul_lz(t, S1, HHH); fp_sub_lz(Y3, Y3, t, m2);                                    // in (0, 4p)
+    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }                                // 2p - S1: in (0, 2p]
+    fp_mul2_lz(Y3, R, t, u, HHH);                                                       // R (V - X3) - S1 HHH under one reduction: < 2p
     fp_mul_lz(Z3, a.z, b.z); fp_mul_lz(Z3, Z3, H);
     r.x = X3; r.y = Y3; r.z = Z3;
 }
@@ -351,8 +353,8 @@ KZG_G1_MID void g1_add_lazy2(G1Jac &r, const G1Jac &a, const G1Jac &b) {
     fp_sqr_lz(X3, R);
     fp_sub_lz(t, X3, HHH, m2); fp_sub_lz(u, t, V, m2); fp_sub_lz(X3, u, V, m2);        // in (0, 8p)
     fp_sub_lz(t, V, X3, m8);                                                            // in (0, 10p)
-    fp_mul_lz(Y3, R, t);
-    fp_mul_lz(t, S1, HHH); fp_sub_lz(Y3, Y3, t, m2);                                    // in (0, 4p)
+    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }                                // 2p - S1: in (0, 2p]
+    fp_mul2_lz(Y3, R, t, u, HHH);                                                       // R (V - X3) - S1 HHH under one reduction: < 2p
     fp_mul_lz(Z3, a.z, b.z); fp_mul_lz(Z3, Z3, H);
     r.x = X3; r.y = Y3; r.z = Z3;
 }

@@ -13,7 +13,9 @@ namespace kzg {
 //     stage 3:  E (D - X3)                                             (every lane for itself;  Y3 = E (D - X3) - 8C)
 // so the quad runs ONE squaring body per stage, each lane on its own operand (picked by v_cndmask), and the results are broadcast with
 // quad_perm DPP moves: 2 squarings + 1 product deep instead of 5 + 2.  All four lanes carry the same (X, Y, Z) and do the cheap linear
-// steps redundantly.  Lazy bounds as in g1_dbl_lazy (g1.h): in X, Y, Z < 32p, out X < 26p, Y < 18p, Z < 6p.
+// steps redundantly.  Lazy bounds: in X, Y, Z < 32p, out X < 26p, Y < 18p, Z < 6p.  (g1_dbl_lazy in g1.h no longer forms C = B^2 -- it takes D = 4 X B
+// and 8 B^2 inside Y3's reduction; here C is one of stage 2's three parallel squarings and costs the quad no depth, so this form stays.  Likewise the
+// last stage of g1_add_quad below runs R (V - X3) and S1 HHH side by side on two lanes: fusing them under one reduction would make the stage deeper.)
 template <int K> __device__ __forceinline__ Fp fp_quad_bcast(const Fp &v) {
     Fp r;
 #pragma unroll

@@ -1,0 +1,170 @@
+"""-m gpu: the kernels that run the lazy G1 chain arithmetic of g1.h (g1_dbl_lazy without C = B^2, the additions with Y3 under one reduction),
+at the smallest shapes that reach them, against the CPU oracle:
+
+  * k_validate_points (decompression + the two [|x|] ladders of 63 lazy doublings): one 64-blob batch of tests/golden/batch64.json and copies of it
+    with ONE commitment or proof replaced by an encoding outside the subgroup, off the curve, or the point at infinity.  Verdicts and per-batch
+    statuses as the oracle gives them, through the bench's entry point on a handle pinned to the bucket form (by size these few batches would take
+    the pre-shifted form, which validates with other kernels) and through stage 1 alone; the decoded points are compared through what they feed --
+    proof_lincomb and rhs, byte for byte (the ABI has no readback of the points themselves).
+  * the tail of the bucket form: 64 batches of 8 blobs with the handle's chain threshold at 1 (k_lc_wsum: g1x_add_lazy2; k_lc_hchain_quad) and lifted
+    out of reach (k_lc_horner: g1_dbl_lazy + g1_add_lazy): r, proof_lincomb and rhs byte for byte, one disturbed batch found at its position."""
+import ctypes as C
+import json
+import os
+
+import pytest
+
+from synth import random_blob
+
+pytestmark = pytest.mark.gpu
+
+INF = bytes([0xC0]) + bytes(47)
+
+
+@pytest.fixture(scope="module")
+def kz():
+    import kzg_rust_amd
+    return kzg_rust_amd
+
+
+@pytest.fixture(scope="module")
+def fx64():
+    fx = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "batch64.json")))
+    blobs = [random_blob(fx["first_index"] + i) for i in range(fx["n"])]
+    return blobs, [bytes.fromhex(c) for c in fx["commitments"]], [bytes.fromhex(p) for p in fx["proofs"]]
+
+
+def _handle(kz, setup_bytes, **opts):
+    g1, g2 = setup_bytes
+    return kz.KzgSettings.load_trusted_setup_ex([g1[48 * i:48 * i + 48] for i in range(4096)], [g2[96 * i:96 * i + 96] for i in range(65)], **opts)
+
+
+def _dev(torch, s, data):
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(torch.device("cuda", s.device))
+
+
+def _special_points(oracle):
+    off = sub = None
+    for x in range(1, 1000):
+        b = bytearray(x.to_bytes(48, "big")); b[0] |= 0x80
+        b = bytes(b)
+        if off is None and oracle.g1_uncompress_only(b) != 0:
+            off = b
+        if sub is None and oracle.g1_uncompress_only(b) == 0 and oracle.g1_validate(b) != 0:
+            sub = b
+        if off and sub:
+            return off, sub
+
+
+def _oracle_batch(oracle, oracle_settings, blobs, cs, ps):
+    """(status, (r, proof_lincomb, rhs, verdict) or None) of one batch by the oracle."""
+    from oracle.oracle import OracleError
+    try:
+        return 0, _want(oracle.verify_batch_intermediates(blobs, cs, ps, oracle_settings))
+    except OracleError as e:
+        return e.code, None
+
+
+def _intermediates(L, s, t_rec, n, groups):
+    out = C.create_string_buffer(128 * groups)
+    ok = (C.c_bool * groups)(); st = (C.c_int * groups)()
+    rc = L.kzg355_debug_batch_intermediates(out, ok, st, t_rec.data_ptr(), n, groups, s.handle)
+    assert rc == 0 and not any(st), (rc, list(st))
+    d = out.raw
+    return [(d[128 * g:128 * g + 32], d[128 * g + 32:128 * g + 80], d[128 * g + 80:128 * g + 128], bool(ok[g])) for g in range(groups)]
+
+
+def _want(inter):
+    return inter["r"], inter["proof_lincomb"], inter["rhs"], inter["ok"]
+
+
+def test_validate_points_on_a_batch_and_its_spoiled_copies(kz, setup_bytes, oracle, oracle_settings, fx64):
+    import torch
+    blobs, cs, ps = fx64
+    n = len(blobs)
+    off, sub = _special_points(oracle)
+    sub_neg = bytes([sub[0] ^ 0x20]) + sub[1:]                     # the other sign of y: the same x, still outside the subgroup
+    batches = [(list(cs), list(ps)) for _ in range(6)]
+    batches[1][0][5] = sub                                         # commitment outside the subgroup
+    batches[2][1][63] = off                                        # proof off the curve
+    batches[3][0][0] = INF                                         # infinity is a valid point (utils.rs:298-301): verdict false, no error
+    batches[4][1][63] = INF
+    batches[5][1][9] = sub_neg
+    G = len(batches)
+    want = [_oracle_batch(oracle, oracle_settings, blobs, c, p) for c, p in batches]
+    assert [w[0] for w in want] == [0, 1, 1, 0, 0, 1] and [w[1][3] for w in want if w[0] == 0] == [True, False, False]      # (the cases are what they claim)
+    L = kz.kzg.lib()
+    # lincomb_form = 2 pins the bucket form.  By size, 6 batches of 64 would take the pre-shifted form, whose stage 1 decodes with k_decompress_points and
+    # tests the subgroup with the DPP-quad ladder (verify_stages.hip: enqueue_points_beside) -- k_validate_points would never see the spoiled points.
+    s = _handle(kz, setup_bytes, lincomb_form=2)
+    try:
+        tb = _dev(torch, s, b"".join(blobs) * G)
+        tc = _dev(torch, s, b"".join(b"".join(c) for c, _ in batches))
+        tp = _dev(torch, s, b"".join(b"".join(p) for _, p in batches))
+        torch.cuda.synchronize()
+        # 1. the entry point the benchmark times, all six batches: k_validate_points on every point, verdicts and statuses
+        ok = (C.c_bool * G)(); st = (C.c_int * G)()
+        rc = L.kzg355_verify_blob_kzg_proof_batch_many_device(ok, st, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, G, s.handle)
+        print("many_device: rc", rc, "status", list(st), "ok", [bool(x) for x in ok], "oracle status", [w[0] for w in want])
+        assert rc == 1
+        assert [st[g] for g in range(G)] == [w[0] for w in want]
+        assert [bool(ok[g]) for g in range(G) if want[g][0] == 0] == [w[1][3] for w in want if w[0] == 0]
+        # 2. stage 1 alone on all six (never pre-shifted: k_validate_points again, on the packed inputs): the same status vector
+        rec = torch.zeros(160 * n * G, dtype=torch.uint8, device=tb.device)
+        torch.cuda.synchronize()
+        st1 = (C.c_int * G)()
+        rc = L.kzg355_verify_shard_records_device(rec.data_ptr(), st1, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, G, s.handle)
+        print("shard_records: rc", rc, "status", list(st1))
+        assert rc == 1 and [st1[g] for g in range(G)] == [w[0] for w in want]
+        # 3. the decoded points, through the sums they enter: the records of the batches without an error go through stage 2, which runs
+        #    k_validate_points once more on the points inside the records; r | proof_lincomb | rhs byte for byte
+        good = [g for g in range(G) if want[g][0] == 0]
+        good_rec = torch.cat([rec[160 * n * g:160 * n * (g + 1)] for g in good]).contiguous()
+        torch.cuda.synchronize()
+        got = _intermediates(L, s, good_rec, n, len(good))
+        for g, have in zip(good, got):
+            assert have == want[g][1], g
+    finally:
+        s.free()
+
+
+@pytest.fixture(scope="module")
+def small_batches(oracle, oracle_settings, fx64):
+    """Eight different 8-blob batches cut from the 64-blob fixture and the oracle's intermediates of each, plus batch 3 with two proofs swapped."""
+    blobs, cs, ps = fx64
+    cut = [(blobs[8 * j:8 * j + 8], cs[8 * j:8 * j + 8], ps[8 * j:8 * j + 8]) for j in range(8)]
+    want = [_want(oracle.verify_batch_intermediates(b, c, p, oracle_settings)) for b, c, p in cut]
+    b, c, p = cut[3]
+    sw = list(p); sw[2], sw[6] = sw[6], sw[2]
+    want_sw = _want(oracle.verify_batch_intermediates(b, c, sw, oracle_settings))
+    assert all(w[3] for w in want) and not want_sw[3]
+    return cut, want, sw, want_sw
+
+
+@pytest.mark.parametrize("chain_from", [1, 1 << 24], ids=["wsum+hchain_quad", "horner"])
+def test_bucket_tail_on_64_batches_of_8(chain_from, kz, setup_bytes, small_batches):
+    import torch
+    cut, want, sw, want_sw = small_batches
+    n, G, bad = 8, 64, 37                                          # batch g is cut[g % 8]; batch 37 (cut[5]) is replaced by the disturbed cut[3]
+    L = kz.kzg.lib()
+    s = _handle(kz, setup_bytes, lincomb_form=2, lc_chain_from=chain_from)
+    try:
+        order = [g % 8 for g in range(G)]
+        order[bad] = 3
+        tb = _dev(torch, s, b"".join(b"".join(cut[j][0]) for j in order))
+        tc = _dev(torch, s, b"".join(b"".join(cut[j][1]) for j in order))
+        tp = _dev(torch, s, b"".join(b"".join(sw if g == bad else cut[j][2]) for g, j in enumerate(order)))
+        rec = torch.zeros(160 * n * G, dtype=torch.uint8, device=tb.device)
+        torch.cuda.synchronize()
+        st1 = (C.c_int * G)()
+        assert L.kzg355_verify_shard_records_device(rec.data_ptr(), st1, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, G, s.handle) == 0 and not any(st1)
+        got = _intermediates(L, s, rec, n, G)
+        expect = [want_sw if g == bad else want[j] for g, j in enumerate(order)]
+        assert [g for g in range(G) if got[g] != expect[g]] == []
+        assert [g for g in range(G) if not got[g][3]] == [bad]
+        # and the entry point the benchmark times: verdicts only
+        ok = (C.c_bool * G)(); st = (C.c_int * G)()
+        assert L.kzg355_verify_blob_kzg_proof_batch_many_device(ok, st, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, G, s.handle) == 0
+        assert [g for g in range(G) if not ok[g]] == [bad] and not any(st)
+    finally:
+        s.free()
