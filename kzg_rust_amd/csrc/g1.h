@@ -32,6 +32,15 @@ KZG_HD void g1_from_affine(G1Jac &r, const G1Affine &a) {
     Fp one = fp_one(), zero = fp_zero();
     fp_select(r.z, inf, one, zero);
 }
+// Constants as values (consts_gen.h holds them as limb lists): beta, the cube root of unity of phi(x, y) = (beta x, y) = [-x^2](x, y); the generator G
+// and -G (the term -[sum r^i y_i] G of the batch check).
+KZG_HD Fp fp_beta() { const uint32_t c[NFP] = FP_BETA_INIT; Fp r; for (int i = 0; i < NFP; i++) r.l[i] = c[i]; return r; }
+KZG_HD G1Affine g1a_gen() {
+    const uint32_t gx[NFP] = G1_GEN_X_INIT, gy[NFP] = G1_GEN_Y_INIT;
+    G1Affine r; for (int i = 0; i < NFP; i++) { r.x.l[i] = gx[i]; r.y.l[i] = gy[i]; }
+    return r;
+}
+KZG_HD G1Affine g1a_neg_gen() { G1Affine r = g1a_gen(); fp_neg(r.y, r.y); return r; }
 
 // 2P, a = 0 (dbl-2009-l): 2M + 5S.  P = infinity stays infinity (z3 = 2 y z = 0).
 KZG_G1_MID void g1_dbl(G1Jac &r, const G1Jac &p) {
@@ -134,6 +143,26 @@ KZG_G1_MID void g1x_add_mixed(G1X &r, const G1X &a, const G1Affine &b) {
     fp_mul(r.zzz, a.zzz, PPP);
     r.x = X3; r.y = Y3;
 }
+// The tail the lazy additions below share (XYZZ names; the Jacobian form passes HHH for PPP and V for Q), stated ONCE here.  (g1x_add_mixed_lazy and
+// g1_add_quad keep the same lines written out: through the helpers the MSM kernels' instruction counts moved.)
+//   g1_lazy_x3:  in RR = R^2, PPP, Q < 2p (lazy products).  X3 = RR + (2p - PPP) + 2 (2p - Q) in (0, 8p);  t = Q + 8p - X3 in (0, 10p)
+//                (the partial sums stay in (0, 4p) and (0, 6p); X3 may be the variable that holds RR)
+//   g1_lazy_y3:  in S1 < 2p (Y1 ZZZ2, or Y1 Z2^3), R and t as above.  Y3 = R t + (2p - S1) PPP with 2p - S1 in (0, 2p], both products under ONE
+//                Montgomery reduction (fp_mul2_lz): < 2p
+KZG_HD void g1_lazy_x3(Fp &X3, Fp &t, const Fp &RR, const Fp &PPP, const Fp &Q) {
+    const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
+    Fp u;
+    fp_sub_lz(t, RR, PPP, m2);                                    // R^2 + 2p - PPP        in (0, 4p)
+    fp_sub_lz(u, t, Q, m2);                                       //  ... + 2p - Q         in (0, 6p)
+    fp_sub_lz(X3, u, Q, m2);                                      //  ... + 2p - Q         in (0, 8p)
+    fp_sub_lz(t, Q, X3, m8);                                      // Q + 8p - X3           in (0, 10p)
+}
+KZG_HD void g1_lazy_y3(Fp &Y3, const Fp &R, const Fp &t, const Fp &S1, const Fp &PPP) {
+    const uint32_t m2[NFP] = FP_MOD2_INIT;
+    Fp u;
+    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }          // 2p - S1               in (0, 2p]
+    fp_mul2_lz(Y3, R, t, u, PPP);
+}
 // The same addition on LAZY coordinates, for the accumulation loops: no conditional subtraction after any product, sum or
 // difference.  Invariant of the accumulator (in and out): X < 8p, Y < 4p, ZZ, ZZZ < 2p (limbs normalised); b canonical.
 //   U2, S2 < 2p;  P = U2 + 8p - X in (0, 10p);  R = S2 + 4p - Y in (0, 6p);  PP, PPP, Q < 2p
@@ -199,10 +228,10 @@ KZG_G1_MID void g1x_to_jac(G1Jac &r, const G1X &a) {
 // XYZZ + XYZZ on lazy coordinates (add-2008-s, 12M + 2S), both operands within the accumulator invariant above (X < 8p, Y < 4p,
 // ZZ, ZZZ < 2p) and the result within it again:
 //   U1 = X1 ZZ2, U2 = X2 ZZ1, S1 = Y1 ZZZ2, S2 = Y2 ZZZ1 < 2p;  P = U2 + 2p - U1, R = S2 + 2p - S1 in (0, 4p);  PP, PPP, Q < 2p
-//   X3 = R^2 + (2p - PPP) + 2 (2p - Q) in (0, 8p);  Y3 = R (Q + 8p - X3) + (2p - S1) PPP, one reduction for both products, < 2p;  ZZ3, ZZZ3 < 2p
+//   X3 by g1_lazy_x3 (PPP, Q < 2p), Y3 by g1_lazy_y3 (S1 < 2p): X3 in (0, 8p), Y3 < 2p;  ZZ3, ZZZ3 < 2p
 // An operand at infinity (ZZ = 0 mod p) or P possibly = 0 mod p (exact low-limb filters) goes through the canonical Jacobian addition.
 KZG_G1_MID void g1x_add_lazy2(G1X &r, const G1X &a, const G1X &b) {
-    const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
+    const uint32_t m2[NFP] = FP_MOD2_INIT;
     Fp U1, U2, S1, S2, ZZ12, ZZZ12, P, R;
     fp_mul_lz(U1, a.x, b.zz); fp_mul_lz(U2, b.x, a.zz);
     fp_mul_lz(S1, a.y, b.zzz); fp_mul_lz(S2, b.y, a.zzz);
@@ -217,15 +246,11 @@ KZG_G1_MID void g1x_add_lazy2(G1X &r, const G1X &a, const G1X &b) {
         r.x = jr.x; r.y = jr.y; fp_sqr(r.zz, jr.z); fp_mul(r.zzz, r.zz, jr.z);
         return;
     }
-    Fp PP, PPP, Q, t, u, X3, Y3;
+    Fp PP, PPP, Q, t, X3, Y3;
     fp_sqr_lz(PP, P); fp_mul_lz(PPP, P, PP); fp_mul_lz(Q, U1, PP);
     fp_sqr_lz(X3, R);
-    fp_sub_lz(t, X3, PPP, m2);                                    // in (0, 4p)
-    fp_sub_lz(u, t, Q, m2);                                       // in (0, 6p)
-    fp_sub_lz(X3, u, Q, m2);                                      // in (0, 8p)
-    fp_sub_lz(t, Q, X3, m8);                                      // in (0, 10p)
-    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }          // 2p - S1: in (0, 2p]
-    fp_mul2_lz(Y3, R, t, u, PPP);                                 // R (Q - X3) - S1 PPP under one reduction: < 2p  (k_lc_wsum is issue-bound)
+    g1_lazy_x3(X3, t, X3, PPP, Q);
+    g1_lazy_y3(Y3, R, t, S1, PPP);                                // R (Q - X3) - S1 PPP under one reduction  (k_lc_wsum is issue-bound)
     fp_mul_lz(r.zz, ZZ12, PP);
     fp_mul_lz(r.zzz, ZZZ12, PPP);
     r.x = X3; r.y = Y3;
@@ -306,59 +331,36 @@ KZG_G1_MID void g1_dbl_lazy(G1Jac &r, const G1Jac &p) {
     r.x = X3;
     fp_add_lz(r.z, u, u);                                        // Z3 = 2 Y Z                     < 2.02p
 }
-KZG_G1_MID void g1_add_lazy(G1Jac &r, const G1Jac &a, const G1Jac &b) {
-    const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
-    Fp Z1Z1, Z2Z2, U1, U2, S1, S2, H, R;
-    fp_sqr_lz(Z1Z1, a.z); fp_sqr_lz(Z2Z2, b.z);
-    fp_mul_lz(U1, a.x, Z2Z2); fp_mul_lz(U2, b.x, Z1Z1);
-    fp_mul_lz(S1, a.y, b.z); fp_mul_lz(S1, S1, Z2Z2);
-    fp_mul_lz(S2, b.y, a.z); fp_mul_lz(S2, S2, Z1Z1);
-    fp_sub_lz(H, U2, U1, m2);                                    // in (0, 4p)
-    fp_sub_lz(R, S2, S1, m2);
-    if (fp_maybe_zero_lz(H) || fp_maybe_zero_lz(a.z) || g1_is_inf(b)) {          // rare: the complete canonical addition
-        G1Jac c; fp_canon64(c.x, a.x); fp_canon64(c.y, a.y); fp_canon64(c.z, a.z);
-        g1_add(r, c, b);
-        return;
-    }
-    Fp HH, HHH, V, t, u;
-    fp_sqr_lz(HH, H); fp_mul_lz(HHH, H, HH); fp_mul_lz(V, U1, HH);
-    Fp X3, Y3, Z3;
-    fp_sqr_lz(X3, R);
-    fp_sub_lz(t, X3, HHH, m2); fp_sub_lz(u, t, V, m2); fp_sub_lz(X3, u, V, m2);        // in (0, 8p)
-    fp_sub_lz(t, V, X3, m8);                                                            // in (0, 10p)
-    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }                                // 2p - S1: in (0, 2p]
-    fp_mul2_lz(Y3, R, t, u, HHH);                                                       // R (V - X3) - S1 HHH under one reduction: < 2p
-    fp_mul_lz(Z3, a.z, b.z); fp_mul_lz(Z3, Z3, H);
-    r.x = X3; r.y = Y3; r.z = Z3;
-}
-// The same with BOTH operands lazy (b within the bounds g1_add_lazy leaves: X < 8p, Y < 4p, Z < 2p): b at infinity is then caught
-// by the low-limb filter too, and the rare path canonicalises both operands.
-KZG_G1_MID void g1_add_lazy2(G1Jac &r, const G1Jac &a, const G1Jac &b) {
-    const uint32_t m2[NFP] = FP_MOD2_INIT, m8[NFP] = FP_MOD8_INIT;
-    Fp Z1Z1, Z2Z2, U1, U2, S1, S2, H, R;
-    fp_sqr_lz(Z1Z1, a.z); fp_sqr_lz(Z2Z2, b.z);
-    fp_mul_lz(U1, a.x, Z2Z2); fp_mul_lz(U2, b.x, Z1Z1);
-    fp_mul_lz(S1, a.y, b.z); fp_mul_lz(S1, S1, Z2Z2);
-    fp_mul_lz(S2, b.y, a.z); fp_mul_lz(S2, S2, Z1Z1);
-    fp_sub_lz(H, U2, U1, m2);                                    // in (0, 4p)
-    fp_sub_lz(R, S2, S1, m2);
-    if (fp_maybe_zero_lz(H) || fp_maybe_zero_lz(a.z) || fp_maybe_zero_lz(b.z)) {      // rare: the complete canonical addition
-        G1Jac c, d; fp_canon64(c.x, a.x); fp_canon64(c.y, a.y); fp_canon64(c.z, a.z); fp_canon64(d.x, b.x); fp_canon64(d.y, b.y); fp_canon64(d.z, b.z);
-        g1_add(r, c, d);
-        return;
-    }
-    Fp HH, HHH, V, t, u;
-    fp_sqr_lz(HH, H); fp_mul_lz(HHH, H, HH); fp_mul_lz(V, U1, HH);
-    Fp X3, Y3, Z3;
-    fp_sqr_lz(X3, R);
-    fp_sub_lz(t, X3, HHH, m2); fp_sub_lz(u, t, V, m2); fp_sub_lz(X3, u, V, m2);        // in (0, 8p)
-    fp_sub_lz(t, V, X3, m8);                                                            // in (0, 10p)
-    { const Fp z = fp_zero(); fp_sub_lz(u, z, S1, m2); }                                // 2p - S1: in (0, 2p]
-    fp_mul2_lz(Y3, R, t, u, HHH);                                                       // R (V - X3) - S1 HHH under one reduction: < 2p
-    fp_mul_lz(Z3, a.z, b.z); fp_mul_lz(Z3, Z3, H);
-    r.x = X3; r.y = Y3; r.z = Z3;
-}
 KZG_HD void g1_canon_lazy(G1Jac &r, const G1Jac &a) { fp_canon64(r.x, a.x); fp_canon64(r.y, a.y); fp_canon64(r.z, a.z); }
+// One body for both lazy Jacobian additions (add-2007-bl without the 2's, 11M + 5S).  B_LAZY = false: b canonical, so its infinity is the exact
+// Z = 0 and the rare path takes it as it is; B_LAZY = true: b within the bounds this addition leaves (X < 8p, Y < 4p, Z < 2p), its infinity is
+// caught by the low-limb filter too, and the rare path makes both operands canonical.
+//   U1, U2, S1, S2 < 2p;  H = U2 + 2p - U1, R = S2 + 2p - S1 in (0, 4p);  HH, HHH, V < 2p;  X3 by g1_lazy_x3 (HHH, V < 2p), Y3 by g1_lazy_y3 (S1 < 2p)
+template <bool B_LAZY> KZG_HD void g1_add_lazy_body(G1Jac &r, const G1Jac &a, const G1Jac &b) {
+    const uint32_t m2[NFP] = FP_MOD2_INIT;
+    Fp Z1Z1, Z2Z2, U1, U2, S1, S2, H, R;
+    fp_sqr_lz(Z1Z1, a.z); fp_sqr_lz(Z2Z2, b.z);
+    fp_mul_lz(U1, a.x, Z2Z2); fp_mul_lz(U2, b.x, Z1Z1);
+    fp_mul_lz(S1, a.y, b.z); fp_mul_lz(S1, S1, Z2Z2);
+    fp_mul_lz(S2, b.y, a.z); fp_mul_lz(S2, S2, Z1Z1);
+    fp_sub_lz(H, U2, U1, m2);                                    // in (0, 4p)
+    fp_sub_lz(R, S2, S1, m2);
+    if (fp_maybe_zero_lz(H) || fp_maybe_zero_lz(a.z) || (B_LAZY ? fp_maybe_zero_lz(b.z) : g1_is_inf(b))) {      // rare: the complete canonical addition
+        G1Jac c; g1_canon_lazy(c, a);
+        if constexpr (B_LAZY) { G1Jac d; g1_canon_lazy(d, b); g1_add(r, c, d); } else g1_add(r, c, b);
+        return;
+    }
+    Fp HH, HHH, V, t;
+    fp_sqr_lz(HH, H); fp_mul_lz(HHH, H, HH); fp_mul_lz(V, U1, HH);
+    Fp X3, Y3, Z3;
+    fp_sqr_lz(X3, R);
+    g1_lazy_x3(X3, t, X3, HHH, V);
+    g1_lazy_y3(Y3, R, t, S1, HHH);                               // R (V - X3) - S1 HHH under one reduction
+    fp_mul_lz(Z3, a.z, b.z); fp_mul_lz(Z3, Z3, H);
+    r.x = X3; r.y = Y3; r.z = Z3;
+}
+KZG_G1_MID void g1_add_lazy(G1Jac &r, const G1Jac &a, const G1Jac &b) { g1_add_lazy_body<false>(r, a, b); }
+KZG_G1_MID void g1_add_lazy2(G1Jac &r, const G1Jac &a, const G1Jac &b) { g1_add_lazy_body<true>(r, a, b); }
 
 // [|x|] P for the BLS parameter |x| = 0xd201000000010000 (weight 6), lazy chain, canonical result.  p canonical.
 KZG_HD void g1_mul_x_abs(G1Jac &r, const G1Jac &p) {
@@ -369,21 +371,24 @@ KZG_HD void g1_mul_x_abs(G1Jac &r, const G1Jac &p) {
     }
     g1_canon_lazy(r, acc);
 }
-KZG_HD bool g1_in_subgroup(const G1Affine &p) {
-    if (g1a_is_inf(p)) return true;
-    G1Jac pj, t;
-    g1_from_affine(pj, p);
-    g1_mul_x_abs(t, pj);
-    g1_mul_x_abs(t, t);                  // [x^2]P
+// phi(P) == -T for an affine P (not infinity) and a canonical Jacobian T = [x^2]P: beta x Z^2 == X and y Z^3 == -Y.  T at infinity: false.
+KZG_HD bool g1_phi_matches(const G1Affine &p, const G1Jac &t) {
     if (g1_is_inf(t)) return false;
-    const uint32_t bc[NFP] = FP_BETA_INIT;
-    Fp beta; for (int i = 0; i < NFP; i++) beta.l[i] = bc[i];
+    const Fp beta = fp_beta();
     Fp z2, z3, lhs, rhs;
     fp_sqr(z2, t.z); fp_mul(z3, z2, t.z);
     fp_mul(lhs, p.x, beta); fp_mul(lhs, lhs, z2);      // beta x Z^2 == X
     if (!fp_eq(lhs, t.x)) return false;
     fp_mul(lhs, p.y, z3); fp_neg(rhs, t.y);            // y Z^3 == -Y
     return fp_eq(lhs, rhs);
+}
+KZG_HD bool g1_in_subgroup(const G1Affine &p) {
+    if (g1a_is_inf(p)) return true;
+    G1Jac pj, t;
+    g1_from_affine(pj, p);
+    g1_mul_x_abs(t, pj);
+    g1_mul_x_abs(t, t);                  // [x^2]P
+    return g1_phi_matches(p, t);
 }
 // Reference form of the same predicate, kept for the unit tests: [r]P == infinity.
 KZG_HD bool g1_in_subgroup_naive(const G1Affine &p) {
@@ -478,8 +483,7 @@ KZG_HD void glv_split_fast(uint32_t a[4], uint32_t b[4], const uint32_t k[8]) {
 }
 // -phi(P) = (beta x, -y)
 KZG_HD void g1a_neg_phi(G1Affine &r, const G1Affine &p) {
-    const uint32_t bc[NFP] = FP_BETA_INIT;
-    Fp beta; for (int i = 0; i < NFP; i++) beta.l[i] = bc[i];
+    const Fp beta = fp_beta();
     fp_mul(r.x, p.x, beta);
     fp_neg(r.y, p.y);
     if (g1a_is_inf(p)) r = p;

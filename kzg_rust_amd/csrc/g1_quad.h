@@ -105,12 +105,5 @@ __device__ __forceinline__ void g1_add_quad(G1Jac &r, const G1Jac &a, const G1Ja
     r.x = X3; r.z = Z3;
     if (rare) g1_add(r, ca, cb);
 }
-__device__ __forceinline__ G1Jac g1_shfl_down_w(const G1Jac &v, int delta) {
-    G1Jac r;
-#pragma unroll
-    for (int i = 0; i < NFP; i++) { r.x.l[i] = __shfl_down(v.x.l[i], delta, 64); r.y.l[i] = __shfl_down(v.y.l[i], delta, 64); r.z.l[i] = __shfl_down(v.z.l[i],
-            delta, 64); }
-    return r;
-}
 
 }  // namespace kzg

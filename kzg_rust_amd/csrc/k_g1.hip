@@ -13,34 +13,16 @@
 namespace kzg {
 
 // ------------------------------------------------------------------------------------------------ points
-// thread j < n_total: commitment j ; j >= n_total: proof j - n_total.
-__device__ __forceinline__ void validate_points_body(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group, G1Affine *pts, int *err,
+// Helpers of this section, each described once here:
+//   decode_point_to_slot   thread j < n_total: commitment j; j >= n_total: proof j - n_total.  48 bytes -> affine point -> ERR_BAD_POINT on the
+//                          point's group i / n_per_group -> its slot in the [group][commitments | proofs] layout (infinity where the decoding
+//                          failed).  SUBGROUP adds the subgroup test, and only that form may be given pts = null (the error word alone is wanted).
+//                          stride 48: packed arrays; RECORD_BYTES: fields of records.
+//   subgroup_ladder_quad   [x^2] base by a DPP quad: two passes of the 63-step ladder for |x| = 0xd201000000010000, canonical result.  ONE loop with
+//                          one inlined instance of each quad routine; a kernel calls it once.
+template <bool SUBGROUP>
+__device__ __forceinline__ void decode_point_to_slot(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group, G1Affine *pts, int *err,
         int stride) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= 2 * n_total) return;
-    const bool is_proof = j >= n_total;
-    if (is_proof && !proofs) return;
-    const int i = is_proof ? j - n_total : j;
-    const uint8_t *src = (is_proof ? proofs : commitments) + (size_t)stride * i;     // 48: packed arrays; 160: fields of records
-    uint8_t b[48];
-    for (int k = 0; k < 48; k++) b[k] = src[k];
-    G1Affine p;
-    int rc = g1_decompress(p, b);
-    if (rc == 0 && !g1a_is_inf(p) && !g1_in_subgroup(p)) rc = 3;     // infinity is accepted (utils.rs:298-301)
-    const int g = i / n_per_group, k = i % n_per_group;
-    if (rc != 0) { atomicOr(&err[g], ERR_BAD_POINT); p = g1a_inf(); }
-    if (pts) pts[(size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k)] = p;
-}
-__global__ void __launch_bounds__(256, 2) k_validate_points(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group,
-                                                         G1Affine *pts, int *err, int stride) {
-    validate_points_body(commitments, proofs, n_total, n_per_group, pts, err, stride);
-}
-
-// The two halves of k_validate_points as kernels of their own, for the single-proof entry point: the linear combination only needs
-// the decompressed points, the subgroup test only feeds the error word -- so the test runs on the side stream beside the rest of the
-// chain (1.2 of verify_kzg_proof's 6.1 ms).
-__global__ void __launch_bounds__(64) k_decompress_points(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group,
-                                                          G1Affine *pts, int *err, int stride) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= 2 * n_total) return;
     const bool is_proof = j >= n_total;
@@ -50,9 +32,36 @@ __global__ void __launch_bounds__(64) k_decompress_points(const uint8_t *commitm
     uint8_t b[48];
     for (int k = 0; k < 48; k++) b[k] = src[k];
     G1Affine p;
+    int rc = g1_decompress(p, b);
+    if (SUBGROUP && rc == 0 && !g1a_is_inf(p) && !g1_in_subgroup(p)) rc = 3;     // infinity is accepted (utils.rs:298-301)
     const int g = i / n_per_group, k = i % n_per_group;
-    if (g1_decompress(p, b) != 0) { atomicOr(&err[g], ERR_BAD_POINT); p = g1a_inf(); }
-    pts[(size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k)] = p;
+    if (rc != 0) { atomicOr(&err[g], ERR_BAD_POINT); p = g1a_inf(); }
+    if (!SUBGROUP || pts) pts[(size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k)] = p;
+}
+__device__ __forceinline__ G1Jac subgroup_ladder_quad(const G1Jac &start, int role) {
+    G1Jac base = start, t = start;
+#pragma unroll 1
+    for (int step = 0; step < 126; step++) {
+        const int i = 62 - (step % 63);
+        if (step == 63) { g1_canon_lazy(t, t); base = t; }       // second ladder: [|x|] of the first one's result
+        g1_dbl_quad(t, role);
+        if ((BLS_X_ABS >> i) & 1) g1_add_quad(t, t, base, role);  // (a constant exponent: the branch is uniform)
+    }
+    g1_canon_lazy(t, t);
+    return t;
+}
+
+__global__ void __launch_bounds__(256, 2) k_validate_points(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group,
+                                                         G1Affine *pts, int *err, int stride) {
+    decode_point_to_slot<true>(commitments, proofs, n_total, n_per_group, pts, err, stride);
+}
+
+// The two halves of k_validate_points as kernels of their own, for the single-proof entry point: the linear combination only needs
+// the decompressed points, the subgroup test only feeds the error word -- so the test runs on the side stream beside the rest of the
+// chain (1.2 of verify_kzg_proof's 6.1 ms).
+__global__ void __launch_bounds__(64) k_decompress_points(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group,
+                                                          G1Affine *pts, int *err, int stride) {
+    decode_point_to_slot<false>(commitments, proofs, n_total, n_per_group, pts, err, stride);
 }
 __global__ void __launch_bounds__(64) k_subgroup_points(const G1Affine *pts, int n_points, int n_per_group, int *err, int commitments_only) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -73,28 +82,8 @@ __global__ void __launch_bounds__(256) k_subgroup_points_quad(const G1Affine *pt
     G1Affine p = pts[skip ? 0 : j];
     if (skip) p = g1a_inf();
     G1Jac base; g1_from_affine(base, p);
-    G1Jac t = base;
-    // one loop, one inlined instance of each quad routine: two passes of the 63-step ladder for |x| = 0xd201000000010000
-#pragma unroll 1
-    for (int step = 0; step < 126; step++) {
-        const int i = 62 - (step % 63);
-        if (step == 63) { g1_canon_lazy(t, t); base = t; }       // second ladder: [|x|] of the first one's result
-        g1_dbl_quad(t, role);
-        if ((BLS_X_ABS >> i) & 1) g1_add_quad(t, t, base, role);  // (a constant exponent: the branch is uniform)
-    }
-    g1_canon_lazy(t, t);
-    bool ok = true;
-    if (!g1a_is_inf(p)) {
-        ok = !g1_is_inf(t);
-        const uint32_t bc[NFP] = FP_BETA_INIT;
-        Fp beta; for (int q = 0; q < NFP; q++) beta.l[q] = bc[q];
-        Fp z2, z3, lhs, rhs;
-        fp_sqr(z2, t.z); fp_mul(z3, z2, t.z);
-        fp_mul(lhs, p.x, beta); fp_mul(lhs, lhs, z2);             // beta x Z^2 == X
-        ok = ok && fp_eq(lhs, t.x);
-        fp_mul(lhs, p.y, z3); fp_neg(rhs, t.y);                   // y Z^3 == -Y
-        ok = ok && fp_eq(lhs, rhs);
-    }
+    const G1Jac t = subgroup_ladder_quad(base, role);
+    const bool ok = g1a_is_inf(p) || g1_phi_matches(p, t);
     if (!skip && role == 0 && !ok) atomicOr(&err[j / (2 * n_per_group)], ERR_BAD_POINT);      // infinity is accepted (utils.rs:298-301)
 }
 
@@ -116,16 +105,7 @@ __global__ void __launch_bounds__(256) k_subgroup_ladder_from_x_quad(const uint8
     G1Jac base;
     fp_mul(base.x, sv, x); fp_sqr(base.y, sv); base.z = fp_one();
     if (inf) base = g1_inf();
-    G1Jac t = base;
-    // one loop, one inlined instance of each quad routine: two passes of the 63-step ladder for |x| = 0xd201000000010000
-#pragma unroll 1
-    for (int step = 0; step < 126; step++) {
-        const int bit = 62 - (step % 63);
-        if (step == 63) { g1_canon_lazy(t, t); base = t; }       // second ladder: [|x|] of the first one's result
-        g1_dbl_quad(t, role);
-        if ((BLS_X_ABS >> bit) & 1) g1_add_quad(t, t, base, role);   // (a constant exponent: the branch is uniform)
-    }
-    g1_canon_lazy(t, t);
+    const G1Jac t = subgroup_ladder_quad(base, role);
     if (live && role == 0) T[i] = t;
 }
 // pts: the decoded points in the [group][commitments | proofs] layout with one commitment per group (slot 2 i); T: the ladder's results on E''
@@ -135,32 +115,13 @@ __global__ void __launch_bounds__(64) k_subgroup_finish(const G1Affine *pts, con
     const G1Affine p = pts[2 * (size_t)i];
     if (g1a_is_inf(p)) return;                                    // infinity is accepted (utils.rs:298-301); a point that failed to decode was flagged there
     G1Jac t = T[i];
-    Fp tz; fp_mul(tz, t.z, p.y);                                  // (X, Y, Z) on E'' = (X, Y, y Z) on E
-    bool ok = !fp_is_zero(tz);
-    const uint32_t bc[NFP] = FP_BETA_INIT;
-    Fp beta; for (int q = 0; q < NFP; q++) beta.l[q] = bc[q];
-    Fp z2, z3, lhs, rhs;
-    fp_sqr(z2, tz); fp_mul(z3, z2, tz);
-    fp_mul(lhs, p.x, beta); fp_mul(lhs, lhs, z2);                 // beta x Z^2 == X
-    ok = ok && fp_eq(lhs, t.x);
-    fp_mul(lhs, p.y, z3); fp_neg(rhs, t.y);                       // y Z^3 == -Y
-    ok = ok && fp_eq(lhs, rhs);
-    if (!ok) atomicOr(&err[i], ERR_BAD_POINT);
+    fp_mul(t.z, t.z, p.y);                                        // (X, Y, Z) on E'' = (X, Y, y Z) on E
+    if (!g1_phi_matches(p, t)) atomicOr(&err[i], ERR_BAD_POINT);
 }
 
 // Decompress the C_i / proof_i fields of gathered records (already validated by their owner rank).
 __global__ void __launch_bounds__(64) k_points_from_records(const uint8_t *records, int n_total, int n_per_group, G1Affine *pts, int *err) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= 2 * n_total) return;
-    const bool is_proof = j >= n_total;
-    const int i = is_proof ? j - n_total : j;
-    const uint8_t *src = records + (size_t)RECORD_BYTES * i + (is_proof ? 112 : 0);
-    uint8_t b[48];
-    for (int k = 0; k < 48; k++) b[k] = src[k];
-    G1Affine p;
-    const int g = i / n_per_group, k = i % n_per_group;
-    if (g1_decompress(p, b) != 0) { atomicOr(&err[g], ERR_BAD_POINT); p = g1a_inf(); }
-    pts[(size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k)] = p;
+    decode_point_to_slot<false>(records, records + 112, n_total, n_per_group, pts, err, RECORD_BYTES);      // C_i at offset 0, proof_i at 112
 }
 
 // ------------------------------------------------------------------------------------------------ lincomb
@@ -176,19 +137,25 @@ __global__ void __launch_bounds__(64) k_points_from_records(const uint8_t *recor
 //                     the wave (shuffles, no LDS) -> 2 partial points per wave
 //   k_lincomb_finish  one workgroup per batch: lane c sums the partials of class c and converts to affine (the two
 //                     inversions run side by side) -> (-proof_lincomb, rhs) for the pairing.
-__device__ __forceinline__ G1Jac g1_shfl_down8(const G1Jac &v, int delta) {      // within segments of 8 lanes
+// Helpers of this section and the ones below it:
+//   g1_shfl<WIDTH, XOR>   a Jacobian point from another lane, limb by limb: __shfl_xor or __shfl_down within segments of WIDTH lanes
+//   the term map          term t of a batch is  t in [0, n): a_t proof_t, class 0;  [n, 2n): b_(t-n) proof_(t-n);  [2n, 3n): a_(t-2n) C_(t-2n);
+//                         3n: c (-G) -- all class 1.  k_lincomb_terms and k_lc_prep each walk it in place (a shared helper moved k_lc_prep's registers)
+//   ps_point_of_item      the same map for the pre-shifted form: the point of item j (items 2t, 2t + 1 belong to term t) as an index into
+//                         [commitments | proofs | -G]
+template <int WIDTH, bool XOR> __device__ __forceinline__ G1Jac g1_shfl(const G1Jac &v, int arg) {
+    auto mv = [&](uint32_t x) { return XOR ? __shfl_xor(x, arg, WIDTH) : __shfl_down(x, arg, WIDTH); };
     G1Jac r;
 #pragma unroll
-    for (int i = 0; i < NFP; i++) { r.x.l[i] = __shfl_down(v.x.l[i], delta, 8); r.y.l[i] = __shfl_down(v.y.l[i], delta, 8); r.z.l[i] = __shfl_down(v.z.l[i],
-            delta, 8); }
+    for (int i = 0; i < NFP; i++) { r.x.l[i] = mv(v.x.l[i]); r.y.l[i] = mv(v.y.l[i]); r.z.l[i] = mv(v.z.l[i]); }
     return r;
 }
-__device__ __forceinline__ G1Jac g1_shfl_xor(const G1Jac &v, int mask) {
-    G1Jac r;
-#pragma unroll
-    for (int i = 0; i < NFP; i++) { r.x.l[i] = __shfl_xor(v.x.l[i], mask, 64); r.y.l[i] = __shfl_xor(v.y.l[i], mask, 64); r.z.l[i] = __shfl_xor(v.z.l[i], mask,
-            64); }
-    return r;
+__device__ __forceinline__ G1Jac g1_shfl_xor(const G1Jac &v, int mask) { return g1_shfl<64, true>(v, mask); }
+__device__ __forceinline__ G1Jac g1_shfl_down16(const G1Jac &v, int delta) { return g1_shfl<16, false>(v, delta); }     // within segments of 16 lanes
+__device__ __forceinline__ G1Jac g1_shfl_down_w(const G1Jac &v, int delta) { return g1_shfl<64, false>(v, delta); }
+__device__ __forceinline__ int ps_point_of_item(int j, int n) {
+    const int t = j >> 1;
+    return t < n ? n + t : t < 2 * n ? n + (t - n) : t < 3 * n ? t - 2 * n : 2 * n;
 }
 __host__ __device__ inline int lincomb_waves_per_group(int n) { return (2 * (3 * n + 1) + 63) / 64; }
 
@@ -207,13 +174,7 @@ __global__ void __launch_bounds__(64) k_lincomb_terms(const G1Affine *pts, const
         if (t < n) { p = gp[n + t]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + t) + q]; cls = 0; }
         else if (t < 2 * n) { p = gp[n + (t - n)]; for (int q = 0; q < 8; q++) k[q] = scal_b[8 * ((size_t)g * n + (t - n)) + q]; cls = 1; }
         else if (t < 3 * n) { p = gp[t - 2 * n]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + (t - 2 * n)) + q]; cls = 1; }
-        else {
-            const uint32_t gx[NFP] = G1_GEN_X_INIT, gy[NFP] = G1_GEN_Y_INIT;
-            for (int q = 0; q < NFP; q++) { p.x.l[q] = gx[q]; p.y.l[q] = gy[q]; }
-            fp_neg(p.y, p.y);
-            for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q];
-            cls = 1;
-        }
+        else { p = g1a_neg_gen(); for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q]; cls = 1; }
         uint32_t ka[4], kb[4];
         glv_split(ka, kb, k);
         if (half) { G1Affine q; g1a_neg_phi(q, p); p = q; }
@@ -255,12 +216,7 @@ __global__ void __launch_bounds__(64) k_lincomb_single(const G1Affine *pts, cons
     const G1Affine *gp = pts + 2 * (size_t)g;                     // [0] commitment, [1] proof
     G1Affine p; uint32_t k[8];
     if (q < 2) { p = gp[1]; for (int w = 0; w < 8; w++) k[w] = scal_b[8 * (size_t)g + w]; }      // [z] proof       (kzg.rs:415-418 moved to the G1 side)
-    else {                                                                                        // [y] (-G)        (kzg.rs:421)
-        const uint32_t gx[NFP] = G1_GEN_X_INIT, gy[NFP] = G1_GEN_Y_INIT;
-        for (int w = 0; w < NFP; w++) { p.x.l[w] = gx[w]; p.y.l[w] = gy[w]; }
-        fp_neg(p.y, p.y);
-        for (int w = 0; w < 8; w++) k[w] = scal_c[8 * (size_t)g + w];
-    }
+    else { p = g1a_neg_gen(); for (int w = 0; w < 8; w++) k[w] = scal_c[8 * (size_t)g + w]; }    // [y] (-G)        (kzg.rs:421)
     uint32_t ka[4], kb[4];
     glv_split_fast(ka, kb, k);                                    // (z, y leave k_rpowers reduced below r < 2^255)
     if (q & 1) { G1Affine t; g1a_neg_phi(t, p); p = t; }
@@ -316,12 +272,7 @@ __global__ void __launch_bounds__(64) k_lc_prep(const G1Affine *pts, const uint3
     if (t < n) { p = gp[n + t]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + t) + q]; }
     else if (t < 2 * n) { p = gp[n + (t - n)]; for (int q = 0; q < 8; q++) k[q] = scal_b[8 * ((size_t)g * n + (t - n)) + q]; }
     else if (t < 3 * n) { p = gp[t - 2 * n]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + (t - 2 * n)) + q]; }
-    else {
-        const uint32_t gx[NFP] = G1_GEN_X_INIT, gy[NFP] = G1_GEN_Y_INIT;
-        for (int q = 0; q < NFP; q++) { p.x.l[q] = gx[q]; p.y.l[q] = gy[q]; }
-        fp_neg(p.y, p.y);
-        for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q];
-    }
+    else { p = g1a_neg_gen(); for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q]; }
     uint32_t half[2][4];
     glv_split(half[0], half[1], k);
     G1Affine q2; g1a_neg_phi(q2, p);
@@ -487,13 +438,6 @@ __global__ void __launch_bounds__(256) k_lc_buckets(const G1Affine *items, const
     }
 }
 
-__device__ __forceinline__ G1Jac g1_shfl_down16(const G1Jac &v, int delta) {     // within segments of 16 lanes
-    G1Jac r;
-#pragma unroll
-    for (int i = 0; i < NFP; i++) { r.x.l[i] = __shfl_down(v.x.l[i], delta, 16); r.y.l[i] = __shfl_down(v.y.l[i], delta, 16); r.z.l[i] = __shfl_down(v.z.l[i],
-            delta, 16); }
-    return r;
-}
 // 256-thread workgroups: four waves, one per SIMD of the CU the workgroup lands on (64-thread workgroups of this latency-bound chain
 // were placed two to a SIMD while other SIMDs idled: 2.9 instead of 1.9 ms per 2048 batches); the waves share nothing.
 __global__ void __launch_bounds__(256) k_lc_horner(const LcSlot *S, int groups, PairPt *pair_pts) {
@@ -670,23 +614,15 @@ __global__ void __launch_bounds__(PS_SHIFT_THREADS) k_ps_shift(const G1Affine *p
         }
     }
 }
-// item j of a batch -> index of its point in the shift table (items 2t, 2t+1 belong to term t; see k_lc_prep)
-__device__ __forceinline__ int ps_point_of_item(int j, int n) {
-    const int t = j >> 1;
-    return t < n ? n + t : t < 2 * n ? n + (t - n) : t < 3 * n ? t - 2 * n : 2 * n;
-}
 // Sums with "no term yet" as a flag instead of the point at infinity (see k_ps_buckets): acc (+)= o where `have` / `ho` say which of the two
 // hold a sum.  The quad addition always runs (every lane takes part in its DPP moves) -- on fixed stand-ins for an absent operand, G and
 // phi(G) = (beta x_G, y_G): two points that differ and are not each other's negatives, so the stand-in addition never takes the rare path.
 struct PsDummies { G1Jac a, b; };
 __device__ __forceinline__ PsDummies ps_dummies() {
-    const uint32_t gx[NFP] = G1_GEN_X_INIT, gy[NFP] = G1_GEN_Y_INIT, bc[NFP] = FP_BETA_INIT;
     PsDummies d;
-    Fp beta;
-    for (int i = 0; i < NFP; i++) { d.a.x.l[i] = gx[i]; d.a.y.l[i] = gy[i]; beta.l[i] = bc[i]; }
-    d.a.z = fp_one();
+    g1_from_affine(d.a, g1a_gen());
     d.b = d.a;
-    fp_mul(d.b.x, d.a.x, beta);
+    fp_mul(d.b.x, d.a.x, fp_beta());
     return d;
 }
 __device__ __forceinline__ void g1_select(G1Jac &r, bool take_b, const G1Jac &a, const G1Jac &b) {
@@ -727,15 +663,14 @@ __global__ void __launch_bounds__(PS_THREADS) k_ps_buckets(const G1Jac *shifts, 
     }
     __syncthreads();
     const int c = cnt;
-    const uint32_t bc[NFP] = FP_BETA_INIT;
-    Fp beta; for (int i = 0; i < NFP; i++) beta.l[i] = bc[i];
+    const Fp beta = fp_beta();
     auto fetch = [&](int j, int w, bool neg) -> G1Jac {
         const int pt = ps_point_of_item(j, n);
         G1Jac p = sh[(size_t)pt * LC_WINDOWS + w];
         {   // the shift table holds points of E'' (k_ps_shift): Z picks up the y of the input point (zero for the point at infinity)
             Fp y0;
             if (pt < 2 * n) y0 = pts[(size_t)g * 2 * n + pt].y;
-            else { const uint32_t gy[NFP] = G1_GEN_Y_INIT; for (int q = 0; q < NFP; q++) y0.l[q] = gy[q]; fp_neg(y0, y0); }
+            else y0 = g1a_neg_gen().y;
             Fp zz; fp_mul(zz, p.z, y0); p.z = zz;
         }
         if (j & 1) { Fp bx; fp_mul(bx, p.x, beta); p.x = bx; neg = !neg; }       // the odd item of a term is -phi(P) = (beta x, -y)
@@ -874,62 +809,71 @@ static size_t lc_glists_entries(int n_per_group, int groups) {
     if (40 * (size_t)n_per_group + 14 <= (size_t)LC_TASKS * LC_LDS_LIST) return 0;
     return (((size_t)groups * 4 * LC_TASKS * lc_list_stride(n_per_group)) + 7) & ~(size_t)7;
 }
+// The scratch of the bucket form, carved once: items | S | digits (padded to 256 bytes) | glists | W.  The pre-shifted form uses the first three.
+struct LcScratch {
+    G1Affine *items; LcSlot *S; int8_t *digits; uint16_t *glists; G1Jac *W;
+    size_t bytes;                                                 // what the allocation has always been: the parts, the digits unpadded, + 512
+    LcScratch(void *d_scratch, int n_per_group, int groups) {
+        const size_t ni = (size_t)lc_items(n_per_group) * groups;
+        uintptr_t at = reinterpret_cast<uintptr_t>(d_scratch);    // (integer arithmetic: a null d_scratch asks for the size alone)
+        auto take = [&](size_t nbytes) { const uintptr_t r = at; at += nbytes; return r; };
+        items = reinterpret_cast<G1Affine *>(take(ni * sizeof(G1Affine)));
+        S = reinterpret_cast<LcSlot *>(take((size_t)2 * LC_WINDOWS * LC_BUCKETS * groups * sizeof(LcSlot)));
+        const size_t dig = ni * LC_DIG_STRIDE, dig_padded = (dig + 255) & ~(size_t)255;
+        digits = reinterpret_cast<int8_t *>(take(dig_padded));
+        glists = reinterpret_cast<uint16_t *>(take(lc_glists_entries(n_per_group, groups) * sizeof(uint16_t)));
+        W = reinterpret_cast<G1Jac *>(take((size_t)2 * LC_WINDOWS * groups * sizeof(G1Jac)));
+        bytes = (size_t)(at - reinterpret_cast<uintptr_t>(d_scratch)) - (dig_padded - dig) + 512;
+    }
+};
+static void launch_lc_prep(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group, int groups,
+        const LcScratch &sc, hipStream_t st) {
+    const int nt = 3 * n_per_group + 1;
+    hipLaunchKernelGGL(k_lc_prep, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, sc.items, sc.digits);
+}
 void launch_lincomb_buckets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group,
                             int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st, int stage, int chain_from) {
     if (groups <= 0) return;
-    const size_t ni = (size_t)lc_items(n_per_group) * groups;
-    G1Affine *items = reinterpret_cast<G1Affine *>(d_scratch);
-    LcSlot *S = reinterpret_cast<LcSlot *>(items + ni);
-    int8_t *digits = reinterpret_cast<int8_t *>(S + (size_t)2 * LC_WINDOWS * LC_BUCKETS * groups);
-    uint16_t *glists = reinterpret_cast<uint16_t *>(digits + ((ni * LC_DIG_STRIDE + 255) & ~(size_t)255));
-    const int nt = 3 * n_per_group + 1;
-    if (stage == 0 || stage == 1) hipLaunchKernelGGL(k_lc_prep, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, d_scal_a, d_scal_b, d_scal_c,
-            n_per_group, items, digits);
-    if (stage == 0 || stage == 2) hipLaunchKernelGGL(k_lc_buckets, dim3(groups), dim3(256), 0, st, items, digits, n_per_group, S, glists,
+    const LcScratch sc(d_scratch, n_per_group, groups);
+    if (stage == 0 || stage == 1) launch_lc_prep(d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, st);
+    if (stage == 0 || stage == 2) hipLaunchKernelGGL(k_lc_buckets, dim3(groups), dim3(256), 0, st, sc.items, sc.digits, n_per_group, sc.S, sc.glists,
             groups >= chain_from ? 1 : 0);
     if (stage == 0 || stage == 3) {
         if (groups >= chain_from) {
-            G1Jac *W = reinterpret_cast<G1Jac *>(glists + lc_glists_entries(n_per_group, groups));
-            hipLaunchKernelGGL(k_lc_wsum, dim3((2 * LC_WINDOWS * groups + 255) / 256), dim3(256), 0, st, S, groups, W);
-            hipLaunchKernelGGL(k_lc_hchain_quad, dim3((8 * groups + 255) / 256), dim3(256), 0, st, W, groups, d_pair_pts);
-        } else hipLaunchKernelGGL(k_lc_horner, dim3((2 * LC_BUCKETS * groups + 255) / 256), dim3(256), 0, st, S, groups, d_pair_pts);
+            hipLaunchKernelGGL(k_lc_wsum, dim3((2 * LC_WINDOWS * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, sc.W);
+            hipLaunchKernelGGL(k_lc_hchain_quad, dim3((8 * groups + 255) / 256), dim3(256), 0, st, sc.W, groups, d_pair_pts);
+        } else hipLaunchKernelGGL(k_lc_horner, dim3((2 * LC_BUCKETS * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, d_pair_pts);
     }
 }
 size_t lincomb_buckets_scratch_bytes(int n_per_group, int groups) {
-    const size_t ni = (size_t)lc_items(n_per_group) * groups;
-    const size_t lists = lc_glists_entries(n_per_group, groups) * sizeof(uint16_t) + (size_t)2 * LC_WINDOWS * groups * sizeof(G1Jac);    // + the window sums W
-    return ni * sizeof(G1Affine) + (size_t)2 * LC_WINDOWS * LC_BUCKETS * groups * sizeof(LcSlot) + ni * LC_DIG_STRIDE + 512 + lists;
+    return LcScratch(nullptr, n_per_group, groups).bytes;
 }
 bool lincomb_preshift_fits(int n_per_group, int groups) { return n_per_group >= 1 && n_per_group <= PS_MAX_N && groups >= 1 && groups < 64; }
 size_t lincomb_preshift_bytes(int n_per_group, int groups) { return sizeof(G1Jac) * (size_t)ps_points(n_per_group) * LC_WINDOWS * groups; }
-void launch_lincomb_preshift(const G1Affine *d_pts, int n_per_group, int groups, G1Jac *d_shifts, hipStream_t st) {
+static void launch_ps_shift(const G1Affine *d_pts, const uint8_t *d_commitments, const uint8_t *d_proofs, int stride, int n_per_group, int groups,
+        G1Jac *d_shifts, hipStream_t st) {
     if (groups <= 0) return;
     const int total = ps_points(n_per_group) * groups;
-    hipLaunchKernelGGL(k_ps_shift, dim3((4 * total + PS_SHIFT_THREADS - 1) / PS_SHIFT_THREADS), dim3(PS_SHIFT_THREADS), 0, st, d_pts, (const uint8_t *)nullptr,
-            (const uint8_t *)nullptr, 0, n_per_group, groups, d_shifts);
+    hipLaunchKernelGGL(k_ps_shift, dim3((4 * total + PS_SHIFT_THREADS - 1) / PS_SHIFT_THREADS), dim3(PS_SHIFT_THREADS), 0, st, d_pts, d_commitments, d_proofs,
+            stride, n_per_group, groups, d_shifts);
+}
+void launch_lincomb_preshift(const G1Affine *d_pts, int n_per_group, int groups, G1Jac *d_shifts, hipStream_t st) {
+    launch_ps_shift(d_pts, nullptr, nullptr, 0, n_per_group, groups, d_shifts, st);
 }
 void launch_lincomb_preshift_bytes(const uint8_t *d_commitments, const uint8_t *d_proofs, int stride, int n_per_group, int groups, G1Jac *d_shifts,
         hipStream_t st) {
-    if (groups <= 0) return;
-    const int total = ps_points(n_per_group) * groups;
-    hipLaunchKernelGGL(k_ps_shift, dim3((4 * total + PS_SHIFT_THREADS - 1) / PS_SHIFT_THREADS), dim3(PS_SHIFT_THREADS), 0, st, (const G1Affine *)nullptr,
-            d_commitments, d_proofs, stride, n_per_group, groups, d_shifts);
+    launch_ps_shift(nullptr, d_commitments, d_proofs, stride, n_per_group, groups, d_shifts, st);
 }
 // stage 0: everything; 1: the digits only (needs the decoded points and the r powers, not the shift table); 2: the sums
 void launch_lincomb_preshifted(const G1Affine *d_pts, const G1Jac *d_shifts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c,
         int n_per_group,
                                int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st, int stage) {
     if (groups <= 0) return;
-    const size_t ni = (size_t)lc_items(n_per_group) * groups;
-    G1Affine *items = reinterpret_cast<G1Affine *>(d_scratch);          // same scratch layout as the bucket form (lincomb_buckets_scratch_bytes)
-    LcSlot *S = reinterpret_cast<LcSlot *>(items + ni);
-    int8_t *digits = reinterpret_cast<int8_t *>(S + (size_t)2 * LC_WINDOWS * LC_BUCKETS * groups);
-    const int nt = 3 * n_per_group + 1;
-    if (stage == 0 || stage == 1) hipLaunchKernelGGL(k_lc_prep, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, d_scal_a, d_scal_b, d_scal_c,
-            n_per_group, items, digits);
+    const LcScratch sc(d_scratch, n_per_group, groups);           // same scratch as the bucket form (lincomb_buckets_scratch_bytes)
+    if (stage == 0 || stage == 1) launch_lc_prep(d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, st);
     if (stage == 1) return;
-    hipLaunchKernelGGL(k_ps_buckets, dim3(2 * groups * LC_BUCKETS), dim3(PS_THREADS), 0, st, d_shifts, d_pts, digits, n_per_group, S);
-    hipLaunchKernelGGL(k_ps_weights, dim3(2 * groups), dim3(64), 0, st, S, groups, d_pair_pts);
+    hipLaunchKernelGGL(k_ps_buckets, dim3(2 * groups * LC_BUCKETS), dim3(PS_THREADS), 0, st, d_shifts, d_pts, sc.digits, n_per_group, sc.S);
+    hipLaunchKernelGGL(k_ps_weights, dim3(2 * groups), dim3(64), 0, st, sc.S, groups, d_pair_pts);
 }
 size_t lincomb_partials_bytes(int n_per_group, int groups) {
     const size_t waves = (size_t)lincomb_waves_per_group(n_per_group) * groups;

@@ -7,7 +7,12 @@ at the smallest shapes that reach them, against the CPU oracle:
     the pre-shifted form, which validates with other kernels) and through stage 1 alone; the decoded points are compared through what they feed --
     proof_lincomb and rhs, byte for byte (the ABI has no readback of the points themselves).
   * the tail of the bucket form: 64 batches of 8 blobs with the handle's chain threshold at 1 (k_lc_wsum: g1x_add_lazy2; k_lc_hchain_quad) and lifted
-    out of reach (k_lc_horner: g1_dbl_lazy + g1_add_lazy): r, proof_lincomb and rhs byte for byte, one disturbed batch found at its position."""
+    out of reach (k_lc_horner: g1_dbl_lazy + g1_add_lazy): r, proof_lincomb and rhs byte for byte, one disturbed batch found at its position.
+  * the reject branches of the latency forms of the validation, on one valid commitment and five spoiled encodings of it: lone compute_blob_kzg_proof
+    calls (k_decompress_points; k_subgroup_ladder_from_x_quad + k_subgroup_finish) and lone verify_kzg_proof calls (entry_points.hip: the record's two
+    points go through enqueue_points_beside -- k_decompress_points, then k_subgroup_points_quad since there are few points): statuses, and proofs /
+    verdicts where there is no error, as the oracle gives them.  The same six checks in ONE verify_kzg_proof_many call take the other route
+    (verify_records_impl with validate = 1: the fused k_validate_points on the fields of the records) and must give the same answers."""
 import ctypes as C
 import json
 import os
@@ -166,5 +171,77 @@ def test_bucket_tail_on_64_batches_of_8(chain_from, kz, setup_bytes, small_batch
         ok = (C.c_bool * G)(); st = (C.c_int * G)()
         assert L.kzg355_verify_blob_kzg_proof_batch_many_device(ok, st, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, G, s.handle) == 0
         assert [g for g in range(G) if not ok[g]] == [bad] and not any(st)
+    finally:
+        s.free()
+
+
+FP_MODULUS = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+
+
+@pytest.fixture(scope="module")
+def six_encodings(oracle, fx64):
+    """The fixture's first commitment and five spoiled encodings: infinity (valid), on the curve but outside the subgroup, x not on the curve, x >= p,
+    no compression bit."""
+    c = fx64[1][0]
+    off, sub = _special_points(oracle)
+    x_ge_p = bytearray(FP_MODULUS.to_bytes(48, "big")); x_ge_p[0] |= 0x80
+    enc = [c, INF, sub, off, bytes(x_ge_p), bytes([c[0] & 0x7F]) + c[1:]]
+    assert [oracle.g1_uncompress_only(e) == 0 for e in enc] == [True, True, True, False, False, False]      # (the cases are what they claim)
+    assert [oracle.g1_validate(e) == 0 for e in enc] == [True, True, False, False, False, False]
+    return enc
+
+
+def test_lone_compute_blob_kzg_proof_on_spoiled_commitments(kz, setup_bytes, oracle, oracle_settings, fx64, six_encodings):
+    from oracle.oracle import OracleError
+    blob = fx64[0][0]
+    L = kz.kzg.lib()
+    s = _handle(kz, setup_bytes)
+    try:
+        got, want = [], []
+        for c in six_encodings:
+            out = C.create_string_buffer(48)
+            rc = L.kzg355_compute_blob_kzg_proof(out, blob, c, s.handle)
+            got.append((rc, out.raw if rc == 0 else None))
+            try:
+                want.append((0, oracle.compute_blob_kzg_proof(blob, c, oracle_settings)))
+            except OracleError as e:
+                want.append((e.code, None))
+        print("compute_blob_kzg_proof: status", [g[0] for g in got], "oracle status", [w[0] for w in want])
+        assert [w[0] for w in want] == [0, 0, 1, 1, 1, 1] and want[0][1] == fx64[2][0]
+        assert got == want
+    finally:
+        s.free()
+
+
+def test_verify_kzg_proof_lone_and_many_on_spoiled_commitments(kz, setup_bytes, oracle, oracle_settings, fx64, six_encodings):
+    from oracle.oracle import OracleError
+    blob = fx64[0][0]
+    z = (0x1234567).to_bytes(32, "big")
+    proof, y = oracle.compute_kzg_proof(blob, z, oracle_settings)
+    want = []
+    for c in six_encodings:
+        try:
+            want.append((0, oracle.verify_kzg_proof(c, z, y, proof, oracle_settings)))
+        except OracleError as e:
+            want.append((e.code, None))
+    assert want == [(0, True), (0, False), (1, None), (1, None), (1, None), (1, None)]
+    n = len(six_encodings)
+    L = kz.kzg.lib()
+    s = _handle(kz, setup_bytes)
+    try:
+        # lone calls: k_decompress_points + k_subgroup_points_quad
+        lone = []
+        for c in six_encodings:
+            one = C.c_bool()
+            rc = L.kzg355_verify_kzg_proof(C.byref(one), c, z, y, proof, s.handle)
+            lone.append((rc, bool(one.value) if rc == 0 else None))
+        print("verify_kzg_proof: (status, ok)", lone, "oracle", want)
+        assert lone == want
+        # one call of six: k_validate_points on the records
+        ok = (C.c_bool * n)(); st = (C.c_int * n)()
+        rc = L.kzg355_verify_kzg_proof_many(ok, st, b"".join(six_encodings), z * n, y * n, proof * n, n, s.handle)
+        print("verify_kzg_proof_many: rc", rc, "status", list(st), "ok", [bool(x) for x in ok], "oracle", want)
+        assert rc == 1
+        assert [(st[i], bool(ok[i]) if st[i] == 0 else None) for i in range(n)] == want
     finally:
         s.free()
