@@ -376,6 +376,21 @@ int kzg355_recover_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL *
 int kzg355_recover_cells_and_kzg_proofs_many(uint8_t *cells_out /* m*128*2048 or NULL */, uint8_t *proofs_out /* m*128*48 or NULL */,
                                              int *status /* m or NULL */, const size_t *cell_indices /* n, shared by all blobs */,
                                              const uint8_t *cells /* m*n*2048: blob after blob */, size_t n, size_t m, const kzg355_settings *s);
+/* m independent recover_cells_and_kzg_proofs calls in one set of launches: blob i is known at cell_counts[i] cells; with
+ * off_i = cell_counts[0] + .. + cell_counts[i-1], its indices are cell_indices[off_i .. off_i + cell_counts[i]) and its cells
+ * cells + 2048 * off_i, in the same order.  Outputs as kzg355_recover_cells_and_kzg_proofs_many (either may be NULL, not both).
+ * The result is exactly that of m single calls (a node that catches up recovers many blocks, each with its own columns).  What is wrong with
+ * one blob is that blob's KZG355_BADARGS: a count outside 64..128 (0 included), an index >= 128, indices not strictly ascending, a cell element
+ * >= r.  The other blobs are computed and are right: the layout always follows the counts as given.  The return value is the first non-OK
+ * status; the output slots of a refused blob are unspecified.  What is wrong with the call refuses it as a whole and marks every status: a NULL
+ * handle, both outputs NULL, NULL cell_counts, cell_indices or cells with m > 0, a handle of another FIELD_ELEMENTS_PER_BLOB, m > 2^32, a sum of
+ * the counts that overflows size_t (or does so times 2048).  m == 0 -> OK, and nothing is touched.  More than 64 cells of a blob that lie on no
+ * polynomial of degree < 4096 are no error: that blob's result is the single call's.  Blobs known at the same index set share its tables
+ * wherever they sit in the call.  Mainnet handles only; a handle over several devices runs on its first device.  Large m runs in chunks. */
+int kzg355_recover_cells_and_kzg_proofs_many_sets(uint8_t *cells_out /* m*128*2048 or NULL */, uint8_t *proofs_out /* m*128*48 or NULL */,
+                                                  int *status /* m or NULL */, const size_t *cell_counts /* m */,
+                                                  const size_t *cell_indices /* sum of the counts */,
+                                                  const uint8_t *cells /* (sum of the counts)*2048 */, size_t m, const kzg355_settings *s);
 /* Test form: the FK20 intermediates H_0 .. H_63 of each blob, compressed (H_e = sum_{m >= 64(e+1)} f_m [tau^(m - 64(e+1))]_1; H_63 = infinity). */
 int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
 /* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */
@@ -406,6 +421,10 @@ int kzg355_compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out /* n*12
 int kzg355_recover_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out /* m*128*2048 or NULL */, uint8_t *d_proofs_out /* m*128*48 or NULL */,
                                                     int *status /* host, m or NULL */, const size_t *cell_indices /* HOST, n, shared by all blobs */,
                                                     const uint8_t *d_cells /* m*n*2048: blob after blob */, size_t n, size_t m, const kzg355_settings *s);
+/* kzg355_recover_cells_and_kzg_proofs_many_sets with d_cells and both outputs in HBM (16-byte aligned, as the other *_device cell calls; a
+ * misaligned pointer refuses the call as a whole); counts and indices stay HOST arguments.  The cells are read where they are. */
+int kzg355_recover_cells_and_kzg_proofs_many_sets_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const size_t *cell_counts,
+                                                         const size_t *cell_indices, const uint8_t *d_cells, size_t m, const kzg355_settings *s);
 /* Test form of the device verify call: the 176 bytes per group of kzg355_debug_cell_batch_intermediates, with the preparation pinned by
  * prep_form: 0 by shape (what the call above does), 1 on the device, 2 copy back and prepare on the host; anything else is KZG355_BADARGS. */
 int kzg355_debug_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,

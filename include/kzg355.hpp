@@ -211,6 +211,41 @@ struct Kzg {
         return out;
     }
 
+    // One independent recover_cells_and_kzg_proofs per unit (cell_indices, cells) in one set of launches: every blob brings its own index set.
+    // One Result per unit; a unit whose two lengths differ is BadArgs for the call.
+    using RecoverUnit = std::pair<std::vector<size_t>, std::vector<Cell>>;
+    static Result<std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>>> recover_cells_and_kzg_proofs_many_sets(
+        const std::vector<RecoverUnit> &units, const KzgSettings &s) {
+        const size_t m = units.size();
+        std::vector<size_t> counts, indices;
+        std::vector<uint8_t> in;
+        for (const RecoverUnit &u : units) {
+            if (u.first.size() != u.second.size()) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(u.first.size());
+            indices.insert(indices.end(), u.first.begin(), u.first.end());
+            for (const Cell &c : u.second) in.insert(in.end(), c.data(), c.data() + KZG355_BYTES_PER_CELL);
+        }
+        const size_t per_cells = (size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL, per_proofs = (size_t)KZG355_CELLS_PER_EXT_BLOB * 48;
+        std::vector<uint8_t> c(per_cells * (m + 1)), p(per_proofs * (m + 1));
+        std::vector<int> st(m + 1, 0);
+        indices.push_back(0);                                      // (data() of an empty vector may be null)
+        in.push_back(0);
+        int rc = kzg355_recover_cells_and_kzg_proofs_many_sets(c.data(), p.data(), st.data(), counts.data(), indices.data(), in.data(), m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_many_sets");
+        std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>> out;
+        for (size_t i = 0; i < m; i++) {
+            if (st[i]) { out.push_back(from_status(st[i], "recover_cells")); continue; }
+            std::pair<std::vector<Cell>, std::vector<KzgProof>> r;
+            for (int k = 0; k < KZG355_CELLS_PER_EXT_BLOB; k++) {
+                r.first.push_back(Cell::from_bytes(&c[per_cells * i + (size_t)k * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+                r.second.push_back(KzgProof::from_bytes(&p[per_proofs * i + (size_t)k * 48], 48).value());
+            }
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+
     // ---- the three cell calls on device-resident data (kzg355.h: pointer and alignment rules).  The d_* arguments are device pointers on the
     // handle's device; one Result per unit, an Err of the call itself only for whole-call failures (whole_call_failed, below).
     static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_device(const uint8_t *d_commitments, const size_t *d_cell_indices,
@@ -245,6 +280,26 @@ struct Kzg {
                                                                  s.raw());
         st.resize(m);
         if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_many_device");
+        return st;
+    }
+
+    // blob i known at cell_counts[i] cells: its indices (host) and its cells (device) follow those of blob i - 1
+    static Result<std::vector<int>> recover_cells_and_kzg_proofs_many_sets_device(uint8_t *d_cells_out, uint8_t *d_proofs_out,
+                                                                                  const std::vector<size_t> &cell_counts,
+                                                                                  const std::vector<size_t> &cell_indices, const uint8_t *d_cells,
+                                                                                  const KzgSettings &s) {
+        const size_t m = cell_counts.size();
+        size_t total = 0;
+        for (size_t c : cell_counts) {
+            if (c > cell_indices.size() - total) return Error{Error::BadArgs, "length mismatch"};
+            total += c;
+        }
+        if (total != cell_indices.size()) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<int> st(m + 1, 0);
+        int rc = kzg355_recover_cells_and_kzg_proofs_many_sets_device(d_cells_out, d_proofs_out, st.data(), cell_counts.data(), cell_indices.data(), d_cells,
+                                                                      m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_many_sets_device");
         return st;
     }
 

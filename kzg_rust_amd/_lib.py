@@ -99,11 +99,13 @@ def load():
         "kzg355_compute_cells_and_kzg_proofs_many": [u8p, u8p, ip, u8p, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs": [u8p, u8p, szp, u8p, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many": [u8p, u8p, ip, szp, u8p, sz, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_many_sets": [u8p, u8p, ip, szp, szp, u8p, sz, vp],
         "kzg355_debug_cell_compute_h": [u8p, ip, u8p, sz, vp],
         "kzg355_debug_cell_setup_monomial_all": [u8p, vp],
         "kzg355_verify_cell_kzg_proof_batch_many_device": [bp, ip, vp, vp, vp, vp, sz, sz, vp],
         "kzg355_compute_cells_and_kzg_proofs_many_device": [vp, vp, ip, vp, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many_device": [vp, vp, ip, szp, vp, sz, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_many_sets_device": [vp, vp, ip, szp, szp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
     }
     for name, args in sigs.items():
@@ -152,4 +154,5 @@ EXPORTED_SYMBOLS = [
     "kzg355_recover_cells_and_kzg_proofs", "kzg355_recover_cells_and_kzg_proofs_many",
     "kzg355_verify_cell_kzg_proof_batch_many_device", "kzg355_compute_cells_and_kzg_proofs_many_device",
     "kzg355_recover_cells_and_kzg_proofs_many_device", "kzg355_debug_cell_batch_intermediates_device", "kzg355_settings_cell_device_prep_calls",
+    "kzg355_recover_cells_and_kzg_proofs_many_sets", "kzg355_recover_cells_and_kzg_proofs_many_sets_device",
 ]

@@ -1,60 +1,139 @@
 // cell_recover.hip -- the C entry points of recover_cells_and_kzg_proofs (EIP-7594 cells; include/kzg355.h; host side of libkzg355.so, see
-// engine.h).  The host checks the index set, copies the known cells in and cells / proofs out and sets the statuses.  The erasure decoding runs
+// engine.h).  The host checks the index sets, copies the known cells in and cells / proofs out and sets the statuses.  The erasure decoding runs
 // in the kernels of k_cell_recover.hip and leaves, per blob, what the field stage of compute_cells_and_kzg_proofs leaves: the coefficients and
 // the 128 cells.  The chunk loop and the proofs are that call's own (cell_compute.hip: cc_run).
 #include "engine.h"
 
 namespace kzg355_impl {
 
-// cells: m blobs of n cells each, the cells of a blob at the n strictly ascending indices idx (one set for all blobs; always host memory).
-// device: cells, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are
-static int rc_impl(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *idx, const uint8_t *cells, size_t n, size_t m,
-                   const kzg355_settings *cs, bool device = false) {
-    auto refuse = [&](int code) { return cc_refuse(status, m, code); };
-    if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
-    if (n < (size_t)CELLS_PER_EXT_BLOB / 2 || n > (size_t)CELLS_PER_EXT_BLOB || !idx) return refuse(KZG355_BADARGS);
-    int pos[CELLS_PER_EXT_BLOB];
-    for (int k = 0; k < CELLS_PER_EXT_BLOB; k++) pos[k] = -1;
+// The 128-bit mask of an index list (mask[0] bits 0..63, mask[1] bits 64..127); false unless it has 64..128 strictly ascending indices < 128.
+static bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n) {
+    mask[0] = mask[1] = 0;
+    if (n < (size_t)CELLS_PER_EXT_BLOB / 2 || n > (size_t)CELLS_PER_EXT_BLOB) return false;
     for (size_t i = 0; i < n; i++) {
-        if (idx[i] >= (size_t)CELLS_PER_EXT_BLOB || (i && idx[i] <= idx[i - 1])) return refuse(KZG355_BADARGS);
-        pos[idx[i]] = (int)i;
+        if (idx[i] >= (size_t)CELLS_PER_EXT_BLOB || (i && idx[i] <= idx[i - 1])) return false;
+        mask[idx[i] >> 6] |= (uint64_t)1 << (idx[i] & 63);
     }
-    if (m == 0) return KZG355_OK;
-    if (!cells) return refuse(KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
-    const size_t in_bytes = (size_t)CELL_BYTES * n;               // per blob
+    return true;
+}
+
+// What every recover call runs, once its arguments are checked (m > 0).  counts null: the shared-set calls, every blob known at the n indices
+// idx (a valid list).  Otherwise blob i is known at counts[i] cells and its index list and cells start counts[0] + .. + counts[i-1] entries
+// into idx and cells (the sum does not overflow); a blob whose list is refused gets KZG355_BADARGS and the others do not notice.
+// Per chunk the distinct masks are numbered (blobs with the same set share one RecoverTables wherever they sit), and w->z holds, one after
+// the other: the chunk's tables, the masks of its sets and the descriptors of its blobs.
+// device: cells, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are
+static_assert(sizeof(RecoverTables) % alignof(RecoverBlob) == 0, "the masks and descriptors behind the tables in w->z are 8-byte aligned");
+static int rc_run(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *counts, const size_t *idx, size_t n, const uint8_t *cells,
+                  size_t m, const kzg355_settings *cs, bool device) {
+    uint64_t shared_mask[2] = {0, 0};
+    if (!counts) rc_mask(shared_mask, idx, n);
+    size_t max_sets = 0, next = 0;                               // tables per chunk; the call's cells before the chunk about to be staged
+    std::vector<uint64_t> up;                                    // what a chunk uploads: 2 * max_sets mask words, then RecoverBlob per blob
+    std::vector<int> refused;                                    // the chunk's err words, when the host refuses one of its blobs
     return cc_run(cs, m, cells_out, proofs_out, nullptr, status,
-        // the workspace's buffers by role: blobs = known cells, z = the call's tables, scal_b = u (cell interpolants, then P_r(a_k))
+        // the workspace's buffers by role: blobs = known cells, z = tables, masks and descriptors, scal_b = u (cell interpolants, then P_r(a_k))
         [&](Workspace *w, size_t CH) {
+            max_sets = counts ? CH : 1;
+            up.resize(2 * max_sets + sizeof(RecoverBlob) / sizeof(uint64_t) * CH);
             int rc;
-            if ((!device && (rc = w->blobs.ensure(in_bytes * CH))) || (rc = w->z.ensure(sizeof(RecoverTables)))) return rc;
+            if ((!device && (rc = w->blobs.ensure((size_t)CELL_BYTES * (counts ? (size_t)CELLS_PER_EXT_BLOB : n) * CH))) ||
+                (rc = w->z.ensure(sizeof(RecoverTables) * max_sets + sizeof(uint64_t) * up.size())))
+                return rc;
             return w->scal_b.ensure(sizeof(Fr) * CELLS_PER_EXT_BLOB * CELL_FE * CH);
         },
         [&](Workspace *w, Timed &tm, size_t c0, int mc, uint8_t *d_cells) -> int {
             const CellComputeConsts *cc = cs->cc_consts.as<CellComputeConsts>();
             RecoverTables *rt = w->z.as<RecoverTables>();
+            uint64_t *d_up = reinterpret_cast<uint64_t *>(rt + max_sets);
+            const RecoverBlob *d_desc = reinterpret_cast<const RecoverBlob *>(d_up + 2 * max_sets);
+            RecoverBlob *desc = reinterpret_cast<RecoverBlob *>(up.data() + 2 * max_sets);
             hipStream_t st = w->stream;
-            const uint8_t *d_known = device ? cells + in_bytes * c0 : w->blobs.as<uint8_t>();
-            if (!device) HIPCHK(hipMemcpyAsync(w->blobs.p, cells + in_bytes * c0, in_bytes * mc, hipMemcpyHostToDevice, st));
-            if (c0 == 0) {
-                HIPCHK(hipMemcpyAsync(rt->pos, pos, sizeof(pos), hipMemcpyHostToDevice, st));
-                tm.begin("rc_vanish");
-                launch_rc_vanish(cc, rt, st);
-                tm.end();
+            // the chunk's sets and descriptors.  The host form packs the accepted blobs' cells into w->blobs (at most 128 each, whatever a refused
+            // blob's count says), run of neighbours by run; the device form reads them where they are, from the chunk's first cell on.
+            std::map<std::pair<uint64_t, uint64_t>, int> sets;
+            const size_t base = next;
+            size_t staged = 0, run_src = 0, run_dst = 0, run_len = 0;
+            bool any_refused = false;
+            refused.assign(mc, 0);
+            auto flush = [&]() -> int {
+                if (run_len) HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + run_dst * CELL_BYTES, cells + run_src * CELL_BYTES, run_len * CELL_BYTES,
+                                                   hipMemcpyHostToDevice, st));
+                run_len = 0;
+                return KZG355_OK;
+            };
+            for (int b = 0; b < mc; b++) {
+                const size_t cnt = counts ? counts[c0 + b] : n;
+                uint64_t mask[2] = {shared_mask[0], shared_mask[1]};
+                int rc;
+                if (counts && !rc_mask(mask, idx + next, cnt)) {
+                    desc[b] = RecoverBlob{0, -1, 0};
+                    refused[b] = ERR_NONCANONICAL_FR;           // any err word is this blob's KZG355_BADARGS (status_from_err)
+                    any_refused = true;
+                    if ((rc = flush())) return rc;
+                } else {
+                    const int set = sets.emplace(std::make_pair(mask[0], mask[1]), (int)sets.size()).first->second;
+                    up[2 * set] = mask[0];
+                    up[2 * set + 1] = mask[1];
+                    desc[b] = RecoverBlob{device ? next - base : staged, set, 0};
+                    if (!device) {
+                        if (!run_len) { run_src = next; run_dst = staged; }
+                        run_len += cnt;
+                        staged += cnt;
+                    }
+                }
+                next += cnt;
             }
+            int rc;
+            if ((rc = flush())) return rc;
+            HIPCHK(hipMemcpyAsync(d_up, up.data(), sizeof(uint64_t) * up.size(), hipMemcpyHostToDevice, st));
+            if (any_refused) HIPCHK(hipMemcpyAsync(w->err.p, refused.data(), sizeof(int) * mc, hipMemcpyHostToDevice, st));
+            const uint8_t *d_known = device ? cells + base * CELL_BYTES : w->blobs.as<uint8_t>();
+            tm.begin("rc_vanish");
+            launch_rc_vanish(cc, d_up, (int)sets.size(), rt, st);
+            tm.end();
             tm.begin("rc_interp");
-            launch_rc_interp(d_known, (int)n, mc, cc, rt, w->scal_b.as<Fr>(), w->err.as<int>(), st);
+            launch_rc_interp(d_known, d_desc, mc, cc, rt, w->scal_b.as<Fr>(), w->err.as<int>(), st);
             tm.end();
             tm.begin("rc_columns");
-            launch_rc_columns(w->scal_b.as<Fr>(), mc, cc, rt, proofs_out ? w->y.as<Fr>() : nullptr, cells_out != nullptr, st);
+            launch_rc_columns(w->scal_b.as<Fr>(), d_desc, mc, cc, rt, proofs_out ? w->y.as<Fr>() : nullptr, cells_out != nullptr, st);
             tm.end();
             if (cells_out) {
                 tm.begin("rc_cells");
-                launch_rc_cells(w->scal_b.as<Fr>(), mc, cc, d_cells, st);
+                launch_rc_cells(w->scal_b.as<Fr>(), d_desc, mc, cc, d_cells, st);
                 tm.end();
             }
             return KZG355_OK;
         }, device);
+}
+
+// m blobs of n cells each, the cells of a blob at the n strictly ascending indices idx (one set for all blobs; always host memory)
+static int rc_shared(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *idx, const uint8_t *cells, size_t n, size_t m,
+                     const kzg355_settings *cs, bool device = false) {
+    auto refuse = [&](int code) { return cc_refuse(status, m, code); };
+    if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
+    uint64_t mask[2];
+    if (!idx || !rc_mask(mask, idx, n)) return refuse(KZG355_BADARGS);
+    if (m == 0) return KZG355_OK;
+    if (!cells) return refuse(KZG355_BADARGS);
+    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
+    return rc_run(cells_out, proofs_out, status, nullptr, idx, n, cells, m, cs, device);
+}
+
+// m blobs, blob i known at counts[i] cells: its index list and its cells follow those of blob i - 1 in idx and cells
+static int rc_sets(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *counts, const size_t *idx, const uint8_t *cells, size_t m,
+                   const kzg355_settings *cs, bool device) {
+    auto refuse = [&](int code) { return cc_refuse(status, m, code); };
+    if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
+    if (m == 0) return KZG355_OK;
+    if (!counts || !idx || !cells || m > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
+    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
+    size_t total = 0;
+    for (size_t i = 0; i < m; i++) {
+        if (counts[i] > SIZE_MAX / CELL_BYTES - total) return refuse(KZG355_BADARGS);    // the sum, in bytes of cells, stays a size_t
+        total += counts[i];
+    }
+    return rc_run(cells_out, proofs_out, status, counts, idx, 0, cells, m, cs, device);
 }
 
 }  // namespace kzg355_impl
@@ -64,17 +143,27 @@ extern "C" {
 
 int kzg355_recover_cells_and_kzg_proofs_many(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *cell_indices, const uint8_t *cells,
                                              size_t n, size_t m, const kzg355_settings *s) {
-    return rc_impl(cells_out, proofs_out, status, cell_indices, cells, n, m, s);
+    return rc_shared(cells_out, proofs_out, status, cell_indices, cells, n, m, s);
 }
 
 int kzg355_recover_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const size_t *cell_indices,
                                                     const uint8_t *d_cells, size_t n, size_t m, const kzg355_settings *s) {
-    return rc_impl(d_cells_out, d_proofs_out, status, cell_indices, d_cells, n, m, s, true);
+    return rc_shared(d_cells_out, d_proofs_out, status, cell_indices, d_cells, n, m, s, true);
 }
 
 int kzg355_recover_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const size_t *cell_indices, const uint8_t *cells, size_t n,
                                         const kzg355_settings *s) {
-    return rc_impl(cells_out, proofs_out, nullptr, cell_indices, cells, n, 1, s);
+    return rc_shared(cells_out, proofs_out, nullptr, cell_indices, cells, n, 1, s);
+}
+
+int kzg355_recover_cells_and_kzg_proofs_many_sets(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *cell_counts,
+                                                  const size_t *cell_indices, const uint8_t *cells, size_t m, const kzg355_settings *s) {
+    return rc_sets(cells_out, proofs_out, status, cell_counts, cell_indices, cells, m, s, false);
+}
+
+int kzg355_recover_cells_and_kzg_proofs_many_sets_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const size_t *cell_counts,
+                                                         const size_t *cell_indices, const uint8_t *d_cells, size_t m, const kzg355_settings *s) {
+    return rc_sets(d_cells_out, d_proofs_out, status, cell_counts, cell_indices, d_cells, m, s, true);
 }
 
 #pragma GCC visibility pop

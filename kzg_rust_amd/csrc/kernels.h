@@ -244,18 +244,28 @@ void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *
 void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
 
 // ---- k_cell_recover.hip: the field stage of recover_cells_and_kzg_proofs (64..128 known cells -> coefficients and all 128 cells; mainnet handles only)
-struct RecoverTables {
+struct RecoverTables {                                        // one per distinct index set of a chunk
     Fr sd[CELLS_PER_EXT_BLOB];                               // S(a_k) / (64 * 128), S the vanishing polynomial of the missing cells' a_m
     Fr sci[CELLS_PER_EXT_BLOB];                              // 1 / (128 S(w a_k))
-    int pos[CELLS_PER_EXT_BLOB];                             // cell k's place in the call's index list, -1 if missing (written by the host)
+    int pos[CELLS_PER_EXT_BLOB];                             // cell k's place in the set's ascending index list, -1 if missing
 };
-// once per call (the index set is shared by the call's blobs): sd and sci from pos
-void launch_rc_vanish(const CellComputeConsts *d_cc, RecoverTables *d_rt, hipStream_t st);
-// d_cells: m blobs of n_cells cells each; d_u: m * 128 * 64 Fr ([blob][cell][column]); non-canonical elements -> ERR_NONCANONICAL_FR in d_err[blob]
-void launch_rc_interp(const uint8_t *d_cells, int n_cells, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_u, int *d_err,
-                      hipStream_t st);
-// d_coef (or null): m * 4096 Fr, the layout launch_cc_columns reads; want_cells: d_u receives P_r(a_k) for all 128 cells
-void launch_rc_columns(Fr *d_u, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_coef, bool want_cells, hipStream_t st);
-void launch_rc_cells(const Fr *d_u, int m, const CellComputeConsts *d_cc, uint8_t *d_cells /* m * 128 * 2048 */, hipStream_t st);
+// a blob of the chunk: its index set (the tables are d_rt[set]; set < 0: refused by the host, no transform runs for it) and where its known cells
+// start, in cells from d_cells
+struct RecoverBlob {
+    uint64_t first;
+    int set, pad;
+};
+// workgroup per set of the chunk: pos, sd and sci of d_rt[set] from the set's 128-bit mask (d_masks[2 set] bits 0..63, d_masks[2 set + 1] bits 64..127)
+void launch_rc_vanish(const CellComputeConsts *d_cc, const uint64_t *d_masks, int sets, RecoverTables *d_rt, hipStream_t st);
+// d_cells: the known cells of the chunk's m blobs (blob b: d_blobs[b].first onwards, in the order of its index list); d_u: m * 128 * 64 Fr
+// ([blob][cell][column]); non-canonical elements -> ERR_NONCANONICAL_FR in d_err[blob]
+void launch_rc_interp(const uint8_t *d_cells, const RecoverBlob *d_blobs, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_u,
+                      int *d_err, hipStream_t st);
+// d_coef (or null): m * 4096 Fr, the layout launch_cc_columns reads (zero for a refused blob); want_cells: d_u receives P_r(a_k) for all 128 cells
+void launch_rc_columns(Fr *d_u, const RecoverBlob *d_blobs, int m, const CellComputeConsts *d_cc, const RecoverTables *d_rt, Fr *d_coef,
+                       bool want_cells, hipStream_t st);
+// a refused blob's 128 output cells are left as they are
+void launch_rc_cells(const Fr *d_u, const RecoverBlob *d_blobs, int m, const CellComputeConsts *d_cc, uint8_t *d_cells /* m * 128 * 2048 */,
+                     hipStream_t st);
 
 }  // namespace kzg

@@ -619,6 +619,48 @@ class Kzg:
         return Kzg._recover(cell_indices, rows, s, True, True)
 
     @staticmethod
+    def _recover_sets(units, s, cells, proofs):
+        us = [([int(i) for i in ix], [_b(x, Cell) for x in row]) for ix, row in units]
+        m = len(us)
+        if any(len(ix) != len(row) for ix, row in us):
+            raise BadArgs("length mismatch")
+        if any(i < 0 or i >= 1 << 64 for ix, _ in us for i in ix):
+            raise BadArgs("cell index out of range")
+        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(m, 1)) if cells else None
+        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1)) if proofs else None
+        st = (C.c_int * max(m, 1))()
+        flat = [i for ix, _ in us for i in ix]
+        counts = (C.c_size_t * max(m, 1))(*[len(ix) for ix, _ in us])
+        idx = (C.c_size_t * max(len(flat), 1))(*flat)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_many_sets(c_out, p_out, st, counts, idx, b"".join(b"".join(row) for _, row in us), m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs_many_sets")
+        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
+        praw = p_out.raw if proofs else b""
+        res = []
+        for i in range(m):
+            if st[i] != 0:
+                res.append(_ERRORS.get(st[i], InternalError)("recover_cells"))
+                continue
+            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
+            pb = 48 * CELLS_PER_EXT_BLOB * i
+            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
+                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
+        return res
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_many_sets(units, s):
+        """units: a sequence of (cell_indices, cells), every blob with its own index set (blocks of a node that catches up hold different
+        columns); one independent recover_cells_and_kzg_proofs per unit in one call.  Returns a list of (cells, proofs) tuples or Error; a
+        unit whose two lengths differ raises BadArgs."""
+        return Kzg._recover_sets(units, s, True, True)
+
+    @staticmethod
+    def recover_cells_many_sets(units, s):
+        """The cells alone, per unit a list of 128 cells or Error (no proof is computed and no proof setup built)."""
+        return [r if isinstance(r, Error) else r[0] for r in Kzg._recover_sets(units, s, True, False)]
+
+    @staticmethod
     def debug_cell_compute_h(blobs, s):
         """FK20 intermediates per blob: H_0 .. H_63 compressed (H_63 is the point at infinity), or Error."""
         bl = [_b(x, Blob) for x in blobs]
@@ -734,4 +776,23 @@ class Kzg:
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many_device(c_out, p_out, st, idx, d_cells, n, m, s.handle)
         if _whole_call_failed(rc, st, m):
             _check(rc, "recover_cells_and_kzg_proofs_many_device")
+        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_many_sets_device(cell_counts, cell_indices, cells, s, cells_out=None, proofs_out=None):
+        """recover_cells_and_kzg_proofs_many_sets of resident blobs: blob i is known at cell_counts[i] cells, its indices following those of
+        blob i - 1 in cell_indices (both host sequences) and its cells those of blob i - 1 in cells (sum of the counts * 2048 bytes on the
+        device).  Outputs and return value as compute_cells_and_kzg_proofs_many_device."""
+        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
+        m = len(cn)
+        if any(c < 0 or c >= 1 << 64 for c in cn) or any(i < 0 or i >= 1 << 64 for i in ix) or sum(cn) != len(ix):
+            raise BadArgs("a count or a cell index out of range, or the counts do not add up to the indices")
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, m)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(ix), optional=m == 0)
+        st = (C.c_int * max(m, 1))()
+        counts = (C.c_size_t * max(m, 1))(*cn)
+        idx = (C.c_size_t * max(len(ix), 1))(*ix)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_many_sets_device(c_out, p_out, st, counts, idx, d_cells, m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs_many_sets_device")
         return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]

@@ -517,6 +517,44 @@ impl Kzg {
             .collect())
     }
 
+    /// One independent `recover_cells_and_kzg_proofs` per unit `(cell_indices, cells)` in one set of launches: every blob brings its own index
+    /// set (blocks of a node that catches up hold different columns).  One `Result` per unit; a unit whose two lengths differ is `BadArgs` for
+    /// the call.
+    pub fn recover_cells_and_kzg_proofs_many_sets(
+        units: &[(&[usize], &[Cell])],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let m = units.len();
+        if units.iter().any(|(ix, cells)| ix.len() != cells.len()) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let counts: Vec<usize> = units.iter().map(|(ix, _)| ix.len()).collect();
+        let indices: Vec<usize> = units.iter().flat_map(|(ix, _)| ix.iter().copied()).collect();
+        let input: Vec<u8> = units.iter().flat_map(|(_, cells)| cells.iter().flat_map(|x| x.iter().copied())).collect();
+        let per_cells = BYTES_PER_CELL * CELLS_PER_EXT_BLOB;
+        let mut out_cells = vec![0u8; per_cells * m.max(1)];
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * m.max(1)];
+        let mut st = vec![0i32; m.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_recover_cells_and_kzg_proofs_many_sets(out_cells.as_mut_ptr(), proofs.as_mut_ptr(), st.as_mut_ptr(), counts.as_ptr(),
+                                                               indices.as_ptr(), input.as_ptr(), m, s.raw)
+        };
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_many_sets")?;
+        Ok((0..m)
+            .map(|i| {
+                check(st[i], "recover_cells")?;
+                let cs = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| Cell::from_bytes(&out_cells[per_cells * i + BYTES_PER_CELL * k..per_cells * i + BYTES_PER_CELL * (k + 1)]))
+                    .collect::<Result<Vec<_>, _>>()?;
+                let base = BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * i;
+                let ps = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[base + 48 * k..base + 48 * (k + 1)]).unwrap()))
+                    .collect();
+                Ok((cs, ps))
+            })
+            .collect())
+    }
+
     /// `verify_cell_kzg_proof_batch_many` on device-resident data: the four pointers are DEVICE pointers on the handle's device (byte buffers
     /// 16-byte aligned, the indices 8-byte aligned), group-major, `n_per_group` cells per group; only the verdicts cross PCIe.
     ///
@@ -573,6 +611,30 @@ impl Kzg {
         let rc = ffi::kzg355_recover_cells_and_kzg_proofs_many_device(d_cells_out, d_proofs_out, st.as_mut_ptr(), cell_indices.as_ptr(), d_cells,
                                                                       cell_indices.len(), m, s.raw);
         whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_many_device")?;
+        Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
+    }
+
+    /// `recover_cells_and_kzg_proofs_many_sets` of resident blobs: blob `i` is known at `cell_counts[i]` cells, its indices (host memory) and its
+    /// cells (device memory) following those of blob `i - 1`; outputs as above.
+    ///
+    /// # Safety
+    /// `d_cells` holds `cell_indices.len()` cells on the handle's device; the outputs `cell_counts.len() * 128` cells / proofs; all 16-byte aligned.
+    pub unsafe fn recover_cells_and_kzg_proofs_many_sets_device(
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        cell_counts: &[usize],
+        cell_indices: &[usize],
+        d_cells: *const u8,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let m = cell_counts.len();
+        if cell_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c)) != Some(cell_indices.len()) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let mut st = vec![0i32; m.max(1)];
+        let rc = ffi::kzg355_recover_cells_and_kzg_proofs_many_sets_device(d_cells_out, d_proofs_out, st.as_mut_ptr(), cell_counts.as_ptr(),
+                                                                           cell_indices.as_ptr(), d_cells, m, s.raw);
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_many_sets_device")?;
         Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
     }
 
