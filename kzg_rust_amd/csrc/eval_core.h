@@ -14,6 +14,8 @@
 // wave that owns the blob), s a constant of the tree.  4095 nodes per blob: 2 x 4095 limb-product passes + 4095 reductions, against
 // 5 + 5 per four values (6825 of each per blob) in the radix-4 Horner form of rounds 3-5, and a third of its additions.
 // The leaves are the values themselves (plain integers), sum_i p_i rides along as a carry-swept sum per lane.
+// A node is 162 limb products + 72 q_i m_j (m_0 = 1 costs no product) = 234 multiply-adds either way; k_verify.hip takes the product by columns
+// (KZG_MONT_COLS_FR, field.h), which leaves 9 64-bit additions (the q_k) and 16 shifts beside them where the row form has 25 and 16.
 //
 // The device deals the tree in groups of three nodes: a group takes four neighbouring children (128 bytes of the blob at level 1) to
 // their grandparent, so six levels of groups -- 1024, 256, 64, 16, 4, 1 groups -- cover the twelve levels of nodes.  Level l uses

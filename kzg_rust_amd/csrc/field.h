@@ -275,6 +275,129 @@ template <int N> KZG_HD void mont_mulsqr2_lazy(uint32_t *r, const uint32_t *a, c
         cy >>= LB;
     }
 }
+// ---------------------------------------------------------------------------------- column (product-scanning) forms of the lazy products
+// The same products with the SAME quotient digits q_i and the same result limbs, bit for bit, taken column by column on ONE 64-bit
+// accumulator: column k = sum_{i+j=k} (limb products) + sum_i q_i m[k-i], started from the column below >> 29.  The carry is then the addend
+// of the column's first multiply-add (v_mad_u64_u32 has a 64-bit addend that the row forms feed a literal 0 once per column), and the
+// columns N .. 2N-1 ARE the result limbs: the row forms' N carry additions and their final sweep of N - 1 additions are gone, the limb
+// products and the q_i m_j products are the same in number.  A column holds what a row-form accumulator of the same weight collects before
+// it is shifted out -- at most N rounds of products -- plus a carry below 2^35, so every bound stated at the row forms holds unchanged.
+// The row forms stay the default: KZG_MONT_COLS_FR selects the Fr pair for a translation unit, the Fp pair fp_mul_lz<COLS> / fp_sqr_lz<COLS> is
+// selected by the point routine (below).
+//
+// PIN: left alone the compiler re-associates a column into (products summed from 0) + carry -- its reassociation adds the value computed last
+// at the end -- which puts the 64-bit addition back (and for N = 14 gives the row forms' code again).  With PIN the device build passes the
+// accumulator through __builtin_annotation after every multiply-add: the intrinsic returns its argument and generates no instruction, but the
+// optimiser does not look through it, so each sum keeps the shape it is written in and the accumulator stays the addend.  (An empty asm
+// statement pins as well, but the hazard recogniser then puts an s_nop before every multiply-add that reads the asm's result; an assumption
+// such as acc != 2^64 - 1 is dropped wherever the limbs' ranges are known, which is after every fp_sub_lz.)  The host build, and PIN = false,
+// are the plain expression.
+template <bool PIN> KZG_HD void col_mad(uint64_t &acc, const uint32_t x, const uint32_t y) {
+    acc += (uint64_t)x * y;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (PIN) acc = __builtin_annotation(acc, "col");
+#endif
+}
+// the reduction half of column k (shared by the four forms): the q_i m[k-i] of the quotient digits known so far, then for k < N the new digit
+// q_k (which clears the column's low 29 bits), for k >= N the result limb k - N.  Leaves the accumulator shifted for column k + 1.
+template <int N, bool PIN> KZG_HD void col_reduce(uint64_t &acc, uint32_t *q, uint32_t *r, const int k, const uint32_t *m, const uint32_t inv) {
+    if (k < N) {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i < k) col_mad<PIN>(acc, q[i], m[k - i]);
+        q[k] = ((uint32_t)acc * inv) & LMASK;
+        acc += (uint64_t)q[k] * m[0];
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i > k - N) col_mad<PIN>(acc, q[i], m[k - i]);
+        r[k - N] = (uint32_t)acc & LMASK;
+    }
+    acc >>= LB;
+}
+// mont_mul_lazy by columns: N^2 + N^2 limb products, no 64-bit additions beside the multiply-adds (and, where m[0] = 1, the q_k that complete a column).
+// Column k: at most N rounds of a_j b_i + q_i m_j below 2^58 each for normalised operands; for N = 9 one operand may be raw with limbs up to 2^31
+// (eval_core.h): 9 * 2^60 + 9 * 2^58 + carry < 2^64.
+template <int N, bool PIN = false> KZG_HD void mont_mul_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
+    static_assert(N <= 14, "a column: 2 N limb products of < 2^58 and a carry must stay below 2^64 (with headroom for the top limb's excess)");
+    uint32_t q[N], t[N];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i <= k && k - i < N) col_mad<PIN>(acc, a[k - i], b[i]);
+        col_reduce<N, PIN>(acc, q, t, k, m, inv);
+    }
+    t[N - 1] = (uint32_t)acc;                                      // column 2N - 1: the carry alone; the top limb keeps any excess
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = t[j];
+}
+// mont_mul2_lazy by columns.  Column k: at most N rounds of a_j b_i + c_j d_i + q_i m_j, each product < 2^58 for normalised operands (3 N 2^58 <
+// 2^63.4 at N = 14), or, for the evaluation tree's raw operands at N = 9 (eval_core.h: A limbs < 2^30, B limbs < 3 * 2^29 against normalised z^k, s),
+// 9 (2^59 + 3 * 2^58 + 2^58) = 27 * 2^59 < 2^63.8; the carry adds less than 2^35.
+template <int N, bool PIN = false> KZG_HD void mont_mul2_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                                                                   const uint32_t *m, const uint32_t inv) {
+    static_assert(N <= 14, "a column: 3 N limb products of < 2^58 and a carry must stay below 2^64");
+    uint32_t q[N], t[N];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i <= k && k - i < N) { col_mad<PIN>(acc, a[k - i], b[i]); col_mad<PIN>(acc, c[k - i], d[i]); }
+        col_reduce<N, PIN>(acc, q, t, k, m, inv);
+    }
+    t[N - 1] = (uint32_t)acc;
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = t[j];
+}
+// mont_sqr by columns: the N (N + 1) / 2 distinct limb products against the pre-doubled copy.  Column k: at most N / 2 cross products < 2^59, one
+// diagonal < 2^58 and N reduction products < 2^58: (2 (N / 2) + 1 + N) 2^58 + 2^35 < 2^64 up to N = 14.
+template <int N, bool LAZY = false, bool PIN = false> KZG_HD void mont_sqr_cols(uint32_t *r, const uint32_t *a, const uint32_t *m, const uint32_t inv) {
+    static_assert(2 * (N / 2) + 1 + N < 64, "a column: N/2 doubled cross, one diagonal and N reduction products must stay below 2^64");
+    uint32_t q[N], t[N], a2[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) a2[j] = a[j] << 1;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * N - 1; k++) {
+        if (!(k & 1)) col_mad<PIN>(acc, a[k / 2], a[k / 2]);       // the diagonal (k / 2, k / 2), then the pairs (i, k - i) with i < k - i < N
+#pragma unroll
+        for (int i = 0; i < N; i++) if (2 * i < k && k - i < N) col_mad<PIN>(acc, a2[i], a[k - i]);
+        col_reduce<N, PIN>(acc, q, t, k, m, inv);
+    }
+    t[N - 1] = (uint32_t)acc;                                      // (canonical form: t < 2m for an operand below m, the top limb needs no mask)
+    if (LAZY) {
+#pragma unroll
+        for (int j = 0; j < N; j++) r[j] = t[j];
+        return;
+    }
+    uint32_t s[N];
+    const uint32_t br = ul_sub<N>(s, t, m);
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = br ? t[j] : s[j];
+}
+// mont_mulsqr2_lazy by columns: r = (a b + 2 c^2) / R.  Column k holds exactly what column k of the row form's 2N accumulators holds:
+//     at most N full products a_j b_i < 2^58,  N/2 cross products (4 c_i) c_j < 2^60,  one diagonal (2 c_i) c_i < 2^59,  N reduction products < 2^58
+// and the carry of the column below < 2^35: (2N + 4 (N/2) + 2) 2^58 + 2^35 = 58 * 2^58 + 2^35 < 2^64 for N = 14 -- asserted below; not true of 15 limbs.
+template <int N, bool PIN = false> KZG_HD void mont_mulsqr2_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *m,
+                                                                      const uint32_t inv) {
+    static_assert(2 * N + 4 * (N / 2) + 2 < 64,
+                  "a column: N full, N/2 quadrupled cross, one doubled diagonal and N reduction products must stay below 2^64");
+    uint32_t q[N], t[N], c2[N], c4[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) { c2[j] = c[j] << 1; c4[j] = c[j] << 2; }
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = 0; i < N; i++) if (i <= k && k - i < N) col_mad<PIN>(acc, a[k - i], b[i]);
+        if (!(k & 1)) col_mad<PIN>(acc, c2[k / 2], c[k / 2]);
+#pragma unroll
+        for (int i = 0; i < N; i++) if (2 * i < k && k - i < N) col_mad<PIN>(acc, c4[i], c[k - i]);
+        col_reduce<N, PIN>(acc, q, t, k, m, inv);
+    }
+    t[N - 1] = (uint32_t)acc;
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = t[j];
+}
 // 32-bit word array (little-endian words, NW of them) -> N 29-bit limbs
 template <int N, int NW> KZG_HD void words_to_limbs(uint32_t *l, const uint32_t *w) {
 #pragma unroll
@@ -308,41 +431,12 @@ KZG_HD void fp_dbl(Fp &r, const Fp &a) { KZG_FP_CONSTS mod_add<NFP>(r.l, a.l, a.
 KZG_HD void fp_neg(Fp &r, const Fp &a) { Fp z = fp_zero(); fp_sub(r, z, a); }
 KZG_HD bool fp_is_zero(const Fp &a) { return ul_is_zero<NFP>(a.l); }
 KZG_HD bool fp_eq(const Fp &a, const Fp &b) { return ul_eq<NFP>(a.l, b.l); }
-#if defined(KZG_FP_MUL_CALL) && defined(__HIP_DEVICE_COMPILE__)
-// Throughput kernels: ONE out-of-line Fp product per kernel image, operands and result in VGPRs (two 16-lane vector
-// arguments = v0..v31, result v0..v15).  A fully inlined G1 formula is ~7k instructions (11 products): several of them
-// plus their callers overflow the 64 KB instruction cache that neighbouring CUs share, and with 8 waves per CU at
-// different program counters instruction fetch becomes the bottleneck.  With the call the hot loop is ~1.5k instructions.
-typedef uint32_t fp_vec __attribute__((ext_vector_type(16)));
-__device__ __attribute__((noinline)) inline fp_vec fp_mul_vec(fp_vec a, fp_vec b) {
-    KZG_FP_CONSTS
-    uint32_t x[NFP], y[NFP], r[NFP];
-#pragma unroll
-    for (int i = 0; i < NFP; i++) { x[i] = a[i]; y[i] = b[i]; }
-    mont_mul<NFP>(r, x, y, FP_MOD, FP_INVW);
-    fp_vec o;
-#pragma unroll
-    for (int i = 0; i < NFP; i++) o[i] = r[i];
-    o[14] = 0; o[15] = 0;
-    return o;
-}
-KZG_HD void fp_mul(Fp &r, const Fp &a, const Fp &b) {
-    fp_vec x, y;
-#pragma unroll
-    for (int i = 0; i < NFP; i++) { x[i] = a.l[i]; y[i] = b.l[i]; }
-    x[14] = 0; x[15] = 0; y[14] = 0; y[15] = 0;
-    const fp_vec o = fp_mul_vec(x, y);
-#pragma unroll
-    for (int i = 0; i < NFP; i++) r.l[i] = o[i];
-}
-#elif defined(KZG_FP_MUL_NOINLINE)
+#if defined(KZG_FP_MUL_NOINLINE)
 KZG_HD_NOINLINE void fp_mul(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
 #else
 KZG_HD void fp_mul(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
 #endif
-#if defined(KZG_FP_MUL_CALL) && defined(__HIP_DEVICE_COMPILE__)
-KZG_HD void fp_sqr(Fp &r, const Fp &a) { fp_mul(r, a, a); }
-#elif defined(KZG_FP_MUL_NOINLINE)
+#if defined(KZG_FP_MUL_NOINLINE)
 KZG_HD_NOINLINE void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, FP_MOD, FP_INVW); }
 #else
 KZG_HD void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, FP_MOD, FP_INVW); }
@@ -353,6 +447,18 @@ KZG_HD void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, F
 // MSM / bucket kernels (g1x_add_mixed_lazy), which spend ~15 % of a canonical addition in those subtractions and selects.
 KZG_HD void fp_mul_lz(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul_lazy<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
 KZG_HD void fp_sqr_lz(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP, true>(r.l, a.l, FP_MOD, FP_INVW); }
+// The same two with the form as a template flag, for the point routines that carry one (g1.h: g1x_add_mixed_lazy<COLS>): COLS takes the column forms,
+// same limbs out.  The kernels of one translation unit disagree about them (EXPERIMENTS.md, "Montgomery products by columns"): the bucket kernel of the
+// batch linear combination gains 2.5-3.9 %, the point validation and the tail of the linear combination spill more registers and lose, so there is no
+// unit-wide switch for Fp, and fp_mul2_lz / fp_mulsqr2_lz -- which only those kernels run -- stay in their row forms.
+template <bool COLS> KZG_HD void fp_mul_lz(Fp &r, const Fp &a, const Fp &b) {
+    KZG_FP_CONSTS
+    if (COLS) mont_mul_lazy_cols<NFP, true>(r.l, a.l, b.l, FP_MOD, FP_INVW); else mont_mul_lazy<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW);
+}
+template <bool COLS> KZG_HD void fp_sqr_lz(Fp &r, const Fp &a) {
+    KZG_FP_CONSTS
+    if (COLS) mont_sqr_cols<NFP, true, true>(r.l, a.l, FP_MOD, FP_INVW); else mont_sqr<NFP, true>(r.l, a.l, FP_MOD, FP_INVW);
+}
 // r = (a b + c d) / R, lazily, ONE Montgomery reduction for the two products (588 limb products instead of 784).  Operands normalised lazy values
 // with a b + c d < 2^12 p^2 (e.g. a < 6p, b < 10p, c < 4p, d < 2p in the point additions); result < p (1 + 2^-13).
 KZG_HD void fp_mul2_lz(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d) { KZG_FP_CONSTS mont_mul2_lazy<NFP>(r.l, a.l, b.l, c.l, d.l, FP_MOD,
@@ -511,10 +617,20 @@ KZG_HD void fr_mul(Fr &r, const Fr &a, const Fr &b) { KZG_FR_CONSTS mont_mul<NFR
 // (a squaring of its own like Fp's: 45 + 81 limb products instead of 162 -- the twelve z powers per blob of the challenge kernel, the r-power ladders)
 KZG_HD void fr_sqr(Fr &r, const Fr &a) { KZG_FR_CONSTS mont_sqr<NFR>(r.l, a.l, FR_MOD, FR_INVW); }
 // lazy product: operands < ~2.6 r, result < 1.1 r, not canonical (see mont_mul_lazy)
+// (a translation unit that defines KZG_MONT_COLS_FR before this header takes the two lazy Fr products in their column forms: same limbs out)
+#if defined(KZG_MONT_COLS_FR)
+KZG_HD void fr_mul_lazy(Fr &r, const Fr &a, const Fr &b) { KZG_FR_CONSTS mont_mul_lazy_cols<NFR, true>(r.l, a.l, b.l, FR_MOD, FR_INVW); }
+#else
 KZG_HD void fr_mul_lazy(Fr &r, const Fr &a, const Fr &b) { KZG_FR_CONSTS mont_mul_lazy<NFR>(r.l, a.l, b.l, FR_MOD, FR_INVW); }
+#endif
 // r = a*b + c*d with one reduction (lazy; result < 1.1 r for a*b + c*d < ~5 r^2)
+#if defined(KZG_MONT_COLS_FR)
+KZG_HD void fr_mul2_lazy(Fr &r, const Fr &a, const Fr &b, const Fr &c, const Fr &d) { KZG_FR_CONSTS mont_mul2_lazy_cols<NFR, true>(r.l, a.l, b.l, c.l, d.l,
+        FR_MOD, FR_INVW); }
+#else
 KZG_HD void fr_mul2_lazy(Fr &r, const Fr &a, const Fr &b, const Fr &c, const Fr &d) { KZG_FR_CONSTS mont_mul2_lazy<NFR>(r.l, a.l, b.l, c.l, d.l, FR_MOD,
         FR_INVW); }
+#endif
 // lazy sum: plain limb addition with carry normalisation, no reduction (value grows; keep chains short)
 KZG_HD void fr_add_lazy(Fr &r, const Fr &a, const Fr &b) {
     uint32_t c = 0;

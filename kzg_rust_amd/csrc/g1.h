@@ -169,7 +169,8 @@ KZG_HD void g1_lazy_y3(Fp &Y3, const Fp &R, const Fp &t, const Fp &S1, const Fp 
 //   X3 = R^2 + (2p - PPP) + 2 (2p - Q) in (0, 8p);  Y3 = R (Q + 8p - X3) + (2p - Y PPP) in (0, 4p);  ZZ3, ZZZ3 < 2p
 // `started` replaces the ZZ == 0 test (a lazy zero need not be all-zero limbs).  Anything unusual -- b at infinity, or P
 // possibly = 0 mod p (exact low-limb filter, one chance in 2^25 for a random P) -- goes through the canonical routine above.
-KZG_G1_MID void g1x_add_mixed_lazy(G1X &acc, bool &started, const G1Affine &b) {
+// COLS: the seven products and two squares in their column forms (field.h: same limbs); the bucket kernel of k_g1.hip asks for it.
+template <bool COLS = false> KZG_G1_MID void g1x_add_mixed_lazy(G1X &acc, bool &started, const G1Affine &b) {
     const uint32_t m2[NFP] = FP_MOD2_INIT, m4[NFP] = FP_MOD4_INIT, m8[NFP] = FP_MOD8_INIT;
     if (!started) {
         if (g1a_is_inf(b)) return;
@@ -177,8 +178,8 @@ KZG_G1_MID void g1x_add_mixed_lazy(G1X &acc, bool &started, const G1Affine &b) {
         return;
     }
     Fp U2, S2, P, R;
-    fp_mul_lz(U2, b.x, acc.zz);
-    fp_mul_lz(S2, b.y, acc.zzz);
+    fp_mul_lz<COLS>(U2, b.x, acc.zz);
+    fp_mul_lz<COLS>(S2, b.y, acc.zzz);
     fp_sub_lz(P, U2, acc.x, m8);
     fp_sub_lz(R, S2, acc.y, m4);
     if (fp_maybe_zero_lz(P) || g1a_is_inf(b)) {                  // rare: redo canonically (doubling / inverse / no-op)
@@ -189,9 +190,9 @@ KZG_G1_MID void g1x_add_mixed_lazy(G1X &acc, bool &started, const G1Affine &b) {
         return;
     }
     Fp PP, PPP, Q, t, u;
-    fp_sqr_lz(PP, P); fp_mul_lz(PPP, P, PP); fp_mul_lz(Q, acc.x, PP);
+    fp_sqr_lz<COLS>(PP, P); fp_mul_lz<COLS>(PPP, P, PP); fp_mul_lz<COLS>(Q, acc.x, PP);
     Fp X3, Y3;
-    fp_sqr_lz(X3, R);
+    fp_sqr_lz<COLS>(X3, R);
     fp_sub_lz(t, X3, PPP, m2);                                    // R^2 + 2p - PPP        in (0, 4p)
     fp_sub_lz(u, t, Q, m2);                                       //  ... + 2p - Q         in (0, 6p)
     fp_sub_lz(X3, u, Q, m2);                                      //  ... + 2p - Q         in (0, 8p)
@@ -203,12 +204,12 @@ KZG_G1_MID void g1x_add_mixed_lazy(G1X &acc, bool &started, const G1Affine &b) {
     { const Fp z = fp_zero(); fp_sub_lz(u, z, acc.y, m4); }       // 4p - Y                in (0, 4p]
     fp_mul2_lz(Y3, R, t, u, PPP);                                 // < 2p
 #else
-    fp_mul_lz(Y3, R, t);
-    fp_mul_lz(t, acc.y, PPP);
+    fp_mul_lz<COLS>(Y3, R, t);
+    fp_mul_lz<COLS>(t, acc.y, PPP);
     fp_sub_lz(Y3, Y3, t, m2);                                     // in (0, 4p)
 #endif
-    fp_mul_lz(acc.zz, acc.zz, PP);
-    fp_mul_lz(acc.zzz, acc.zzz, PPP);
+    fp_mul_lz<COLS>(acc.zz, acc.zz, PP);
+    fp_mul_lz<COLS>(acc.zzz, acc.zzz, PPP);
     acc.x = X3; acc.y = Y3;
 }
 // lazy accumulator -> canonical XYZZ (infinity if nothing was added)

@@ -12,6 +12,7 @@
 // The rhs is algebraically the reference's  sum r^i (C_i - [y_i]G) + sum r^i z_i proof_i  (kzg.rs:603-622): same
 // group element, so the same boolean.
 #define KZG_FP_MUL_NOINLINE 1
+#define KZG_MONT_COLS_FR 1      // k_eval: the lazy Fr products of eval_core.h by columns (field.h)
 #include "kernels.h"
 #include "sha256_rounds.h"
 #include "fr_block.h"
