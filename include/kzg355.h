@@ -338,8 +338,17 @@ int kzg355_debug_verify_sharded_intermediates(uint8_t *out /* groups*128, host *
  * commitment or proof that fails validate_kzg_g1 or a cell element >= r -> KZG355_BADARGS.  The challenge r hashes the domain
  * "RCKZGCBATCH__V1_", u64be(4096), u64be(64), u64be(#unique commitments), u64be(n), the unique commitments (first-appearance order), then per cell
  * u64be(commitment position), u64be(cell index), cell, proof -- on host threads; everything else runs on the device.  Mainnet handles only (a
- * handle of another FIELD_ELEMENTS_PER_BLOB -> KZG355_BADARGS); a handle over several devices runs these calls on its first device.  The first
- * cell call of a handle derives what the check needs from the setup (the 64 monomial points [tau^t]_1 and the lines of setup g2[64]). */
+ * handle of another FIELD_ELEMENTS_PER_BLOB -> KZG355_BADARGS).  The first cell call of a handle derives what the check needs from the setup
+ * (the 64 monomial points [tau^t]_1 and the lines of setup g2[64]).
+ *
+ * A handle over several devices runs the host-buffer cell calls (verify, compute, recover: every call of this section but the debug readbacks of
+ * the setup) on all of them, inside the library.  Independent units -- groups for verify, blobs for compute and recover -- go to the devices in
+ * contiguous ranges, each device running the single-device call on its range from its own host thread; a call uses as many devices as it has
+ * units.  A verify call with fewer groups than devices D and n_per_group >= 2 D cuts every group into D contiguous blocks of cells instead: the
+ * check is linear in the cells once r is known, so each device reduces its block to three G1 points per group, those go to one device per group
+ * (peer copies), and that device adds them and runs the pairing.  Results are byte for byte those of a single-device handle.  What refuses a call
+ * as a whole is decided once, before any device is used; per-unit statuses keep their positions and the return value stays the first non-OK
+ * status in unit order.  Every device builds its own cell setup on its first use.  The caller's current device is left as it was. */
 int kzg355_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments /* n*48 */, const size_t *cell_indices /* n */, const uint8_t *cells /* n*2048 */,
                                        const uint8_t *proofs /* n*48 */, size_t n, const kzg355_settings *s);
 /* `groups` independent calls of the above in one set of launches (one verdict per data-column sidecar): the four arrays group-major, n_per_group
@@ -354,8 +363,9 @@ int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *o
 int kzg355_debug_cell_setup_monomial(uint8_t *out /* 64*48 */, const kzg355_settings *s);
 /* compute_cells_and_kzg_proofs of the consensus specs: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their
  * 128 proofs (FK20), in cell order.  Either output may be NULL (then that half is not computed; without proofs_out no proof setup is built),
- * not both (KZG355_BADARGS).  A blob element >= r -> KZG355_BADARGS.  Mainnet handles only; a handle over several devices runs on its first
- * device.  The first call that wants proofs derives the 4096 monomial points [tau^t]_1 and a fixed-base table (384 MiB) from the setup. */
+ * not both (KZG355_BADARGS).  A blob element >= r -> KZG355_BADARGS.  Mainnet handles only; a handle over several devices spreads the blobs of a
+ * call over them (above; one blob is never cut).  The first call that wants proofs derives the 4096 monomial points [tau^t]_1 and a fixed-base
+ * table (384 MiB) from the setup, on every device that gets a blob. */
 int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL */, uint8_t *proofs_out /* 128*48 or NULL */, const uint8_t *blob,
                                         const kzg355_settings *s);
 /* n independent calls of the above (blobs n*131072 bytes): status[i] per blob; the return value is the first non-OK status.  n == 0 -> OK.  A
@@ -367,7 +377,7 @@ int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out /* n*128*2048 or
  * the blob.  n outside 64..128, an index >= 128, indices not strictly ascending (so: any duplicate) or a cell element >= r -> KZG355_BADARGS.
  * Either output may be NULL, with the meaning it has there; not both.  More than 64 cells that lie on no polynomial of degree < 4096 are no
  * error, as in the specs and in c-kzg-4844: the result is the cells and proofs of the 4096 coefficients the specs' algorithm keeps.  Mainnet
- * handles only; a handle over several devices runs on its first device. */
+ * handles only; a handle over several devices spreads the blobs of a call over them (above). */
 int kzg355_recover_cells_and_kzg_proofs(uint8_t *cells_out /* 128*2048 or NULL */, uint8_t *proofs_out /* 128*48 or NULL */,
                                         const size_t *cell_indices /* n */, const uint8_t *cells /* n*2048 */, size_t n, const kzg355_settings *s);
 /* m blobs known at the SAME n cell indices (a node holds the same columns of every blob of a block) in one set of launches: cells holds blob
@@ -386,7 +396,8 @@ int kzg355_recover_cells_and_kzg_proofs_many(uint8_t *cells_out /* m*128*2048 or
  * handle, both outputs NULL, NULL cell_counts, cell_indices or cells with m > 0, a handle of another FIELD_ELEMENTS_PER_BLOB, m > 2^32, a sum of
  * the counts that overflows size_t (or does so times 2048).  m == 0 -> OK, and nothing is touched.  More than 64 cells of a blob that lie on no
  * polynomial of degree < 4096 are no error: that blob's result is the single call's.  Blobs known at the same index set share its tables
- * wherever they sit in the call.  Mainnet handles only; a handle over several devices runs on its first device.  Large m runs in chunks. */
+ * wherever they sit in the call (on a handle over several devices: wherever they sit in a device's range of blobs, whose indices and cells start
+ * at the sum of the counts before it).  Mainnet handles only.  Large m runs in chunks. */
 int kzg355_recover_cells_and_kzg_proofs_many_sets(uint8_t *cells_out /* m*128*2048 or NULL */, uint8_t *proofs_out /* m*128*48 or NULL */,
                                                   int *status /* m or NULL */, const size_t *cell_counts /* m */,
                                                   const size_t *cell_indices /* sum of the counts */,
@@ -397,7 +408,7 @@ int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or 
 int kzg355_debug_cell_setup_monomial_all(uint8_t *out /* 4096*48 */, const kzg355_settings *s);
 /* ---- EIP-7594 cell calls on device-resident data -------------------------------------------------------------------------------------------
  * The three *_many cell calls with their bulk arguments in HBM: every d_* argument is a DEVICE pointer on the handle's device (its first device,
- * for a handle over several), ok / status are host pointers, and the calls are synchronous like the other *_device calls.  Layouts, NULL-output
+ * for a handle over several: these calls run on that device alone), ok / status are host pointers, and the calls are synchronous like the other *_device calls.  Layouts, NULL-output
  * meanings, per-unit status, "a refusal of the whole call marks every unit", the n == 0 / m == 0 / groups == 0 / n_per_group == 0 cases and every
  * KZG355_BADARGS rule are those of the host forms above.  Device byte buffers (commitments, cells, proofs, blobs, outputs) must be 16-byte
  * aligned and device cell indices 8-byte aligned (hipMalloc and torch allocations are); a misaligned pointer is KZG355_BADARGS.  Output buffers
@@ -432,6 +443,11 @@ int kzg355_debug_cell_batch_intermediates_device(uint8_t *out /* host, groups*17
                                                  size_t n_per_group, size_t groups, int prep_form, const kzg355_settings *s);
 /* How many device-resident cell verify calls on this handle were prepared on the device so far (the others took the host preparation). */
 long kzg355_settings_cell_device_prep_calls(const kzg355_settings *s);
+/* How the cell calls of a handle were spread: returns the number of devices the handle spans (1 for a plain handle) and fills out[d], d < min(cap,
+ * that number), with the cell launch sets device d has run so far -- a verify, compute or recover call (or its range of one) counts one on the
+ * device that ran it, a verify call cut into blocks one on every device.  A call refused as a whole counts nowhere.  A NULL handle, or a NULL out
+ * with cap > 0, is KZG355_BADARGS. */
+int kzg355_settings_cell_calls_per_device(const kzg355_settings *s, long *out /* cap */, size_t cap);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

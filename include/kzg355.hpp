@@ -107,6 +107,13 @@ public:
         if (rc) return from_status(rc, "load_trusted_setup");
         return KzgSettings(raw);
     }
+    // one count per device of the handle: the cell launch sets (verify, compute, recover) that device has run so far; empty without a handle
+    std::vector<long> cell_calls_per_device() const {
+        if (!h_) return {};
+        std::vector<long> out((size_t)kzg355_settings_cell_calls_per_device(h_.get(), nullptr, 0));
+        kzg355_settings_cell_calls_per_device(h_.get(), out.data(), out.size());
+        return out;
+    }
 };
 
 // pub struct Kzg (kzg.rs:983-1079)

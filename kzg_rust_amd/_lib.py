@@ -107,6 +107,7 @@ def load():
         "kzg355_recover_cells_and_kzg_proofs_many_device": [vp, vp, ip, szp, vp, sz, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many_sets_device": [vp, vp, ip, szp, szp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
+        "kzg355_settings_cell_calls_per_device": [vp, C.POINTER(C.c_long), sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -155,4 +156,5 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_cell_kzg_proof_batch_many_device", "kzg355_compute_cells_and_kzg_proofs_many_device",
     "kzg355_recover_cells_and_kzg_proofs_many_device", "kzg355_debug_cell_batch_intermediates_device", "kzg355_settings_cell_device_prep_calls",
     "kzg355_recover_cells_and_kzg_proofs_many_sets", "kzg355_recover_cells_and_kzg_proofs_many_sets_device",
+    "kzg355_settings_cell_calls_per_device",
 ]

@@ -148,6 +148,7 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
     int rc;
     if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
     if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
+    s->n_cell_sets.fetch_add(1);
     const size_t CH = units < CC_CHUNK ? units : CC_CHUNK;
     if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg, dev_out, dev_out && proofs_out))) return refuse(rc);
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
@@ -171,13 +172,19 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
     return first;
 }
 
-// device: blobs, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are
-static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
-                   bool device = false) {
-    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return cc_refuse(status, n, KZG355_BADARGS);
-    if (n == 0) return KZG355_OK;
-    if (!blobs) return cc_refuse(status, n, KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return cc_refuse(status, n, KZG355_BADARGS);
+// The host-buffer compute and recover calls on a handle over several devices (multi_device.hip): what cc_run would refuse for every range alike
+// is refused here, once; then contiguous ranges of the blobs go to as many replicas as there are blobs, fn(replica, first blob, count) on the
+// replica's own host thread (cc_run takes its workspace and scopes its device there).  A blob is never cut.
+int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn) {
+    if (units > ((size_t)1 << 32) || is_small(cs)) return cc_refuse(status, units, KZG355_BADARGS);
+    MultiDev *m = cs->multi;
+    const size_t D = m->rep.size();
+    return fan_out(units < D ? units : D, units, [&](size_t d, size_t u0, size_t n) { return fn(m->rep[d], u0, n); });
+}
+
+// n blobs on the device of cs (a replica, for a handle over several devices); the arguments are checked
+static int cc_single(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
+                     bool device) {
     return cc_run(cs, n, cells_out, proofs_out, h_dbg, status,
         [&](Workspace *w, size_t CH) { return device ? KZG355_OK : w->blobs.ensure((size_t)BLOB_BYTES * CH); },
         [&](Workspace *w, Timed &tm, size_t c0, int m, uint8_t *d_cells) -> int {
@@ -189,6 +196,22 @@ static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int 
             tm.end();
             return KZG355_OK;
         }, device);
+}
+
+// device: blobs, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are -- on
+// the first device of a handle over several, where they live
+static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
+                   bool device = false) {
+    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return cc_refuse(status, n, KZG355_BADARGS);
+    if (n == 0) return KZG355_OK;
+    if (!blobs) return cc_refuse(status, n, KZG355_BADARGS);
+    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return cc_refuse(status, n, KZG355_BADARGS);
+    if (cs->multi && !device)
+        return cc_fan_out(cs, n, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
+            return cc_single(cells_out ? cells_out + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * u0 : nullptr, proofs_out ? proofs_out + (size_t)48 * CC_FFT * u0 : nullptr,
+                             h_dbg ? h_dbg + (size_t)48 * CELL_FE * u0 : nullptr, status ? status + u0 : nullptr, blobs + (size_t)BLOB_BYTES * u0, k, rep, false);
+        });
+    return cc_single(cells_out, proofs_out, h_dbg, status, blobs, n, cs, device);
 }
 
 }  // namespace kzg355_impl

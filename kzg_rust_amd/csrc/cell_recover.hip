@@ -6,6 +6,8 @@
 
 namespace kzg355_impl {
 
+static const size_t RC_CELLS_OUT = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES, RC_PROOFS_OUT = (size_t)48 * CC_FFT;   // bytes of output per blob
+
 // The 128-bit mask of an index list (mask[0] bits 0..63, mask[1] bits 64..127); false unless it has 64..128 strictly ascending indices < 128.
 static bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n) {
     mask[0] = mask[1] = 0;
@@ -117,6 +119,11 @@ static int rc_shared(uint8_t *cells_out, uint8_t *proofs_out, int *status, const
     if (m == 0) return KZG355_OK;
     if (!cells) return refuse(KZG355_BADARGS);
     if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
+    if (cs->multi && !device)                                     // ranges of blobs over the replicas (cc_fan_out)
+        return cc_fan_out(cs, m, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
+            return rc_run(cells_out ? cells_out + RC_CELLS_OUT * u0 : nullptr, proofs_out ? proofs_out + RC_PROOFS_OUT * u0 : nullptr,
+                          status ? status + u0 : nullptr, nullptr, idx, n, cells + (size_t)CELL_BYTES * n * u0, k, rep, false);
+        });
     return rc_run(cells_out, proofs_out, status, nullptr, idx, n, cells, m, cs, device);
 }
 
@@ -132,6 +139,14 @@ static int rc_sets(uint8_t *cells_out, uint8_t *proofs_out, int *status, const s
     for (size_t i = 0; i < m; i++) {
         if (counts[i] > SIZE_MAX / CELL_BYTES - total) return refuse(KZG355_BADARGS);    // the sum, in bytes of cells, stays a size_t
         total += counts[i];
+    }
+    if (cs->multi && !device) {                                   // ranges of blobs over the replicas: a range's indices and cells start at the sum of the counts before it
+        std::vector<size_t> first(m + 1, 0);
+        for (size_t i = 0; i < m; i++) first[i + 1] = first[i] + counts[i];
+        return cc_fan_out(cs, m, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
+            return rc_run(cells_out ? cells_out + RC_CELLS_OUT * u0 : nullptr, proofs_out ? proofs_out + RC_PROOFS_OUT * u0 : nullptr,
+                          status ? status + u0 : nullptr, counts + u0, idx + first[u0], 0, cells + (size_t)CELL_BYTES * first[u0], k, rep, false);
+        });
     }
     return rc_run(cells_out, proofs_out, status, counts, idx, 0, cells, m, cs, device);
 }

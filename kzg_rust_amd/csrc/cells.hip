@@ -64,68 +64,100 @@ struct CellHostPrep {
     std::vector<CellHostGroup> hg;
     int S = 0;                               // segments of all groups
 };
-// the four arrays in host memory (the caller's, or a device-resident call's copied back) -> hp; one group per host-pool task
+// The preparation has two pieces.  One hashes: a group's transcript over all its cells, with the commitments deduplicated over the whole group.
+// The other deduplicates and column-sorts a RANGE of a group's cells, which is all the kernels need of it.  A whole group is the range of all
+// its cells and shares one dedup between the two; a group cut over several devices (cell_multi_sharded) is hashed once and its blocks are
+// ranges of their own.
+// the unique commitments among `count` in order of first appearance into uc (48 per slot, padded to `count` slots with the encoding of infinity),
+// every entry's slot into cidx; returns how many there are
+static int cell_dedup(const uint8_t *commitments, size_t count, uint8_t *uc, int *cidx) {
+    std::unordered_map<std::string_view, int> seen;
+    seen.reserve(count * 2);
+    int u = 0;
+    for (size_t k = 0; k < count; k++) {
+        const std::string_view key(reinterpret_cast<const char *>(commitments + 48 * k), 48);
+        auto it = seen.find(key);
+        int pos;
+        if (it == seen.end()) {
+            pos = u++;
+            memcpy(uc + 48 * pos, key.data(), 48);
+            seen.emplace(key, pos);                             // (the key views caller memory, which outlives the map)
+        } else {
+            pos = it->second;
+        }
+        cidx[k] = pos;
+    }
+    for (size_t i = u; i < count; i++) { memset(uc + 48 * i, 0, 48); uc[48 * i] = 0xc0; }      // infinity, weight 0
+    return u;
+}
+// the transcript digest of one group of npg cells whose u unique commitments are uc, entry k carrying commitment cidx[k]
+static void cell_transcript(const kzg355_settings *s, const uint8_t *uc, int u, const int *cidx, const size_t *cell_indices, const uint8_t *cells,
+                            const uint8_t *proofs, size_t npg, uint8_t *dig) {
+    const size_t len = 16 + 32 + 48 * (size_t)u + npg * (16 + CELL_BYTES + 48);
+    std::vector<uint8_t> msg(len);
+    uint8_t *p = msg.data();
+    memcpy(p, CELL_DOMAIN, 16); p += 16;
+    put_u64be(p, N_FE); put_u64be(p + 8, CELL_FE); put_u64be(p + 16, (uint64_t)u); put_u64be(p + 24, npg); p += 32;
+    memcpy(p, uc, 48 * (size_t)u); p += 48 * (size_t)u;
+    for (size_t k = 0; k < npg; k++) {
+        put_u64be(p, (uint64_t)cidx[k]); put_u64be(p + 8, cell_indices[k]); p += 16;
+        memcpy(p, cells + (size_t)CELL_BYTES * k, CELL_BYTES); p += CELL_BYTES;
+        memcpy(p, proofs + 48 * k, 48); p += 48;
+    }
+    kzg_host::sha256(dig, msg.data(), len, s->sha_impl);
+}
+// the digests alone, of `groups` whole groups of npg cells (32 bytes each into dig); one group per host-pool task
+static void cell_host_digests(kzg355_settings *s, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                              size_t npg, size_t groups, uint8_t *dig) {
+    auto one = [&](size_t gi) {
+        const size_t base = gi * npg;
+        std::vector<uint8_t> uc(48 * npg);
+        std::vector<int> cidx(npg);
+        const int u = cell_dedup(commitments + 48 * base, npg, uc.data(), cidx.data());
+        cell_transcript(s, uc.data(), u, cidx.data(), cell_indices + base, cells + (size_t)CELL_BYTES * base, proofs + 48 * base, npg, dig + 32 * gi);
+    };
+    if (s->host_pool && groups > 1) s->host_pool->parallel_for(groups, one);
+    else for (size_t gi = 0; gi < groups; gi++) one(gi);
+}
+// The four arrays in host memory (the caller's, or a device-resident call's copied back) -> hp; one group per host-pool task.  A launch set
+// takes cells [off, off + cnt) of every group of npg, numbered gi * cnt + k on the device.  The whole group (off 0, cnt npg) is hashed here from
+// the same dedup; a block of it leaves hp.dig alone (the group's digest covers all its cells: cell_host_digests).
 static void cell_host_prep(kzg355_settings *s, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t npg,
-                           size_t groups, CellHostPrep &hp) {
-    const int n = (int)npg, G = (int)groups;
-    const size_t N = npg * groups;
+                           size_t groups, CellHostPrep &hp, size_t off, size_t cnt) {
+    const bool whole = off == 0 && cnt == npg;
+    const int n = (int)cnt, G = (int)groups;
+    const size_t N = cnt * groups;
     const int seg_cap = n < CELLS_PER_EXT_BLOB ? n : CELLS_PER_EXT_BLOB;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> &h_uc = hp.uc, &h_dig = hp.dig;
-    h_uc.resize(48 * N); h_dig.resize(32 * groups);
+    h_uc.resize(48 * N);
+    if (whole) h_dig.resize(32 * groups);
     std::vector<int> h_cell(N), h_cidx(N), h_perm(N);
     std::vector<int4> h_seg_local((size_t)G * seg_cap);
     std::vector<CellHostGroup> &hg = hp.hg;
     hg.assign(groups, CellHostGroup());
     auto prep = [&](size_t gi) {
-        const size_t base = gi * npg;
+        const size_t base = gi * cnt, src = gi * npg + off;       // the range on the device and in the caller's arrays
         CellHostGroup &gr = hg[gi];
-        for (size_t k = 0; k < npg; k++) {
-            const size_t c = cell_indices[base + k];
+        for (size_t k = 0; k < cnt; k++) {
+            const size_t c = cell_indices[src + k];
             if (c >= (size_t)CELLS_PER_EXT_BLOB) gr.bad_index = true;
             h_cell[base + k] = c < (size_t)CELLS_PER_EXT_BLOB ? (int)c : 0;
         }
-        std::unordered_map<std::string_view, int> seen;
-        seen.reserve(npg * 2);
-        int u = 0;
         uint8_t *uc = h_uc.data() + 48 * base;
-        for (size_t k = 0; k < npg; k++) {
-            const std::string_view key(reinterpret_cast<const char *>(commitments + 48 * (base + k)), 48);
-            auto it = seen.find(key);
-            int pos;
-            if (it == seen.end()) {
-                pos = u++;
-                memcpy(uc + 48 * pos, key.data(), 48);
-                seen.emplace(key, pos);                             // (the key views caller memory, which outlives the map)
-            } else {
-                pos = it->second;
-            }
-            h_cidx[base + k] = pos;
-        }
-        for (int i = u; i < n; i++) { memset(uc + 48 * i, 0, 48); uc[48 * i] = 0xc0; }      // infinity, weight 0
+        const int u = cell_dedup(commitments + 48 * src, cnt, uc, h_cidx.data() + base);
         // counting sort by column
-        int cnt[CELLS_PER_EXT_BLOB] = {0}, at[CELLS_PER_EXT_BLOB];
-        for (size_t k = 0; k < npg; k++) cnt[h_cell[base + k]]++;
+        int ccnt[CELLS_PER_EXT_BLOB] = {0}, at[CELLS_PER_EXT_BLOB];
+        for (size_t k = 0; k < cnt; k++) ccnt[h_cell[base + k]]++;
         int acc = 0;
         for (int c = 0; c < CELLS_PER_EXT_BLOB; c++) {
             at[c] = acc;
-            if (cnt[c]) h_seg_local[gi * seg_cap + gr.n_segs++] = make_int4((int)gi, c, (int)base + acc, cnt[c]);
-            acc += cnt[c];
+            if (ccnt[c]) h_seg_local[gi * seg_cap + gr.n_segs++] = make_int4((int)gi, c, (int)base + acc, ccnt[c]);
+            acc += ccnt[c];
         }
-        for (size_t k = 0; k < npg; k++) h_perm[base + at[h_cell[base + k]]++] = (int)(base + k);
-        // transcript
-        const size_t len = 16 + 32 + 48 * (size_t)u + npg * (16 + CELL_BYTES + 48);
-        std::vector<uint8_t> msg(len);
-        uint8_t *p = msg.data();
-        memcpy(p, CELL_DOMAIN, 16); p += 16;
-        put_u64be(p, N_FE); put_u64be(p + 8, CELL_FE); put_u64be(p + 16, (uint64_t)u); put_u64be(p + 24, npg); p += 32;
-        memcpy(p, uc, 48 * (size_t)u); p += 48 * (size_t)u;
-        for (size_t k = 0; k < npg; k++) {
-            put_u64be(p, (uint64_t)h_cidx[base + k]); put_u64be(p + 8, cell_indices[base + k]); p += 16;
-            memcpy(p, cells + (size_t)CELL_BYTES * (base + k), CELL_BYTES); p += CELL_BYTES;
-            memcpy(p, proofs + 48 * (base + k), 48); p += 48;
-        }
-        kzg_host::sha256(h_dig.data() + 32 * gi, msg.data(), len, s->sha_impl);
+        for (size_t k = 0; k < cnt; k++) h_perm[base + at[h_cell[base + k]]++] = (int)(base + k);
+        if (whole)
+            cell_transcript(s, uc, u, h_cidx.data() + base, cell_indices + src, cells + (size_t)CELL_BYTES * src, proofs + 48 * src, npg, h_dig.data() + 32 * gi);
     };
     if (s->host_pool && groups > 1) s->host_pool->parallel_for(groups, prep);
     else for (size_t gi = 0; gi < groups; gi++) prep(gi);
@@ -166,30 +198,83 @@ static bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t n
     return bytes > CELL_PREP_HOST_FROM_BYTES && groups < (size_t)CELL_PREP_HOST_UPTO_GROUPS_PER_CU * (size_t)s->cu_count;
 }
 
+// What cell_single and a stage-1 block of cell_multi_sharded share: the buffers of a launch set, the upload of a host-prepared one and the chain.
+// The workspace's buffers by role: blobs = cells, commitments = unique commitments, q = meta, z = r powers, y = column coefficients, scal_a =
+// lincomb scalars, partials = lincomb terms, lc_partials = the three sums per group, out48 = r | debug output.  N = n * groups cells, S segments;
+// host_input: cells and proofs are uploaded (else read where the caller has them).
+static int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints) {
+    const size_t N = (size_t)n * groups, T = (size_t)cell_terms(n);
+    int rc;
+    if ((host_input && ((rc = w->blobs.ensure((size_t)CELL_BYTES * N)) || (rc = w->proofs.ensure(48 * N)))) || (rc = w->commitments.ensure(48 * N)) ||
+        (rc = w->pts.ensure(sizeof(G1Affine) * 2 * N)) || (rc = w->digests.ensure(32 * groups)) || (rc = w->q.ensure(sizeof(int) * meta_ints)) ||
+        (rc = w->z.ensure(sizeof(Fr) * N)) || (rc = w->y.ensure(sizeof(Fr) * CELL_FE * (size_t)(S > 0 ? S : 1))) ||
+        (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * T * groups)) || (rc = w->partials.ensure(sizeof(G1Jac) * T * groups)) ||
+        (rc = w->lc_partials.ensure(sizeof(G1Jac) * 3 * groups)) || (rc = w->pair_pts.ensure(sizeof(PairPt) * 2 * groups)) ||
+        (rc = w->ok.ensure(sizeof(int) * groups)) || (rc = w->err.ensure(sizeof(int) * groups)) || (rc = w->h_ok.ensure(sizeof(int) * groups)) ||
+        (rc = w->h_err.ensure(sizeof(int) * groups)) || (rc = w->out48.ensure((size_t)(32 + CELL_DEBUG_BYTES) * groups)) ||
+        (rc = w->h_out.ensure((size_t)CELL_DEBUG_BYTES * groups)))
+        return rc;
+    return KZG355_OK;
+}
+// hp and the digests up; with host arrays (cells, proofs not null) also cells [off, off + cnt) of every group of npg and their proofs, group after group
+static int cell_upload(Workspace *w, const CellHostPrep &hp, const uint8_t *dig, const uint8_t *cells, const uint8_t *proofs, size_t npg, size_t off,
+                       size_t cnt, size_t groups) {
+    hipStream_t st = w->stream;
+    HIPCHK(hipMemcpyAsync(w->commitments.p, hp.uc.data(), 48 * cnt * groups, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->q.p, hp.meta.data(), sizeof(int) * hp.meta.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(w->digests.p, dig, 32 * groups, hipMemcpyHostToDevice, st));
+    if (!cells) return KZG355_OK;
+    const size_t runs = cnt == npg ? 1 : groups, len = cnt == npg ? cnt * groups : cnt;       // whole groups lie back to back
+    for (size_t g = 0; g < runs; g++) {
+        const size_t src = g * npg + off, dst = g * cnt;
+        HIPCHK(hipMemcpyAsync(w->proofs.as<uint8_t>() + 48 * dst, proofs + 48 * src, 48 * len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + (size_t)CELL_BYTES * dst, cells + (size_t)CELL_BYTES * src, (size_t)CELL_BYTES * len, hipMemcpyHostToDevice,
+                              st));
+    }
+    return KZG355_OK;
+}
+// The chain on prepared buffers: points, scalars with weights r^(k0 + k), interpolation, then the three sums per group in lc_partials -- and, with
+// finish, the pairing arguments (d_dbg or null: the debug bytes).  A block of a cut group stops at the sums (k_cell_merge ends it elsewhere).
+static void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
+                       uint8_t *d_dbg) {
+    const size_t N = (size_t)n * G;
+    hipStream_t st = w->stream;
+    const int4 *d_segs = w->q.as<int4>();
+    const int *d_gseg = w->q.as<int>() + 4 * (size_t)S, *d_cell = d_gseg + G + 1, *d_cidx = d_cell + N, *d_perm = d_cidx + N;
+    uint8_t *d_r = w->out48.as<uint8_t>();
+    tm.begin("cell_points");
+    launch_decompress_points(w->commitments.as<uint8_t>(), d_proofs, (int)N, n, w->pts.as<G1Affine>(), w->err.as<int>(), st);
+    launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
+    tm.end();
+    tm.begin("cell_scalars");
+    launch_cell_scalars(w->digests.as<uint8_t>(), d_cell, d_cidx, n, G, k0, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(), w->scal_a.as<uint32_t>(), d_r, st);
+    tm.end();
+    tm.begin("cell_interp");
+    launch_cell_interp(d_cells, d_perm, d_segs, S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), n, G, w->y.as<Fr>(),
+                       w->scal_a.as<uint32_t>(), w->err.as<int>(), st);
+    tm.end();
+    tm.begin("cell_lincomb");
+    if (finish)
+        launch_cell_lincomb(w->pts.as<G1Affine>(), s->cell_mono.as<G1Affine>(), w->scal_a.as<uint32_t>(), n, G, w->partials.as<G1Jac>(),
+                            w->lc_partials.as<G1Jac>(), d_r, w->pair_pts.as<PairPt>(), d_dbg, st);
+    else
+        launch_cell_sums(w->pts.as<G1Affine>(), s->cell_mono.as<G1Affine>(), w->scal_a.as<uint32_t>(), n, G, w->partials.as<G1Jac>(), w->lc_partials.as<G1Jac>(), st);
+    tm.end();
+}
+
+// One set of launches for `groups` whole groups on the device of cs (a replica, for a handle over several devices); the arguments are checked.
 // device = false: the four arrays are host memory (the launch sequence of the host-buffer calls).  device = true: they are device memory on the
 // handle's device; prep_form 0 by size, 1 device preparation, 2 copy back and prepare on the host.
-static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
-                     size_t npg, size_t groups, const kzg355_settings *cs, bool device = false, int prep_form = 0) {
-    if (!cs || !ok) return KZG355_BADARGS;
-    if (groups == 0) return KZG355_OK;
+static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                       size_t npg, size_t groups, const kzg355_settings *cs, bool device, int prep_form) {
     auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
-    if (device && (prep_form < 0 || prep_form > 2)) return refuse(KZG355_BADARGS);
-    if (npg == 0) {                                               // verify_cell_kzg_proof_batch of no cells: true
-        for (size_t i = 0; i < groups; i++) { ok[i] = true; if (status) status[i] = KZG355_OK; }
-        if (dbg) memset(dbg, 0, (size_t)CELL_DEBUG_BYTES * groups);
-        return KZG355_OK;
-    }
-    if (!commitments || !cell_indices || !cells || !proofs) return refuse(KZG355_BADARGS);
-    if (device && (((uintptr_t)commitments & 15) || ((uintptr_t)cells & 15) || ((uintptr_t)proofs & 15) || ((uintptr_t)cell_indices & 7)))
-        return refuse(KZG355_BADARGS);
-    if (npg > CELL_MAX_CELLS || groups > CELL_MAX_CELLS || npg * groups > CELL_MAX_CELLS) return refuse(KZG355_BADARGS);
-    if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
     WsGuard g(cs);
     if (!g.w) return refuse(KZG355_NO_DEVICE);
     kzg355_settings *s = g.s; Workspace *w = g.w;
     int rc;
     if ((rc = ensure_cell_setup(s, w))) return refuse(rc);
-    const int n = (int)npg, G = (int)groups, T = cell_terms(n);
+    s->n_cell_sets.fetch_add(1);
+    const int n = (int)npg, G = (int)groups;
     const size_t N = npg * groups;
     const int seg_cap = n < CELLS_PER_EXT_BLOB ? n : CELLS_PER_EXT_BLOB;
     hipStream_t st = w->stream;
@@ -198,7 +283,7 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
     const bool dev_prep = device && !cell_device_call_prepares_on_host(s, npg, groups, prep_form);
     CellHostPrep hp;
     if (!device) {
-        cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp);
+        cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, 0, npg);
     } else if (!dev_prep) {
         // into the workspace's pinned staging buffer (kept from call to call): indices | commitments | proofs | cells
         if ((rc = w->h_stage.ensure((sizeof(size_t) + 48 + 48 + (size_t)CELL_BYTES) * N))) return refuse(rc);
@@ -209,7 +294,7 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
         HIPCHK(hipMemcpyAsync(b_p, proofs, 48 * N, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(b_cells, cells, (size_t)CELL_BYTES * N, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        cell_host_prep(s, b_c, b_idx, b_cells, b_p, npg, groups, hp);
+        cell_host_prep(s, b_c, b_idx, b_cells, b_p, npg, groups, hp, 0, npg);
     }
     // meta buffer of the device preparation: the host's layout with a fixed seg_cap segments per group, then the unique-commitment counts and
     // (tables too large for LDS) the dedup tables
@@ -218,31 +303,20 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
     const int S = dev_prep ? G * seg_cap : hp.S;
     const size_t meta_ints = dev_prep ? (size_t)4 * S + (G + 1) + 3 * N + groups + gtab_ints : hp.meta.size();
 
-    // ---- device.  (The workspace's buffers by role: blobs = cells, commitments = unique commitments, q = meta, z = r powers, y = column
-    // coefficients, scal_a = lincomb scalars, partials = lincomb terms, lc_partials = the three sums per group, out48 = r | debug output.)
-    if ((!device && ((rc = w->blobs.ensure((size_t)CELL_BYTES * N)) || (rc = w->proofs.ensure(48 * N)))) || (rc = w->commitments.ensure(48 * N)) ||
-        (rc = w->pts.ensure(sizeof(G1Affine) * 2 * N)) || (rc = w->digests.ensure(32 * groups)) || (rc = w->q.ensure(sizeof(int) * meta_ints)) ||
-        (rc = w->z.ensure(sizeof(Fr) * N)) || (rc = w->y.ensure(sizeof(Fr) * CELL_FE * (size_t)(S > 0 ? S : 1))) ||
-        (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * (size_t)T * groups)) || (rc = w->partials.ensure(sizeof(G1Jac) * (size_t)T * groups)) ||
-        (rc = w->lc_partials.ensure(sizeof(G1Jac) * 3 * groups)) || (rc = w->pair_pts.ensure(sizeof(PairPt) * 2 * groups)) ||
-        (rc = w->ok.ensure(sizeof(int) * groups)) || (rc = w->err.ensure(sizeof(int) * groups)) || (rc = w->h_ok.ensure(sizeof(int) * groups)) ||
-        (rc = w->h_err.ensure(sizeof(int) * groups)) || (rc = w->out48.ensure((size_t)(32 + CELL_DEBUG_BYTES) * groups)) ||
-        (rc = w->h_out.ensure((size_t)CELL_DEBUG_BYTES * groups)))
-        return refuse(rc);
+    // ---- device
+    if ((rc = cell_reserve(w, !device, n, groups, S, meta_ints))) return refuse(rc);
     Fp *f12 = nullptr;
     if (w->pair_f.ensure(pairing_f12_bytes(G)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
     w->in_flight = true;
     Timed tm(s, w);
-    const int4 *d_segs = w->q.as<int4>();
-    const int *d_gseg = w->q.as<int>() + 4 * (size_t)S, *d_cell = d_gseg + G + 1, *d_cidx = d_cell + N, *d_perm = d_cidx + N;
     const uint8_t *d_cells = device ? cells : w->blobs.as<uint8_t>(), *d_proofs = device ? proofs : w->proofs.as<uint8_t>();
-    uint8_t *d_r = w->out48.as<uint8_t>(), *d_dbg = dbg ? d_r + 32 * groups : nullptr;
+    uint8_t *d_dbg = dbg ? w->out48.as<uint8_t>() + 32 * groups : nullptr;
     HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * groups, st));
     if (dev_prep) {
         int *m = w->q.as<int>() + 4 * (size_t)S;
-        int *d_ucount = m + (G + 1) + 3 * N, *d_gtab = gtab_ints ? d_ucount + groups : nullptr;
+        int *d_cidx = m + (G + 1) + N, *d_ucount = m + (G + 1) + 3 * N, *d_gtab = gtab_ints ? d_ucount + groups : nullptr;
         tm.begin("cell_prep");
-        launch_cell_prep(commitments, cell_indices, n, G, tab_size, d_gtab, w->commitments.as<uint8_t>(), w->q.as<int4>(), m, m + (G + 1), m + (G + 1) + N,
+        launch_cell_prep(commitments, cell_indices, n, G, tab_size, d_gtab, w->commitments.as<uint8_t>(), w->q.as<int4>(), m, m + (G + 1), d_cidx,
                          m + (G + 1) + 2 * N, d_ucount, w->err.as<int>(), st);
         tm.end();
         tm.begin("cell_rhash");
@@ -250,28 +324,10 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
                           st);
         tm.end();
         s->n_cell_device_prep.fetch_add(1);
-    } else {
-        HIPCHK(hipMemcpyAsync(w->commitments.p, hp.uc.data(), 48 * N, hipMemcpyHostToDevice, st));
-        if (!device) HIPCHK(hipMemcpyAsync(w->proofs.p, proofs, 48 * N, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(w->q.p, hp.meta.data(), sizeof(int) * hp.meta.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(w->digests.p, hp.dig.data(), 32 * groups, hipMemcpyHostToDevice, st));
-        if (!device) HIPCHK(hipMemcpyAsync(w->blobs.p, cells, (size_t)CELL_BYTES * N, hipMemcpyHostToDevice, st));
+    } else if ((rc = cell_upload(w, hp, hp.dig.data(), device ? nullptr : cells, proofs, npg, 0, npg, groups))) {
+        return rc;
     }
-    tm.begin("cell_points");
-    launch_decompress_points(w->commitments.as<uint8_t>(), d_proofs, (int)N, n, w->pts.as<G1Affine>(), w->err.as<int>(), st);
-    launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
-    tm.end();
-    tm.begin("cell_scalars");
-    launch_cell_scalars(w->digests.as<uint8_t>(), d_cell, d_cidx, n, G, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(), w->scal_a.as<uint32_t>(), d_r, st);
-    tm.end();
-    tm.begin("cell_interp");
-    launch_cell_interp(d_cells, d_perm, d_segs, S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), n, G, w->y.as<Fr>(),
-                       w->scal_a.as<uint32_t>(), w->err.as<int>(), st);
-    tm.end();
-    tm.begin("cell_lincomb");
-    launch_cell_lincomb(w->pts.as<G1Affine>(), s->cell_mono.as<G1Affine>(), w->scal_a.as<uint32_t>(), n, G, w->partials.as<G1Jac>(), w->lc_partials.as<G1Jac>(),
-                        d_r, w->pair_pts.as<PairPt>(), d_dbg, st);
-    tm.end();
+    cell_chain(s, w, tm, d_cells, d_proofs, S, n, G, 0, true, d_dbg);
     tm.begin("cell_pairing");
     launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, G, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from, s->miller_segments);
     tm.end();
@@ -291,6 +347,172 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
         if (stt != KZG355_OK && first == KZG355_OK) first = stt;
     }
     return first;
+}
+
+// ---- a handle over several devices (multi_device.hip) ------------------------------------------------------------------------------------------
+// A group cut over the devices.  The check is linear in the cells once r is known: LL = sum r^k pi_k, RL = sum w_i C_i - [I(tau)]_1 +
+// sum r^k h_k^64 pi_k, and I is a sum over the cells of r^k times a linear map of the cell.  So device d takes cells [off_d, off_d + cnt_d) of every
+// group (off_d = n d / D, ragged allowed, cnt_d >= 1 by the rule of cell_multi), deduplicates and column-sorts its block on its own -- a
+// commitment in two blocks is weighted in both, a column in two blocks is a segment in each -- and runs the chain of cell_single with weights
+// r^(off_d + k) up to the three sums per group.  r comes from the group's transcript over ALL its cells, hashed once on the host.  The exchange is
+// those three points per (block, group), copied to the group's stage-2 device g mod D, where k_cell_merge adds them and the pairing runs.
+static int cell_multi_sharded(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
+                              const uint8_t *proofs, size_t npg, size_t groups, const kzg355_settings *cs) {
+    MultiDev *m = cs->multi;
+    const size_t D = m->rep.size();
+    const int G = (int)groups;
+    auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
+    DeviceScope keep; keep.hold();               // this thread visits every replica's device below
+    std::vector<size_t> cnt(D), off(D);
+    for (size_t d = 0; d < D; d++) { off[d] = npg * d / D; cnt[d] = npg * (d + 1) / D - off[d]; }
+    std::vector<std::unique_ptr<WsGuard>> gs;                    // (whatever device the last guard leaves current, `keep` puts the caller's back)
+    for (size_t d = 0; d < D; d++) {
+        gs.emplace_back(new WsGuard(m->rep[d]));
+        if (!gs[d]->w) return refuse(KZG355_NO_DEVICE);
+    }
+    std::vector<uint8_t> h_dig(32 * groups);
+    cell_host_digests(gs[0]->s, commitments, cell_indices, cells, proofs, npg, groups, h_dig.data());
+    auto join = [](std::vector<std::future<int>> &fut) {
+        int first = KZG355_OK;
+        for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
+        return first;
+    };
+    // stage 1: the block's three sums per group in lc_partials, r of every group in out48, its status per group in st1
+    std::vector<std::vector<int>> st1(D, std::vector<int>(groups, KZG355_OK));
+    {
+        std::vector<std::future<int>> fut;
+        for (size_t d = 0; d < D; d++) {
+            fut.push_back(std::async(std::launch::async, [&, d]() -> int {
+                kzg355_settings *s = gs[d]->s; Workspace *w = gs[d]->w;
+                if (hipSetDevice(s->device) != hipSuccess) return KZG355_NO_DEVICE;
+                int rc;
+                if ((rc = ensure_cell_setup(s, w))) return rc;
+                s->n_cell_sets.fetch_add(1);
+                CellHostPrep hp;
+                cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, off[d], cnt[d]);
+                if ((rc = cell_reserve(w, true, (int)cnt[d], groups, hp.S, hp.meta.size()))) return rc;
+                hipStream_t st = w->stream;
+                w->in_flight = true;
+                Timed tm(s, w);
+                HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * groups, st));
+                if ((rc = cell_upload(w, hp, h_dig.data(), cells, proofs, npg, off[d], cnt[d], groups))) return rc;
+                cell_chain(s, w, tm, w->blobs.as<uint8_t>(), w->proofs.as<uint8_t>(), hp.S, (int)cnt[d], G, (int)off[d], false, nullptr);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * groups, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                w->in_flight = false;
+                tm.collect();
+                for (size_t g = 0; g < groups; g++) st1[d][g] = hp.hg[g].bad_index ? KZG355_BADARGS : status_from_err(w->h_err.as<int>()[g]);
+                return KZG355_OK;
+            }));
+        }
+        const int rc = join(fut);
+        if (rc != KZG355_OK) return refuse(rc);
+    }
+    m->n_peer_exchanges++;
+    // stage 2: group g on device g mod D, over the sums of all blocks
+    {
+        std::vector<std::future<int>> fut;
+        for (size_t t = 0; t < D && t < groups; t++) {
+            fut.push_back(std::async(std::launch::async, [&, t]() -> int {
+                kzg355_settings *s = gs[t]->s; Workspace *w = gs[t]->w;
+                if (hipSetDevice(s->device) != hipSuccess) return KZG355_NO_DEVICE;
+                const size_t Gt = (groups - t + D - 1) / D;              // groups t, t + D, ...
+                int rc;
+                DevBuf &gath = w->records;                                 // [group of this device][block][3 sums]
+                if ((rc = gath.ensure(sizeof(G1Jac) * 3 * D * Gt))) return rc;       // (pair_pts, ok, out48 ...: cell_reserve sized them for all groups)
+                Fp *f12 = nullptr;
+                if (w->pair_f.ensure(pairing_f12_bytes((int)Gt)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
+                hipStream_t st = w->stream;
+                w->in_flight = true;
+                Timed tm(s, w);
+                for (size_t k = 0; k < Gt; k++)
+                    for (size_t d = 0; d < D; d++) {
+                        G1Jac *dst = gath.as<G1Jac>() + 3 * (k * D + d);
+                        const G1Jac *src = gs[d]->w->lc_partials.as<G1Jac>() + 3 * (t + k * D);
+                        if (gs[d]->s->device == s->device) HIPCHK(hipMemcpyAsync(dst, src, sizeof(G1Jac) * 3, hipMemcpyDeviceToDevice, st));
+                        else HIPCHK(hipMemcpyPeerAsync(dst, s->device, src, gs[d]->s->device, sizeof(G1Jac) * 3, st));
+                    }
+                uint8_t *d_r = w->out48.as<uint8_t>(), *d_dbg = dbg ? d_r + 32 * groups : nullptr;
+                tm.begin("cell_merge");
+                if (!launch_cell_merge(gath.as<G1Jac>(), (int)D, (int)Gt, d_r, (int)t, (int)D, w->pair_pts.as<PairPt>(), d_dbg, st)) return KZG355_INTERNAL;
+                tm.end();
+                tm.begin("cell_pairing");
+                launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, (int)Gt, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from,
+                               s->miller_segments);
+                tm.end();
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(w->h_ok.p, w->ok.p, sizeof(int) * Gt, hipMemcpyDeviceToHost, st));
+                if (dbg) HIPCHK(hipMemcpyAsync(w->h_out.p, d_dbg, (size_t)CELL_DEBUG_BYTES * Gt, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                w->in_flight = false;
+                tm.collect();
+                for (size_t k = 0; k < Gt; k++) {
+                    const size_t g = t + k * D;
+                    if (dbg) memcpy(dbg + (size_t)CELL_DEBUG_BYTES * g, w->h_out.as<uint8_t>() + (size_t)CELL_DEBUG_BYTES * k, CELL_DEBUG_BYTES);
+                    ok[g] = w->h_ok.as<int>()[k] != 0;
+                }
+                return KZG355_OK;
+            }));
+        }
+        const int rc = join(fut);
+        if (rc != KZG355_OK) return refuse(rc);
+    }
+    // an Err in any block is the group's Err: the first one in block order
+    int first = KZG355_OK;
+    for (size_t g = 0; g < groups; g++) {
+        int stt = KZG355_OK;
+        for (size_t d = 0; d < D && stt == KZG355_OK; d++) stt = st1[d][g];
+        if (status) status[g] = stt;
+        if (stt != KZG355_OK) ok[g] = false;
+        if (stt != KZG355_OK && first == KZG355_OK) first = stt;
+    }
+    return first;
+}
+
+// Cells per device from which a call with fewer groups than devices cuts its groups over the devices: the blob path's rule (multi_verify_many),
+// so that one rule describes the handle.  No measurement on several cards stands behind the figure.
+static const size_t CELL_SHARD_MIN_CELLS_PER_DEVICE = 2;
+static_assert(MAX_HANDLE_DEVICES <= (size_t)CELL_MERGE_MAX_BLOCKS, "k_cell_merge adds one block per lane of one wave");
+
+// The host-buffer calls on a handle over several devices: enough independent groups (or groups too small to cut) go to the replicas in
+// contiguous ranges, each on its replica's own host thread and workspace, with no exchange; fewer groups than devices are cut into blocks.
+static int cell_multi(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                      size_t npg, size_t groups, const kzg355_settings *cs) {
+    MultiDev *m = cs->multi;
+    const size_t D = m->rep.size();
+    const bool force_sharded = cs->force_sharded && npg >= D;         // (test hook: kzg355_options.force_sharded)
+    if (!force_sharded && (groups >= D || npg < CELL_SHARD_MIN_CELLS_PER_DEVICE * D)) {
+        // as many replicas as there are groups; each range's WsGuard scopes its device on the range's own thread
+        return fan_out(groups < D ? groups : D, groups, [&](size_t d, size_t g0, size_t n) -> int {
+            const size_t c0 = g0 * npg;
+            return cell_single(ok + g0, status ? status + g0 : nullptr, dbg ? dbg + (size_t)CELL_DEBUG_BYTES * g0 : nullptr, commitments + 48 * c0,
+                               cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, npg, n, m->rep[d], false, 0);
+        });
+    }
+    return cell_multi_sharded(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs);
+}
+
+// What is decided once for the whole call, whatever runs it afterwards
+static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                     size_t npg, size_t groups, const kzg355_settings *cs, bool device = false, int prep_form = 0) {
+    if (!cs || !ok) return KZG355_BADARGS;
+    if (groups == 0) return KZG355_OK;
+    auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
+    if (device && (prep_form < 0 || prep_form > 2)) return refuse(KZG355_BADARGS);
+    if (npg == 0) {                                               // verify_cell_kzg_proof_batch of no cells: true
+        for (size_t i = 0; i < groups; i++) { ok[i] = true; if (status) status[i] = KZG355_OK; }
+        if (dbg) memset(dbg, 0, (size_t)CELL_DEBUG_BYTES * groups);
+        return KZG355_OK;
+    }
+    if (!commitments || !cell_indices || !cells || !proofs) return refuse(KZG355_BADARGS);
+    if (device && (((uintptr_t)commitments & 15) || ((uintptr_t)cells & 15) || ((uintptr_t)proofs & 15) || ((uintptr_t)cell_indices & 7)))
+        return refuse(KZG355_BADARGS);
+    if (npg > CELL_MAX_CELLS || groups > CELL_MAX_CELLS || npg * groups > CELL_MAX_CELLS) return refuse(KZG355_BADARGS);
+    if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
+    // device-resident arrays live on the handle's first device and stay there
+    if (cs->multi && !device) return cell_multi(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs);
+    return cell_single(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs, device, prep_form);
 }
 
 }  // namespace kzg355_impl
@@ -331,6 +553,13 @@ int kzg355_debug_cell_batch_intermediates_device(uint8_t *out, bool *ok, int *st
 }
 
 long kzg355_settings_cell_device_prep_calls(const kzg355_settings *s) { return s ? s->n_cell_device_prep.load() : 0L; }
+
+int kzg355_settings_cell_calls_per_device(const kzg355_settings *s, long *out, size_t cap) {
+    if (!s || (!out && cap > 0)) return KZG355_BADARGS;
+    const std::vector<kzg355_settings *> rep = replicas_of(const_cast<kzg355_settings *>(s));
+    for (size_t d = 0; d < rep.size() && d < cap; d++) out[d] = rep[d]->n_cell_sets.load();
+    return (int)rep.size();
+}
 
 int kzg355_debug_cell_setup_monomial(uint8_t *out, const kzg355_settings *cs) {
     if (!cs || !out) return KZG355_BADARGS;

@@ -231,6 +231,9 @@ struct kzg355_settings {
     DeviceTables cell_t{};
     DevBuf cell_consts, cell_mono, cell_mono48, cell_lines, cell_lines_w, cell_lines_inf;
     std::atomic<long> n_cell_device_prep{0};   // introspection: device-resident cell verify calls prepared by the kernels of k_cell_prep.hip
+    // ... and the cell launch sets this handle (a replica of a multi-device handle: this device) has run: verify, compute and recover calls, and the
+    // stage-1 blocks of a verify call cut over the devices (kzg355_settings_cell_calls_per_device)
+    std::atomic<long> n_cell_sets{0};
     // compute_cells_and_kzg_proofs (cell_compute.hip): the field-stage constants, then -- first call that wants proofs -- the 4096 monomial points
     // and the FK20 comb table (CC_TABLE_ENTRIES affine points), each built once under cc_mu.  A failed proof setup releases its buffers like the
     // one above, but is remembered in cc_proof_rc unless it was NO_MEMORY (a later call may find the memory).  The two setups came with different
@@ -298,6 +301,7 @@ struct Timed {
     }
 };
 
+static const size_t MAX_HANDLE_DEVICES = 64;     // replicas of one handle (load_devices); k_cell_merge adds one block per lane of one wave
 inline bool is_small(const kzg355_settings *s) { return s->t.n_fe != N_FE; }
 inline size_t blob_bytes_of(const kzg355_settings *s) { return (size_t)32 * s->t.n_fe; }
 
@@ -401,6 +405,7 @@ int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs);
 static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
 int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
 int cc_refuse(int *status, size_t units, int code);
+int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
            const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells)> &stage, bool dev_out = false);

@@ -10,7 +10,13 @@
 // Launch order of one call (cells.hip): decode + subgroup (k_g1.hip) | k_cell_rpowers -> k_cell_weights, k_cell_columns -> k_cell_interp ->
 // k_cell_terms -> k_cell_sum -> k_cell_finish -> launch_pairing with the [tau^64]_2 line set.  The lincomb is one double-and-add scalar
 // multiplication per term (255-bit scalars) and a tree per group and side: the 4844 lincomb families have their scalar layout baked in.
-#define KZG_FP_MUL_NOINLINE 1
+//
+// A group cut over the devices of a multi-device handle (cells.hip: cell_multi_sharded): the check is linear in the cells once r is known, so a
+// contiguous block of cells [k0, k0 + cnt) runs the same chain with weights r^(k0 + k) and stops after k_cell_sum; k_cell_merge adds the
+// blocks' three sums on the group's stage-2 device and ends as k_cell_finish does.
+// The G1 routines and the field products are inlined here (the out-of-line forms of g1.h / field.h take their operands by address, which puts
+// every point a kernel holds into private memory): no kernel of this file uses scratch.
+#define KZG_MID_INLINE 1
 #include "kernels.h"
 #include "cell_domain.h"
 
@@ -61,9 +67,10 @@ __global__ void __launch_bounds__(64) k_cell_lines(const uint8_t *g2_bytes, Line
 }
 
 // ---- per call
-// thread (g, k): r of group g from its digest, r^k, and the two proof scalars: r^k (LL) and r^k h_k^64 (RL)
-__global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, const int *cell_idx, int npg, int groups, const CellConsts *cc, Fr *rpow,
-                                                      uint32_t *scal, uint8_t *r_out) {
+// thread (g, k): r of group g from its digest, r^(k0 + k), and the two proof scalars: r^(k0 + k) (LL) and r^(k0 + k) h_k^64 (RL).  k0: the
+// position in its group of the first cell handed to this launch (0 unless the group is cut into blocks)
+__global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, const int *cell_idx, int npg, int groups, int k0, const CellConsts *cc,
+                                                      Fr *rpow, uint32_t *scal, uint8_t *r_out) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= npg * groups) return;
     const int g = gid / npg, k = gid % npg;
@@ -71,7 +78,7 @@ __global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, co
     uint32_t w[8]; be32_to_words(w, digests + 32 * (size_t)g);
     Fr r; fr_from_words(r, w);                                    // int(digest) mod r_BLS
     if (k == 0) fr_to_be32(r_out + 32 * (size_t)g, r);
-    const Fr p = fr_pow_small(r, (uint32_t)k);
+    const Fr p = fr_pow_small(r, (uint32_t)k0 + (uint32_t)k);
     rpow[gid] = p;
     Fr q; fr_mul(q, p, cc->h64[cell_idx[gid]]);
     fr_store_words(scal + 8 * ((size_t)g * T + npg + k), q);
@@ -155,24 +162,52 @@ __global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum(const G1Jac *part
     }
     if (tid == 0) sums[3 * (size_t)g + side] = red[0];
 }
-// thread g: the pairing arguments (-LL, RL) and, with dbg, r | [I(tau)]_1 | LL | RL compressed (CELL_DEBUG_BYTES per group)
+// The end of a group's check from its three sums a (commitments + RL proofs), b (= -[I(tau)]_1) and ll: the pairing arguments (-LL, RL) and, with
+// o, r | [I(tau)]_1 | LL | RL compressed (CELL_DEBUG_BYTES)
+__device__ __forceinline__ void cell_finish_group(const G1Jac &a, const G1Jac &b, const G1Jac &ll, const uint8_t *r_be, PairPt *pp, uint8_t *o) {
+    G1Jac rl; g1_add(rl, a, b);
+    pairpt_from_jac(pp[0], ll, true);
+    pairpt_from_jac(pp[1], rl, false);
+    if (!o) return;
+    for (int i = 0; i < 32; i++) o[i] = r_be[i];
+    G1Jac itau; g1_neg(itau, b);
+#pragma unroll 1
+    for (int q = 0; q < 3; q++) {
+        const G1Jac p = q == 0 ? itau : q == 1 ? ll : rl;        // by value: a table of addresses would put the three points into private memory
+        G1Affine af; g1_to_affine(af, p);
+        g1_compress_affine(o + 32 + 48 * q, af);
+    }
+}
+// thread g: the end of group g's check from sums[3 g ..]
 __global__ void __launch_bounds__(64) k_cell_finish(const G1Jac *sums, int groups, const uint8_t *r_be, PairPt *pair_pts, uint8_t *dbg) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= groups) return;
-    const G1Jac a = sums[3 * (size_t)g], b = sums[3 * (size_t)g + 1], ll = sums[3 * (size_t)g + 2];
-    G1Jac rl; g1_add(rl, a, b);
-    pairpt_from_jac(pair_pts[2 * (size_t)g], ll, true);
-    pairpt_from_jac(pair_pts[2 * (size_t)g + 1], rl, false);
-    if (!dbg) return;
-    uint8_t *o = dbg + (size_t)CELL_DEBUG_BYTES * g;
-    for (int i = 0; i < 32; i++) o[i] = r_be[32 * (size_t)g + i];
-    G1Jac itau; g1_neg(itau, b);
-    const G1Jac *pts[3] = {&itau, &ll, &rl};
-    for (int q = 0; q < 3; q++) {
-        G1Affine p; g1_to_affine(p, *pts[q]);
-        uint8_t c[48]; g1_compress_affine(c, p);
-        for (int i = 0; i < 48; i++) o[32 + 48 * q + i] = c[i];
+    cell_finish_group(sums[3 * (size_t)g], sums[3 * (size_t)g + 1], sums[3 * (size_t)g + 2], r_be + 32 * (size_t)g, pair_pts + 2 * (size_t)g,
+                      dbg ? dbg + (size_t)CELL_DEBUG_BYTES * g : nullptr);
+}
+// One wave per group j of a stage-2 device: parts is [j][block][side], the three sums of every block of the group's cells.  Per side lane d
+// takes block d's sum and a tree over the wave adds them; lane 0 then ends the check as k_cell_finish does.  r of group j is at
+// r_be + 32 (r_first + j r_stride): every device derived the r of every group in stage 1.
+__global__ void __launch_bounds__(CELL_MERGE_MAX_BLOCKS) k_cell_merge(const G1Jac *parts, int blocks, int groups, const uint8_t *r_be, int r_first,
+                                                                      int r_stride, PairPt *pair_pts, uint8_t *dbg) {
+    __shared__ G1Jac red[CELL_MERGE_MAX_BLOCKS], sum[3];
+    const int j = blockIdx.x, d = threadIdx.x;
+    if (j >= groups) return;
+    int top = 1;                                                  // the tree starts at the power of two at or above `blocks`
+    while (top < blocks) top <<= 1;
+    for (int side = 0; side < 3; side++) {
+        red[d] = d < blocks ? parts[((size_t)j * blocks + d) * 3 + side] : g1_inf();
+        __syncthreads();
+        for (int s = top / 2; s > 0; s >>= 1) {
+            if (d < s) { G1Jac a = red[d], b = red[d + s]; g1_add(a, a, b); red[d] = a; }
+            __syncthreads();
+        }
+        if (d == 0) sum[side] = red[0];
+        __syncthreads();
     }
+    if (d != 0) return;
+    cell_finish_group(sum[0], sum[1], sum[2], r_be + 32 * ((size_t)r_first + (size_t)j * r_stride), pair_pts + 2 * (size_t)j,
+                      dbg ? dbg + (size_t)CELL_DEBUG_BYTES * j : nullptr);
 }
 
 // ---- launchers
@@ -180,11 +215,11 @@ void launch_cell_setup(const uint8_t *d_g2_tau64, CellConsts *d_cc, LineCoeff *d
     hipLaunchKernelGGL(k_cell_consts, dim3(1), dim3(CELLS_PER_EXT_BLOB), 0, st, d_cc);
     hipLaunchKernelGGL(k_cell_lines, dim3(1), dim3(64), 0, st, d_g2_tau64, d_lines, d_lines_inf, d_err);
 }
-void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,
-                         uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st) {
+void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, int k0, const CellConsts *d_cc,
+                         Fr *d_rpow, uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st) {
     const int n = npg * groups;
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_cell_rpowers, dim3((n + 255) / 256), dim3(256), 0, st, d_digests, d_cell_idx, npg, groups, d_cc, d_rpow, d_scal, d_r_be);
+    hipLaunchKernelGGL(k_cell_rpowers, dim3((n + 255) / 256), dim3(256), 0, st, d_digests, d_cell_idx, npg, groups, k0, d_cc, d_rpow, d_scal, d_r_be);
     hipLaunchKernelGGL(k_cell_weights, dim3((n + 255) / 256), dim3(256), 0, st, d_cidx, d_rpow, npg, groups, d_scal);
 }
 void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg, const Fr *d_rpow, const CellConsts *d_cc,
@@ -193,13 +228,25 @@ void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d
     if (n_segs > 0) hipLaunchKernelGGL(k_cell_columns, dim3(n_segs), dim3(CELL_FE), 0, st, d_cells, d_perm, d_segs, d_rpow, d_cc, d_coef, d_err);
     hipLaunchKernelGGL(k_cell_interp, dim3(groups), dim3(CELL_FE), 0, st, d_coef, d_gseg, npg, d_scal);
 }
-void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
-                         const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st) {
+void launch_cell_sums(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
+                      hipStream_t st) {
     if (groups <= 0) return;
     const size_t terms = (size_t)cell_terms(npg) * groups;
     hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 63) / 64)), dim3(64), 0, st, d_pts, d_mono, d_scal, npg, groups, d_partials);
     hipLaunchKernelGGL(k_cell_sum, dim3(groups, 3), dim3(CELL_SUM_THREADS), 0, st, d_partials, npg, d_sums);
+}
+void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
+                         const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st) {
+    if (groups <= 0) return;
+    launch_cell_sums(d_pts, d_mono, d_scal, npg, groups, d_partials, d_sums, st);
     hipLaunchKernelGGL(k_cell_finish, dim3((groups + 63) / 64), dim3(64), 0, st, d_sums, groups, d_r_be, d_pair_pts, d_dbg);
+}
+bool launch_cell_merge(const G1Jac *d_parts, int blocks, int groups, const uint8_t *d_r_be, int r_first, int r_stride, PairPt *d_pair_pts, uint8_t *d_dbg,
+                       hipStream_t st) {
+    if (blocks <= 0 || blocks > CELL_MERGE_MAX_BLOCKS) return false;
+    if (groups > 0)
+        hipLaunchKernelGGL(k_cell_merge, dim3(groups), dim3(CELL_MERGE_MAX_BLOCKS), 0, st, d_parts, blocks, groups, d_r_be, r_first, r_stride, d_pair_pts, d_dbg);
+    return true;
 }
 
 }  // namespace kzg

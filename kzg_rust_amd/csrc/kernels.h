@@ -189,10 +189,10 @@ struct CellConsts {
 };
 // once per handle: the constants and the Miller-loop lines of setup g2[64] into slot 2 of d_lines / d_lines_inf (bad g2 bytes: ERR_SETUP_POINT in d_err)
 void launch_cell_setup(const uint8_t *d_g2_tau64, CellConsts *d_cc, LineCoeff *d_lines, int *d_lines_inf, int *d_err, hipStream_t st);
-// r per group (from the host digests), r^k (d_rpow: npg * groups), the proof scalars and the unique-commitment weights into d_scal
-// ([group][cell_terms(npg)][8 words]); d_r_be: 32 bytes of r per group
-void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, const CellConsts *d_cc, Fr *d_rpow,
-                         uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st);
+// r per group (from the host digests), r^(k0 + k) (d_rpow: npg * groups), the proof scalars and the unique-commitment weights into d_scal
+// ([group][cell_terms(npg)][8 words]); d_r_be: 32 bytes of r per group.  k0: where in its group the first of the npg cells sits (0 for whole groups)
+void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, int npg, int groups, int k0, const CellConsts *d_cc,
+                         Fr *d_rpow, uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st);
 // column sums, inverse DFT and shift per (group, column) segment (d_segs: group, column, first entry of d_perm, count), then I per group into d_scal;
 // d_coef: n_segs * 64 Fr; non-canonical cell elements set ERR_NONCANONICAL_FR in their group's d_err
 void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg /* groups + 1 */, const Fr *d_rpow,
@@ -201,6 +201,15 @@ void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d
 // per group
 void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
                          const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st);
+// a group cut into blocks of cells over several devices: the first half of launch_cell_lincomb on one block of every group (its three sums per
+// group into d_sums), and the second half over the sums of all blocks on the group's stage-2 device.  d_parts: [group][block][3] G1Jac,
+// blocks <= CELL_MERGE_MAX_BLOCKS; r of group j at d_r_be + 32 (r_first + j r_stride); d_pair_pts, d_dbg as above
+void launch_cell_sums(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
+                      hipStream_t st);
+// false (nothing launched): more blocks than the one wave of k_cell_merge adds
+constexpr int CELL_MERGE_MAX_BLOCKS = 64;
+bool launch_cell_merge(const G1Jac *d_parts, int blocks, int groups, const uint8_t *d_r_be, int r_first, int r_stride, PairPt *d_pair_pts, uint8_t *d_dbg,
+                       hipStream_t st);
 // ---- k_cell_prep.hip: what the host prepares per group of a cell batch, from inputs that are in HBM already (the *_device entry points)
 constexpr int CELL_PREP_LDS_SLOTS = 8192;      // slots of the dedup table k_cell_prep keeps in LDS; a larger table lives in d_gtab
 constexpr int CELL_PREP_MAX_CELLS = 16384;     // cells per group up to which the device prepares (128 blobs x 128 cells: a block as one batch)

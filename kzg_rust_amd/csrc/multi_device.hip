@@ -14,13 +14,16 @@ namespace kzg355_impl {
 //     of blobs, one per device: stage 1 per block -> ONE all-gather of the 160-byte records (RCCL ncclAllGather
 //     over xGMI on a persistent communicator set, or peer copies when RCCL is unavailable / the blocks are ragged) -> stage 2
 //     for each batch on one device.
+// The EIP-7594 cell calls follow the same two rules from their own translation units (cells.hip: cell_multi, cell_multi_sharded; cell_compute.hip:
+// cc_fan_out, also behind cell_recover.hip): ranges of groups or blobs through fan_out below, and a cell batch of fewer groups than devices cut
+// into blocks of cells whose exchange is three G1 points per block and group, by peer copy.
 // RCCL is bound at run time (dlopen of the librccl the process already has, or /opt/rocm's), so the library carries no link
 // dependency on it and single-device users never load it.
 std::vector<kzg355_settings *> replicas_of(kzg355_settings *s) { return s->multi ? s->multi->rep : std::vector<kzg355_settings *>{s}; }
 
 static int load_devices(const uint8_t *g1_bytes, size_t n1, const uint8_t *g2_bytes, size_t n2, const int *devices, size_t n_devices, const kzg355_options &opt,
                         kzg355_settings **out) {
-    if (!out || !devices || n_devices == 0 || n_devices > 64) return KZG355_BADARGS;
+    if (!out || !devices || n_devices == 0 || n_devices > MAX_HANDLE_DEVICES) return KZG355_BADARGS;
     DeviceScope keep; keep.hold();               // the peer-access loop and the communicator set-up visit every device: the caller's current device comes back
     std::vector<kzg355_settings *> rep;
     auto fail = [&](int code) { for (auto *r : rep) free_single(r); return code; };

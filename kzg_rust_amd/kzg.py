@@ -265,6 +265,15 @@ class KzgSettings:
         """Device-resident cell verify calls on this handle that were prepared on the device so far."""
         return lib().kzg355_settings_cell_device_prep_calls(self.handle)
 
+    def cell_calls_per_device(self):
+        """One count per device of the handle: the cell launch sets (verify, compute, recover; a block of a verify call cut over the devices
+        counts too) that device has run so far."""
+        n = self.device_count
+        out = (C.c_long * n)()
+        if lib().kzg355_settings_cell_calls_per_device(self.handle, out, n) != n:
+            raise BadArgs("cell_calls_per_device")
+        return list(out)
+
     @property
     def host_threads(self):
         """host threads that hash for one call on this handle (its workers + the calling thread)"""

@@ -132,6 +132,7 @@ extern "C" {
     pub fn kzg355_settings_set_host_hash(s: *mut kzg355_settings, mode: c_int, max_blobs: c_int) -> c_int;
     pub fn kzg355_settings_host_hashed_calls(s: *const kzg355_settings) -> c_long;
     pub fn kzg355_settings_cell_device_prep_calls(s: *const kzg355_settings) -> c_long;
+    pub fn kzg355_settings_cell_calls_per_device(s: *const kzg355_settings, out: *mut c_long, cap: usize) -> c_int;
     pub fn kzg355_settings_host_threads(s: *const kzg355_settings) -> c_int;
     pub fn kzg355_version() -> *const c_char;
 }

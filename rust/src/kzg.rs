@@ -107,6 +107,14 @@ impl KzgSettings {
         unsafe { ffi::kzg355_settings_field_elements_per_blob(self.raw) as usize }
     }
 
+    /// Extension: one count per device of the handle, the EIP-7594 cell launch sets (verify, compute, recover) that device has run so far.
+    pub fn cell_calls_per_device(&self) -> Vec<i64> {
+        let n = unsafe { ffi::kzg355_settings_cell_calls_per_device(self.raw, std::ptr::null_mut(), 0) };
+        let mut out = vec![0 as std::os::raw::c_long; if n > 0 { n as usize } else { 0 }];
+        unsafe { ffi::kzg355_settings_cell_calls_per_device(self.raw, out.as_mut_ptr(), out.len()) };
+        out.into_iter().map(|v| v as i64).collect()
+    }
+
     pub fn load_trusted_setup_file<P: AsRef<Path>>(trusted_setup_file: P) -> Result<Self, Error> {
         let p = trusted_setup_file.as_ref().to_str().ok_or_else(|| Error::InvalidTrustedSetup("path is not UTF-8".into()))?;
         let c = CString::new(p).map_err(|_| Error::InvalidTrustedSetup("path contains NUL".into()))?;
