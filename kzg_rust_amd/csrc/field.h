@@ -2,10 +2,13 @@
 //
 // Why 29-bit limbs: measured on MI355X (profiles/r01_valu_issue_rates.txt) v_mad_u64_u32 issues at
 // the same rate as any other VALU op, so the cost of a field product is its instruction COUNT.
-// With limbs < 2^29 every column sum of a Montgomery product (<= 28 terms < 2^58 each) fits a 64-bit
+// With limbs < 2^29 every column sum of a Montgomery product (<= 28 terms < 2^58 each; up to 58 such units where two products or a product and a
+// doubled square share one reduction: mont_units() below counts them and every body asserts the count) fits a 64-bit
 // accumulator, so each limb product is exactly ONE v_mad_u64_u32 with no carry handling: an Fp product
 // is 2*14*14 = 392 mads + ~100 shift/mask ops, versus ~1350 instructions for saturated 32-bit limbs
 // (288 mads + carry/zero-extension traffic).  Fp: 14 limbs (R = 2^406), Fr: 9 limbs (R = 2^261).
+// All products are three bodies (mont_mul, mont_sqr, mont_cols) under one overflow bound; the lazy forms and the column forms are wrappers of
+// those (the Montgomery section below).
 //
 // Every value is kept CANONICAL (limbs < 2^29, value < modulus) so equality is limb equality.
 // Reference counterpart: the blst_fp / blst_fr types behind src/utils.rs, src/kzg.rs;
@@ -92,18 +95,70 @@ template <int N> KZG_HD void mod_sub(uint32_t *r, const uint32_t *a, const uint3
         r[i] = t & LMASK;
     }
 }
-// Montgomery product r = a*b/2^(29N) mod m.  a, b: limbs < 2^29, a*b < m*2^(29N).  inv = -m^-1 mod 2^29.
-// Column accumulators: acc[j] collects a[j']*b[i] and q_i*m[j'] for the current weight; after each outer
-// step the (now zero mod 2^29) lowest column is shifted out.  No carries until the final sweep.
-template <int N> KZG_HD void mont_mul(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
+// ---------------------------------------------------------------------------------- Montgomery products
+// r = (a b + c d + 2^SH e^2) / 2^(29N) mod m (whichever of the three terms a routine takes), inv = -m^-1 mod 2^29, reduced word by word: every limb
+// product and every q_i m[j] is ONE multiply-add into the 64-bit accumulator of its weight, and carries move only when a weight is finished.  Three
+// bodies take the same products in three orders; for the same operands they compute the same quotient digits q_i and the same result limbs, bit
+// for bit (tests/test_mont_columns_host.py).
+//   mont_mul   N accumulators, operand scanning: round i adds a[j] b[i] (TWO: and c[j] d[i]) and q_i m[j] to acc[j], then shifts the lowest
+//              accumulator (now zero mod 2^29) out.  No carries until the final sweep.  TWO: two products share one reduction, 3 N^2 multiply-adds
+//              instead of 4 N^2.  Wrappers: mont_mul_lazy, mont_mul2_lazy.
+//   mont_sqr   2N accumulators, all limb products first, then the reduction: 2^SH a^2 + (AB ? x y : 0).  The square is taken by its N (N + 1) / 2
+//              distinct limb products, a << SH on the diagonal and a << (SH + 1) off it (Fp: 105 + 196 multiply-adds for a square against 392; 497 for
+//              x y + 2 a^2 against 693 apart).  The factor 2^SH sits in shifted copies of the limbs (32-bit words: SH <= 2), and the bound below
+//              allows SH = 1 at N = 14; the doubling chain, which needs 8 B^2, passes a = 2B normalised, so that the rest of the factor sits in the
+//              VALUE and not in every limb product.  Wrapper: mont_mulsqr2_lazy.
+//   mont_cols  ONE accumulator, product scanning: column k = sum_{i+j=k} (limb products) + sum_i q_i m[k-i], started from the column below >> 29.
+//              The carry is then the addend of the column's first multiply-add (v_mad_u64_u32 has a 64-bit addend, which the row forms feed a
+//              literal 0 once per column), and the columns N .. 2N-1 ARE the result limbs: the row forms' N carry additions and their final sweep
+//              of N - 1 additions are gone, the multiply-adds are the same in number.  FULL in {0, 1, 2} full products (a b, c d) per column; SH >= 0
+//              adds 2^SH e^2 by half products, SH = -1 no square.  Wrappers: mont_mul_lazy_cols, mont_mul2_lazy_cols, mont_sqr_cols,
+//              mont_mulsqr2_lazy_cols.  The row forms stay the default: KZG_MONT_COLS_FR selects the lazy Fr pair by columns for a translation
+//              unit, fp_mul_lz<COLS> / fp_sqr_lz<COLS> are selected by the point routine (below).
+// LAZY leaves out the final conditional subtraction and keeps the top limb unmasked: the result is < m (1 + value / (m 2^(29N))) with every limb below
+// the top one normalised (< 2^29), which is all a following product or a bounded number of additions needs; the last operation of a chain is canonical.
+// Saves ~45 of ~316 (Fr) instructions per product on the throughput kernels.
+//
+// Why the canonical names ARE the two row bodies, and why each body spells out its own sweep and tail: every level of forwarding, above or below,
+// gives the optimiser one more round over the body while m is still a pointer, and the conditional subtraction then comes out of the compiler in
+// another shape once m is the constant modulus (its top limb's borrow as x + (2^29 - m) and x < m, or as one x - m < 0): a few instructions in every
+// kernel with a canonical product, registers and spills with them (EXPERIMENTS.md, "Montgomery bodies folded").  The lazy forms do not care.
+//
+// The overflow bound, once, for all three.  An accumulator of one weight k collects, in units of 2^58 (one product of two limbs below 2^29):
+//     FULL N           limb products x[j] y[i], i + j = k, of the FULL full products,
+//     N                reduction products q_i m[k-i],
+//     2^(SH+1) (N/2)   cross products (2^(SH+1) e_i) e_j of the square -- the pairs i < j with i + j = k, N / 2 of them and not N --
+//     2^SH             and its one diagonal (2^SH e_i) e_i,
+// and, when its turn comes, the carry of the weight below, < 2^35.  mont_units() is that count and every body asserts mont_units() < 64: at most
+// 63 * 2^58 + 2^35 < 2^64.  The largest in use is a b + 2 c^2 at N = 14: 2 * 14 + 4 * 7 + 2 = 58.  (That count was once noted as "not true of 15
+// limbs"; it is 60 at N = 15 and first fails, with 66, at N = 16.)  The unit assumes every limb below 2^29; the top limb of a lazy value is smaller still
+// (Fp: < 2^10 for a value below 2^6 p), and fp_sub_lz / fp_add_lz / fr_add_lazy / the lazy products leave every other limb normalised.  RAW operands
+// (limbs not normalised) are inside the bound only where counted by hand, which is for N = 9 (eval_core.h), in either order of the products:
+//     one product, one operand raw with limbs up to 2^31 against a normalised one:  9 * 2^60 + 9 * 2^58 + carry < 2^64;
+//     two products, A with limbs < 2^30 and B with limbs < 3 * 2^29 against normalised z^k, s:  9 (2^59 + 3 * 2^58 + 2^58) = 27 * 2^59 < 2^63.8.
+//
+// Operand contracts (value bounds; "lazy" = every limb below the top one < 2^29).  r may be any of the operands.
+//     mont_mul                                    a, b limbs < 2^29, a b < m 2^(29N)                     r canonical (t < m + a b / R, one subtraction)
+//     mont_sqr, mont_sqr_cols                     a canonical (LAZY: lazy, as mont_mul_lazy)             r canonical (LAZY: as mont_mul_lazy)
+//     mont_mul_lazy, mont_mul_lazy_cols           lazy; N = 9: a, b < ~2.6 m, one may be raw (above);    r < 1.1 m
+//                                                 N = 14: a, b < 2^6 m                                   r < m (1 + 2^-13)
+//     mont_mul2_lazy, mont_mul2_lazy_cols         lazy; N = 9: a b + c d < ~5 m^2, a, c may be raw       r < 1.1 m
+//                                                 (above); N = 14: a b + c d < 2^12 m^2                  r < m (1 + 2^-13)
+//     mont_mulsqr2_lazy, mont_mulsqr2_lazy_cols   lazy, a b + 2 c^2 < 2^12 m^2                           r < m (1 + 2^-13)
+constexpr int mont_units(int N, int FULL, int SH) { return (FULL + 1) * N + (SH < 0 ? 0 : (2 << SH) * (N / 2) + (1 << SH)); }
+
+// (callers write mont_mul<N>(r, a, b, m, inv); TWO, LAZY and the trailing c, d are for the wrappers mont_mul_lazy / mont_mul2_lazy alone)
+template <int N, bool TWO = false, bool LAZY = false> KZG_HD void mont_mul(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv,
+                                                                           const uint32_t *c = nullptr, const uint32_t *d = nullptr) {
+    static_assert(mont_units(N, TWO ? 2 : 1, -1) < 64, "an accumulator's limb and reduction products and a carry must stay below 2^64");
     uint64_t acc[N];
 #pragma unroll
     for (int j = 0; j < N; j++) acc[j] = 0;
 #pragma unroll
     for (int i = 0; i < N; i++) {
-        const uint32_t bi = b[i];
+        const uint32_t bi = b[i], di = TWO ? d[i] : 0u;
 #pragma unroll
-        for (int j = 0; j < N; j++) acc[j] += (uint64_t)a[j] * bi;
+        for (int j = 0; j < N; j++) { acc[j] += (uint64_t)a[j] * bi; if (TWO) acc[j] += (uint64_t)c[j] * di; }
         const uint32_t q = ((uint32_t)acc[0] * inv) & LMASK;
 #pragma unroll
         for (int j = 0; j < N; j++) acc[j] += (uint64_t)q * m[j];
@@ -114,33 +169,40 @@ template <int N> KZG_HD void mont_mul(uint32_t *r, const uint32_t *a, const uint
         acc[0] += carry;
     }
     uint32_t t[N];
-    uint64_t c = 0;
+    uint32_t *o = LAZY ? r : t;                                    // (every operand has been read by now)
+    uint64_t cy = 0;
 #pragma unroll
     for (int j = 0; j < N; j++) {
-        c += acc[j];
-        t[j] = (uint32_t)c & LMASK;
-        c >>= LB;
+        cy += acc[j];
+        o[j] = (LAZY && j == N - 1) ? (uint32_t)cy : ((uint32_t)cy & LMASK);     // LAZY: the top limb keeps any excess
+        cy >>= LB;
     }
-    // t < m + a*b/R; one conditional subtraction makes it canonical
+    if (LAZY) return;
     uint32_t s[N];
     const uint32_t br = ul_sub<N>(s, t, m);
 #pragma unroll
     for (int j = 0; j < N; j++) r[j] = br ? t[j] : s[j];
 }
-// Montgomery square: the N(N+1)/2 distinct limb products (cross terms against a pre-doubled copy) go to 2N column
-// accumulators, then the same word-by-word reduction.  N(N+1)/2 + N^2 limb products instead of 2 N^2 (Fp: 301 vs 392).
-// Columns stay below 2^64: at most N products of < 2^59 plus N of < 2^58 each, N <= 14.
-template <int N, bool LAZY = false> KZG_HD void mont_sqr(uint32_t *r, const uint32_t *a, const uint32_t *m, const uint32_t inv) {
-    static_assert(N <= 14, "column accumulators sized for at most 14 limbs");
+// (callers write mont_sqr<N, LAZY>(r, a, m, inv); AB, SH and the trailing x, y are for the wrapper mont_mulsqr2_lazy alone, whose (a, b, c) arrive
+// here as (x, y, a): the squared operand is a in this body)
+template <int N, bool LAZY = false, bool AB = false, int SH = 0> KZG_HD void mont_sqr(uint32_t *r, const uint32_t *a, const uint32_t *m, const uint32_t inv,
+                                                                                     const uint32_t *x = nullptr, const uint32_t *y = nullptr) {
+    static_assert(SH >= 0 && LB + SH + 1 <= 32 && mont_units(N, AB ? 1 : 0, SH) < 64,
+                  "an accumulator's limb and reduction products and a carry must stay below 2^64");
     uint64_t acc[2 * N];
-    uint32_t a2[N];
+    uint32_t a1[N], a2[N];
 #pragma unroll
-    for (int j = 0; j < N; j++) a2[j] = a[j] << 1;
+    for (int j = 0; j < N; j++) { a1[j] = a[j] << SH; a2[j] = a[j] << (SH + 1); }
 #pragma unroll
     for (int k = 0; k < 2 * N; k++) acc[k] = 0;
 #pragma unroll
     for (int i = 0; i < N; i++) {
-        acc[2 * i] += (uint64_t)a[i] * a[i];
+        if (AB) {
+            const uint32_t yi = y[i];
+#pragma unroll
+            for (int j = 0; j < N; j++) acc[i + j] += (uint64_t)x[j] * yi;
+        }
+        acc[2 * i] += (uint64_t)a1[i] * a[i];
 #pragma unroll
         for (int j = i + 1; j < N; j++) acc[i + j] += (uint64_t)a2[i] * a[j];
     }
@@ -152,139 +214,20 @@ template <int N, bool LAZY = false> KZG_HD void mont_sqr(uint32_t *r, const uint
         acc[i + 1] += acc[i] >> LB;
     }
     uint32_t t[N];
-    uint64_t c = 0;
+    uint32_t *o = LAZY ? r : t;
+    uint64_t cy = 0;
 #pragma unroll
     for (int j = 0; j < N; j++) {
-        c += acc[N + j];
-        t[j] = (LAZY && j == N - 1) ? (uint32_t)c : ((uint32_t)c & LMASK);
-        c >>= LB;
+        cy += acc[N + j];
+        o[j] = (LAZY && j == N - 1) ? (uint32_t)cy : ((uint32_t)cy & LMASK);
+        cy >>= LB;
     }
-    if (LAZY) {
-#pragma unroll
-        for (int j = 0; j < N; j++) r[j] = t[j];
-        return;
-    }
+    if (LAZY) return;
     uint32_t s[N];
     const uint32_t br = ul_sub<N>(s, t, m);
 #pragma unroll
     for (int j = 0; j < N; j++) r[j] = br ? t[j] : s[j];
 }
-// Same product WITHOUT the final conditional subtraction: result < m (1 + a*b / (m 2^(29N))), limbs normalised.
-// For operands below ~2.6 m the result stays below 1.1 m, which is all a following product (or a bounded number of
-// additions) needs; the last operation of a chain uses mont_mul, which canonicalises.  Saves ~45 of ~316 (Fr)
-// instructions per product on throughput kernels.
-template <int N> KZG_HD void mont_mul_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
-    uint64_t acc[N];
-#pragma unroll
-    for (int j = 0; j < N; j++) acc[j] = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const uint32_t bi = b[i];
-#pragma unroll
-        for (int j = 0; j < N; j++) acc[j] += (uint64_t)a[j] * bi;
-        const uint32_t q = ((uint32_t)acc[0] * inv) & LMASK;
-#pragma unroll
-        for (int j = 0; j < N; j++) acc[j] += (uint64_t)q * m[j];
-        const uint64_t carry = acc[0] >> LB;
-#pragma unroll
-        for (int j = 0; j < N - 1; j++) acc[j] = acc[j + 1];
-        acc[N - 1] = 0;
-        acc[0] += carry;
-    }
-    uint64_t c = 0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        c += acc[j];
-        r[j] = j < N - 1 ? ((uint32_t)c & LMASK) : (uint32_t)c;     // the top limb keeps any excess
-        c >>= LB;
-    }
-}
-// r = (a*b + c*d) / R, lazily: two products share one Montgomery reduction (2N^2 + N^2 limb products instead of 4N^2).
-// Operands as for mont_mul_lazy with (a*b + c*d) < ~5 m^2 (N = 9) / < 2^6 m * 2^6 m in all (N = 14).  Column sums: an accumulator collects at most
-// N rounds of three limb products (a_j b_i, c_j d_i, q m_j), each below 2^58 for limbs below 2^29 (the top limb of a lazy value is smaller still),
-// plus carries below 2^36: 3 * 14 * 2^58 < 2^63.4 -- inside 64 bits up to N = 14 PROVIDED every limb below the top one is normalised (< 2^29),
-// which is what fp_sub_lz / fp_add_lz / the lazy products leave.
-template <int N> KZG_HD void mont_mul2_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
-                                            const uint32_t *m, const uint32_t inv) {
-    static_assert(N <= 14, "column accumulators: 3 N limb products of < 2^58 must stay below 2^64");
-    uint64_t acc[N];
-#pragma unroll
-    for (int j = 0; j < N; j++) acc[j] = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const uint32_t bi = b[i], di = d[i];
-#pragma unroll
-        for (int j = 0; j < N; j++) { acc[j] += (uint64_t)a[j] * bi; acc[j] += (uint64_t)c[j] * di; }
-        const uint32_t q = ((uint32_t)acc[0] * inv) & LMASK;
-#pragma unroll
-        for (int j = 0; j < N; j++) acc[j] += (uint64_t)q * m[j];
-        const uint64_t carry = acc[0] >> LB;
-#pragma unroll
-        for (int j = 0; j < N - 1; j++) acc[j] = acc[j + 1];
-        acc[N - 1] = 0;
-        acc[0] += carry;
-    }
-    uint64_t cy = 0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        cy += acc[j];
-        r[j] = j < N - 1 ? ((uint32_t)cy & LMASK) : (uint32_t)cy;
-        cy >>= LB;
-    }
-}
-// r = (a*b + 2 c^2) / R, lazily: a product and a (doubled) square share one Montgomery reduction -- N^2 + N(N+1)/2 + N^2 limb products
-// (Fp: 196 + 105 + 196 = 497) against 2N^2 + N(N+1)/2 + N^2 (693) for fp_mul_lz and fp_sqr_lz apart.  The doubled square is taken with
-// half-products as in mont_sqr: 2 c^2 = sum_i (2 c_i) c_i + sum_{i<j} (4 c_i) c_j, into the 2N column accumulators that also take a_j b_i;
-// then the same word-by-word reduction.  (The doubling chain needs 8 B^2: it passes c = 2B, normalised, so that the factor sits in the
-// VALUE spread over the limbs and not in every limb product.)
-// Operands: normalised lazy values (every limb below the top one < 2^29, the top one smaller still) with a*b + 2 c^2 < 2^12 m^2; result
-// < m (1 + 2^-13), limbs normalised.  Column k of the 2N holds at most
-//     N full products a_j b_i < 2^58,  N/2 cross products (4 c_i) c_j < 2^60 (the pairs i < j with i + j = k),  one diagonal (2 c_i) c_i < 2^59,
-//     N reduction terms q_i m_j < 2^58,  and the carry of the column below < 2^35:
-// (2N + 4 (N/2) + 2) 2^58 + 2^35 = 58 * 2^58 + 2^35 < 2^64 for N = 14 -- asserted below; not true of 15 limbs.
-template <int N> KZG_HD void mont_mulsqr2_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *m, const uint32_t inv) {
-    static_assert(2 * N + 4 * (N / 2) + 2 < 64,
-                  "column accumulators: N full, N/2 quadrupled cross, one doubled diagonal and N reduction products must stay below 2^64");
-    uint64_t acc[2 * N];
-    uint32_t c2[N], c4[N];
-#pragma unroll
-    for (int j = 0; j < N; j++) { c2[j] = c[j] << 1; c4[j] = c[j] << 2; }
-#pragma unroll
-    for (int k = 0; k < 2 * N; k++) acc[k] = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const uint32_t bi = b[i];
-#pragma unroll
-        for (int j = 0; j < N; j++) acc[i + j] += (uint64_t)a[j] * bi;
-        acc[2 * i] += (uint64_t)c2[i] * c[i];
-#pragma unroll
-        for (int j = i + 1; j < N; j++) acc[i + j] += (uint64_t)c4[i] * c[j];
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const uint32_t q = ((uint32_t)acc[i] * inv) & LMASK;
-#pragma unroll
-        for (int j = 0; j < N; j++) acc[i + j] += (uint64_t)q * m[j];
-        acc[i + 1] += acc[i] >> LB;
-    }
-    uint64_t cy = 0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        cy += acc[N + j];
-        r[j] = j < N - 1 ? ((uint32_t)cy & LMASK) : (uint32_t)cy;
-        cy >>= LB;
-    }
-}
-// ---------------------------------------------------------------------------------- column (product-scanning) forms of the lazy products
-// The same products with the SAME quotient digits q_i and the same result limbs, bit for bit, taken column by column on ONE 64-bit
-// accumulator: column k = sum_{i+j=k} (limb products) + sum_i q_i m[k-i], started from the column below >> 29.  The carry is then the addend
-// of the column's first multiply-add (v_mad_u64_u32 has a 64-bit addend that the row forms feed a literal 0 once per column), and the
-// columns N .. 2N-1 ARE the result limbs: the row forms' N carry additions and their final sweep of N - 1 additions are gone, the limb
-// products and the q_i m_j products are the same in number.  A column holds what a row-form accumulator of the same weight collects before
-// it is shifted out -- at most N rounds of products -- plus a carry below 2^35, so every bound stated at the row forms holds unchanged.
-// The row forms stay the default: KZG_MONT_COLS_FR selects the Fr pair for a translation unit, the Fp pair fp_mul_lz<COLS> / fp_sqr_lz<COLS> is
-// selected by the point routine (below).
-//
 // PIN: left alone the compiler re-associates a column into (products summed from 0) + carry -- its reassociation adds the value computed last
 // at the end -- which puts the 64-bit addition back (and for N = 14 gives the row forms' code again).  With PIN the device build passes the
 // accumulator through __builtin_annotation after every multiply-add: the intrinsic returns its argument and generates no instruction, but the
@@ -298,8 +241,8 @@ template <bool PIN> KZG_HD void col_mad(uint64_t &acc, const uint32_t x, const u
     if (PIN) acc = __builtin_annotation(acc, "col");
 #endif
 }
-// the reduction half of column k (shared by the four forms): the q_i m[k-i] of the quotient digits known so far, then for k < N the new digit
-// q_k (which clears the column's low 29 bits), for k >= N the result limb k - N.  Leaves the accumulator shifted for column k + 1.
+// the reduction half of column k: the q_i m[k-i] of the quotient digits known so far, then for k < N the new digit q_k (which clears the column's
+// low 29 bits), for k >= N the result limb k - N.  Leaves the accumulator shifted for column k + 1.
 template <int N, bool PIN> KZG_HD void col_reduce(uint64_t &acc, uint32_t *q, uint32_t *r, const int k, const uint32_t *m, const uint32_t inv) {
     if (k < N) {
 #pragma unroll
@@ -313,57 +256,32 @@ template <int N, bool PIN> KZG_HD void col_reduce(uint64_t &acc, uint32_t *q, ui
     }
     acc >>= LB;
 }
-// mont_mul_lazy by columns: N^2 + N^2 limb products, no 64-bit additions beside the multiply-adds (and, where m[0] = 1, the q_k that complete a column).
-// Column k: at most N rounds of a_j b_i + q_i m_j below 2^58 each for normalised operands; for N = 9 one operand may be raw with limbs up to 2^31
-// (eval_core.h): 9 * 2^60 + 9 * 2^58 + carry < 2^64.
-template <int N, bool PIN = false> KZG_HD void mont_mul_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
-    static_assert(N <= 14, "a column: 2 N limb products of < 2^58 and a carry must stay below 2^64 (with headroom for the top limb's excess)");
-    uint32_t q[N], t[N];
+// Within a column: the full products, interleaved per i; the diagonal (k / 2, k / 2); the cross pairs (i, k - i) with i < k - i < N; the reduction.
+template <int N, bool PIN, int FULL, int SH, bool LAZY> KZG_HD void mont_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c,
+                                                                              const uint32_t *d, const uint32_t *e, const uint32_t *m, const uint32_t inv) {
+    static_assert(FULL >= 0 && FULL <= 2 && SH >= -1 && LB + SH + 1 <= 32 && mont_units(N, FULL, SH) < 64,
+                  "a column's limb and reduction products and a carry must stay below 2^64");
+    constexpr int S = SH < 0 ? 0 : SH;
+    uint32_t q[N], t[N], e1[N], e2[N];
+    if (SH >= 0) {
+#pragma unroll
+        for (int j = 0; j < N; j++) { e1[j] = e[j] << S; e2[j] = e[j] << (S + 1); }
+    }
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; k++) {
+        if (FULL >= 1) {
 #pragma unroll
-        for (int i = 0; i < N; i++) if (i <= k && k - i < N) col_mad<PIN>(acc, a[k - i], b[i]);
-        col_reduce<N, PIN>(acc, q, t, k, m, inv);
+            for (int i = 0; i < N; i++) if (i <= k && k - i < N) { col_mad<PIN>(acc, a[k - i], b[i]); if (FULL == 2) col_mad<PIN>(acc, c[k - i], d[i]); }
+        }
+        if (SH >= 0) {
+            if (!(k & 1)) col_mad<PIN>(acc, e1[k / 2], e[k / 2]);
+#pragma unroll
+            for (int i = 0; i < N; i++) if (2 * i < k && k - i < N) col_mad<PIN>(acc, e2[i], e[k - i]);
+        }
+        col_reduce<N, PIN>(acc, q, t, k, m, inv);                  // (into t: the operands are still being read)
     }
-    t[N - 1] = (uint32_t)acc;                                      // column 2N - 1: the carry alone; the top limb keeps any excess
-#pragma unroll
-    for (int j = 0; j < N; j++) r[j] = t[j];
-}
-// mont_mul2_lazy by columns.  Column k: at most N rounds of a_j b_i + c_j d_i + q_i m_j, each product < 2^58 for normalised operands (3 N 2^58 <
-// 2^63.4 at N = 14), or, for the evaluation tree's raw operands at N = 9 (eval_core.h: A limbs < 2^30, B limbs < 3 * 2^29 against normalised z^k, s),
-// 9 (2^59 + 3 * 2^58 + 2^58) = 27 * 2^59 < 2^63.8; the carry adds less than 2^35.
-template <int N, bool PIN = false> KZG_HD void mont_mul2_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
-                                                                   const uint32_t *m, const uint32_t inv) {
-    static_assert(N <= 14, "a column: 3 N limb products of < 2^58 and a carry must stay below 2^64");
-    uint32_t q[N], t[N];
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 2 * N - 1; k++) {
-#pragma unroll
-        for (int i = 0; i < N; i++) if (i <= k && k - i < N) { col_mad<PIN>(acc, a[k - i], b[i]); col_mad<PIN>(acc, c[k - i], d[i]); }
-        col_reduce<N, PIN>(acc, q, t, k, m, inv);
-    }
-    t[N - 1] = (uint32_t)acc;
-#pragma unroll
-    for (int j = 0; j < N; j++) r[j] = t[j];
-}
-// mont_sqr by columns: the N (N + 1) / 2 distinct limb products against the pre-doubled copy.  Column k: at most N / 2 cross products < 2^59, one
-// diagonal < 2^58 and N reduction products < 2^58: (2 (N / 2) + 1 + N) 2^58 + 2^35 < 2^64 up to N = 14.
-template <int N, bool LAZY = false, bool PIN = false> KZG_HD void mont_sqr_cols(uint32_t *r, const uint32_t *a, const uint32_t *m, const uint32_t inv) {
-    static_assert(2 * (N / 2) + 1 + N < 64, "a column: N/2 doubled cross, one diagonal and N reduction products must stay below 2^64");
-    uint32_t q[N], t[N], a2[N];
-#pragma unroll
-    for (int j = 0; j < N; j++) a2[j] = a[j] << 1;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 2 * N - 1; k++) {
-        if (!(k & 1)) col_mad<PIN>(acc, a[k / 2], a[k / 2]);       // the diagonal (k / 2, k / 2), then the pairs (i, k - i) with i < k - i < N
-#pragma unroll
-        for (int i = 0; i < N; i++) if (2 * i < k && k - i < N) col_mad<PIN>(acc, a2[i], a[k - i]);
-        col_reduce<N, PIN>(acc, q, t, k, m, inv);
-    }
-    t[N - 1] = (uint32_t)acc;                                      // (canonical form: t < 2m for an operand below m, the top limb needs no mask)
+    t[N - 1] = (uint32_t)acc;      // column 2N - 1: the carry alone; LAZY: the top limb keeps any excess (canonical: t < 2m, it needs no mask)
     if (LAZY) {
 #pragma unroll
         for (int j = 0; j < N; j++) r[j] = t[j];
@@ -374,29 +292,30 @@ template <int N, bool LAZY = false, bool PIN = false> KZG_HD void mont_sqr_cols(
 #pragma unroll
     for (int j = 0; j < N; j++) r[j] = br ? t[j] : s[j];
 }
-// mont_mulsqr2_lazy by columns: r = (a b + 2 c^2) / R.  Column k holds exactly what column k of the row form's 2N accumulators holds:
-//     at most N full products a_j b_i < 2^58,  N/2 cross products (4 c_i) c_j < 2^60,  one diagonal (2 c_i) c_i < 2^59,  N reduction products < 2^58
-// and the carry of the column below < 2^35: (2N + 4 (N/2) + 2) 2^58 + 2^35 = 58 * 2^58 + 2^35 < 2^64 for N = 14 -- asserted below; not true of 15 limbs.
+// The other seven names.  (mont_mul has no column sibling: no canonical product sits on a throughput path.)
+template <int N> KZG_HD void mont_mul_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
+    mont_mul<N, false, true>(r, a, b, m, inv);
+}
+template <int N> KZG_HD void mont_mul2_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                                            const uint32_t *m, const uint32_t inv) {
+    mont_mul<N, true, true>(r, a, b, m, inv, c, d);
+}
+template <int N> KZG_HD void mont_mulsqr2_lazy(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *m, const uint32_t inv) {
+    mont_sqr<N, true, true, 1>(r, c, m, inv, a, b);
+}
+template <int N, bool PIN = false> KZG_HD void mont_mul_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *m, const uint32_t inv) {
+    mont_cols<N, PIN, 1, -1, true>(r, a, b, nullptr, nullptr, nullptr, m, inv);
+}
+template <int N, bool PIN = false> KZG_HD void mont_mul2_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                                                                   const uint32_t *m, const uint32_t inv) {
+    mont_cols<N, PIN, 2, -1, true>(r, a, b, c, d, nullptr, m, inv);
+}
+template <int N, bool LAZY = false, bool PIN = false> KZG_HD void mont_sqr_cols(uint32_t *r, const uint32_t *a, const uint32_t *m, const uint32_t inv) {
+    mont_cols<N, PIN, 0, 0, LAZY>(r, nullptr, nullptr, nullptr, nullptr, a, m, inv);
+}
 template <int N, bool PIN = false> KZG_HD void mont_mulsqr2_lazy_cols(uint32_t *r, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *m,
                                                                       const uint32_t inv) {
-    static_assert(2 * N + 4 * (N / 2) + 2 < 64,
-                  "a column: N full, N/2 quadrupled cross, one doubled diagonal and N reduction products must stay below 2^64");
-    uint32_t q[N], t[N], c2[N], c4[N];
-#pragma unroll
-    for (int j = 0; j < N; j++) { c2[j] = c[j] << 1; c4[j] = c[j] << 2; }
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 2 * N - 1; k++) {
-#pragma unroll
-        for (int i = 0; i < N; i++) if (i <= k && k - i < N) col_mad<PIN>(acc, a[k - i], b[i]);
-        if (!(k & 1)) col_mad<PIN>(acc, c2[k / 2], c[k / 2]);
-#pragma unroll
-        for (int i = 0; i < N; i++) if (2 * i < k && k - i < N) col_mad<PIN>(acc, c4[i], c[k - i]);
-        col_reduce<N, PIN>(acc, q, t, k, m, inv);
-    }
-    t[N - 1] = (uint32_t)acc;
-#pragma unroll
-    for (int j = 0; j < N; j++) r[j] = t[j];
+    mont_cols<N, PIN, 1, 1, true>(r, a, b, nullptr, nullptr, c, m, inv);
 }
 // 32-bit word array (little-endian words, NW of them) -> N 29-bit limbs
 template <int N, int NW> KZG_HD void words_to_limbs(uint32_t *l, const uint32_t *w) {
@@ -431,16 +350,14 @@ KZG_HD void fp_dbl(Fp &r, const Fp &a) { KZG_FP_CONSTS mod_add<NFP>(r.l, a.l, a.
 KZG_HD void fp_neg(Fp &r, const Fp &a) { Fp z = fp_zero(); fp_sub(r, z, a); }
 KZG_HD bool fp_is_zero(const Fp &a) { return ul_is_zero<NFP>(a.l); }
 KZG_HD bool fp_eq(const Fp &a, const Fp &b) { return ul_eq<NFP>(a.l, b.l); }
+// (a translation unit that defines KZG_FP_MUL_NOINLINE before this header calls the two canonical products out of line)
 #if defined(KZG_FP_MUL_NOINLINE)
-KZG_HD_NOINLINE void fp_mul(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
+#define KZG_FP_MUL_ATTR KZG_HD_NOINLINE
 #else
-KZG_HD void fp_mul(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
+#define KZG_FP_MUL_ATTR KZG_HD
 #endif
-#if defined(KZG_FP_MUL_NOINLINE)
-KZG_HD_NOINLINE void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, FP_MOD, FP_INVW); }
-#else
-KZG_HD void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, FP_MOD, FP_INVW); }
-#endif
+KZG_FP_MUL_ATTR void fp_mul(Fp &r, const Fp &a, const Fp &b) { KZG_FP_CONSTS mont_mul<NFP>(r.l, a.l, b.l, FP_MOD, FP_INVW); }
+KZG_FP_MUL_ATTR void fp_sqr(Fp &r, const Fp &a) { KZG_FP_CONSTS mont_sqr<NFP>(r.l, a.l, FP_MOD, FP_INVW); }
 // ---- lazy (unreduced) Fp: R = 2^406 leaves 25 bits above p, so values may run up to a few dozen p between reductions.
 // Products of operands a < 2^6 p, b < 2^6 p come out below p (1 + 2^-13) without the final conditional subtraction; sums are
 // plain limb additions with carry normalisation; differences add a multiple of p first.  Used by the accumulation loops of the
@@ -619,18 +536,20 @@ KZG_HD void fr_sqr(Fr &r, const Fr &a) { KZG_FR_CONSTS mont_sqr<NFR>(r.l, a.l, F
 // lazy product: operands < ~2.6 r, result < 1.1 r, not canonical (see mont_mul_lazy)
 // (a translation unit that defines KZG_MONT_COLS_FR before this header takes the two lazy Fr products in their column forms: same limbs out)
 #if defined(KZG_MONT_COLS_FR)
-KZG_HD void fr_mul_lazy(Fr &r, const Fr &a, const Fr &b) { KZG_FR_CONSTS mont_mul_lazy_cols<NFR, true>(r.l, a.l, b.l, FR_MOD, FR_INVW); }
+constexpr bool FR_LAZY_COLS = true;
 #else
-KZG_HD void fr_mul_lazy(Fr &r, const Fr &a, const Fr &b) { KZG_FR_CONSTS mont_mul_lazy<NFR>(r.l, a.l, b.l, FR_MOD, FR_INVW); }
+constexpr bool FR_LAZY_COLS = false;
 #endif
+KZG_HD void fr_mul_lazy(Fr &r, const Fr &a, const Fr &b) {
+    KZG_FR_CONSTS
+    if (FR_LAZY_COLS) mont_mul_lazy_cols<NFR, true>(r.l, a.l, b.l, FR_MOD, FR_INVW); else mont_mul_lazy<NFR>(r.l, a.l, b.l, FR_MOD, FR_INVW);
+}
 // r = a*b + c*d with one reduction (lazy; result < 1.1 r for a*b + c*d < ~5 r^2)
-#if defined(KZG_MONT_COLS_FR)
-KZG_HD void fr_mul2_lazy(Fr &r, const Fr &a, const Fr &b, const Fr &c, const Fr &d) { KZG_FR_CONSTS mont_mul2_lazy_cols<NFR, true>(r.l, a.l, b.l, c.l, d.l,
-        FR_MOD, FR_INVW); }
-#else
-KZG_HD void fr_mul2_lazy(Fr &r, const Fr &a, const Fr &b, const Fr &c, const Fr &d) { KZG_FR_CONSTS mont_mul2_lazy<NFR>(r.l, a.l, b.l, c.l, d.l, FR_MOD,
-        FR_INVW); }
-#endif
+KZG_HD void fr_mul2_lazy(Fr &r, const Fr &a, const Fr &b, const Fr &c, const Fr &d) {
+    KZG_FR_CONSTS
+    if (FR_LAZY_COLS) mont_mul2_lazy_cols<NFR, true>(r.l, a.l, b.l, c.l, d.l, FR_MOD, FR_INVW);
+    else mont_mul2_lazy<NFR>(r.l, a.l, b.l, c.l, d.l, FR_MOD, FR_INVW);
+}
 // lazy sum: plain limb addition with carry normalisation, no reduction (value grows; keep chains short)
 KZG_HD void fr_add_lazy(Fr &r, const Fr &a, const Fr &b) {
     uint32_t c = 0;

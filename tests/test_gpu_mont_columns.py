@@ -1,6 +1,7 @@
-"""-m gpu: the kernels that were built and measured with the column forms of field.h's lazy Montgomery products -- k_eval (k_verify.hip:
-KZG_MONT_COLS_FR) and the bucket kernel (k_g1.hip: g1x_add_mixed_lazy<true>) keep them, the point validation and the tails of the bucket form
-went back to the row forms (EXPERIMENTS.md) -- at the smallest shapes that reach them, byte for byte against the CPU oracle:
+"""-m gpu: the kernels that were built and measured with the column forms of field.h's lazy Montgomery products (the wrappers of its column body
+mont_cols; the row forms are those of the bodies mont_mul and mont_sqr) -- k_eval (k_verify.hip: KZG_MONT_COLS_FR) and the bucket kernel (k_g1.hip:
+g1x_add_mixed_lazy<true>) keep them, the point validation and the tails of the bucket form went back to the row forms (EXPERIMENTS.md) -- at the
+smallest shapes that reach them, byte for byte against the CPU oracle:
 
   * k_eval: one batch of 4 blobs (one workgroup) and one of 5 (a second workgroup whose spare waves repeat the last blob): an all-zero blob, a blob of
     r - 1 throughout, random blobs -- z and y of the records as the oracle computes them -- and the same batches with ONE field element replaced by

@@ -1,8 +1,10 @@
 """The column (product-scanning) forms of the lazy Montgomery products of kzg_rust_amd/csrc/field.h -- mont_mul_lazy_cols, mont_mul2_lazy_cols,
-mont_sqr_cols, mont_mulsqr2_lazy_cols -- compiled for the HOST (tests/native/mont_columns_probe.cpp) and checked, for N = 9 (Fr) and N = 14 (Fp),
-against their row forms limb for limb and against Python big integers.  The probe takes RAW limbs, so the operands sit at the bounds the
-callers really pass: lazy values of up to 32p with the excess in the top limb, all-ones limbs, the carry-free operands of the evaluation
-tree (limbs up to 2^30, 3 * 2^29 and 2^31), the doubling's operand bounds, zeros and multiples of the modulus.  Runs without a GPU."""
+mont_sqr_cols, mont_mulsqr2_lazy_cols, the four wrappers of the one column body mont_cols -- compiled for the HOST
+(tests/native/mont_columns_probe.cpp) and checked, for N = 9 (Fr) and N = 14 (Fp), against their row forms (mont_mul_lazy, mont_mul2_lazy: the
+body mont_mul<N, TWO, LAZY>; mont_sqr, mont_mulsqr2_lazy: the body mont_sqr<N, LAZY, AB, SH>) limb for limb and against Python big integers.  The probe takes RAW limbs,
+so the operands sit at the bounds the callers really pass: lazy values of up to 32p with the excess in the top limb, all-ones limbs, the
+carry-free operands of the evaluation tree (limbs up to 2^30, 3 * 2^29 and 2^31), the doubling's operand bounds, zeros and multiples of the
+modulus.  Runs without a GPU."""
 import ctypes as C
 import os
 import random
