@@ -71,12 +71,6 @@ static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
     return done(KZG355_OK);
 }
 
-// a call refused as a whole: every unit gets the code the call returns
-int cc_refuse(int *status, size_t units, int code) {
-    if (status) for (size_t i = 0; i < units; i++) status[i] = code;
-    return code;
-}
-
 // The device chain behind the field stage.  compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_recover.hip) differ in their field
 // stage only, and both leave the same two things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role:
 // y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H.
@@ -114,18 +108,14 @@ static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     hipStream_t st = w->stream;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    int rc;
+    if ((rc = launch_set_results(w, m))) return rc;
     if (cells_out && !dev_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
     if (proofs_out && !dev_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
     if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    w->in_flight = false;
-    tm.collect();
-    for (int i = 0; i < m; i++) {
-        const int stt = status_from_err(w->h_err.as<int>()[i]);
-        if (status) status[c0 + i] = stt;
-        if (stt != KZG355_OK && first == KZG355_OK) first = stt;
-    }
+    if ((rc = launch_set_wait(w, tm))) return rc;
+    rc = launch_set_read(w, m, status ? status + c0 : nullptr);
+    if (first == KZG355_OK) first = rc;
     return KZG355_OK;
 }
 
@@ -138,7 +128,7 @@ static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int, uint8_t *)> &stage,
            bool dev_out) {
-    auto refuse = [&](int code) { return cc_refuse(status, units, code); };
+    auto refuse = [&](int code) { return refuse_call(status, units, code); };
     if (units > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
     if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
     WsGuard g(cs);
@@ -157,9 +147,8 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
     auto run = [&]() -> int {                                     // (HIPCHK returns from here: a failed chunk refuses the whole call)
     for (size_t c0 = 0; c0 < units; c0 += CH) {
         const int m = (int)(units - c0 < CH ? units - c0 : CH);
-        w->in_flight = true;
-        HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * m, w->stream));
         int crc;
+        if ((crc = launch_set_begin(w, m))) return crc;           // (cc_chain_buffers has sized the words for CH)
         uint8_t *d_cells = !cells_out ? nullptr : dev_out ? cells_out + cell_bytes * c0 : w->q.as<uint8_t>();
         uint8_t *d_proofs = dev_out && proofs_out ? proofs_out + (size_t)48 * CC_FFT * c0 : w->out48.as<uint8_t>();
         if ((crc = stage(w, tm, c0, m, d_cells))) return crc;
@@ -176,10 +165,9 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
 // is refused here, once; then contiguous ranges of the blobs go to as many replicas as there are blobs, fn(replica, first blob, count) on the
 // replica's own host thread (cc_run takes its workspace and scopes its device there).  A blob is never cut.
 int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn) {
-    if (units > ((size_t)1 << 32) || is_small(cs)) return cc_refuse(status, units, KZG355_BADARGS);
-    MultiDev *m = cs->multi;
-    const size_t D = m->rep.size();
-    return fan_out(units < D ? units : D, units, [&](size_t d, size_t u0, size_t n) { return fn(m->rep[d], u0, n); });
+    if (units > ((size_t)1 << 32) || is_small(cs)) return refuse_call(status, units, KZG355_BADARGS);
+    const size_t D = cs->multi->rep.size();
+    return fan_out(cs, units < D ? units : D, units, fn);
 }
 
 // n blobs on the device of cs (a replica, for a handle over several devices); the arguments are checked
@@ -202,10 +190,10 @@ static int cc_single(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, in
 // the first device of a handle over several, where they live
 static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
                    bool device = false) {
-    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return cc_refuse(status, n, KZG355_BADARGS);
+    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return refuse_call(status, n, KZG355_BADARGS);
     if (n == 0) return KZG355_OK;
-    if (!blobs) return cc_refuse(status, n, KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return cc_refuse(status, n, KZG355_BADARGS);
+    if (!blobs) return refuse_call(status, n, KZG355_BADARGS);
+    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return refuse_call(status, n, KZG355_BADARGS);
     if (cs->multi && !device)
         return cc_fan_out(cs, n, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
             return cc_single(cells_out ? cells_out + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * u0 : nullptr, proofs_out ? proofs_out + (size_t)48 * CC_FFT * u0 : nullptr,

@@ -112,7 +112,7 @@ static int rc_run(uint8_t *cells_out, uint8_t *proofs_out, int *status, const si
 // m blobs of n cells each, the cells of a blob at the n strictly ascending indices idx (one set for all blobs; always host memory)
 static int rc_shared(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *idx, const uint8_t *cells, size_t n, size_t m,
                      const kzg355_settings *cs, bool device = false) {
-    auto refuse = [&](int code) { return cc_refuse(status, m, code); };
+    auto refuse = [&](int code) { return refuse_call(status, m, code); };
     if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
     uint64_t mask[2];
     if (!idx || !rc_mask(mask, idx, n)) return refuse(KZG355_BADARGS);
@@ -130,7 +130,7 @@ static int rc_shared(uint8_t *cells_out, uint8_t *proofs_out, int *status, const
 // m blobs, blob i known at counts[i] cells: its index list and its cells follow those of blob i - 1 in idx and cells
 static int rc_sets(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *counts, const size_t *idx, const uint8_t *cells, size_t m,
                    const kzg355_settings *cs, bool device) {
-    auto refuse = [&](int code) { return cc_refuse(status, m, code); };
+    auto refuse = [&](int code) { return refuse_call(status, m, code); };
     if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
     if (m == 0) return KZG355_OK;
     if (!counts || !idx || !cells || m > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);

@@ -267,7 +267,7 @@ static void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_
 // handle's device; prep_form 0 by size, 1 device preparation, 2 copy back and prepare on the host.
 static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
                        size_t npg, size_t groups, const kzg355_settings *cs, bool device, int prep_form) {
-    auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
+    auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
     WsGuard g(cs);
     if (!g.w) return refuse(KZG355_NO_DEVICE);
     kzg355_settings *s = g.s; Workspace *w = g.w;
@@ -307,11 +307,10 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     if ((rc = cell_reserve(w, !device, n, groups, S, meta_ints))) return refuse(rc);
     Fp *f12 = nullptr;
     if (w->pair_f.ensure(pairing_f12_bytes(G)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
-    w->in_flight = true;
+    if ((rc = launch_set_begin(w, groups, true))) return rc;       // (cell_reserve has sized the words)
     Timed tm(s, w);
     const uint8_t *d_cells = device ? cells : w->blobs.as<uint8_t>(), *d_proofs = device ? proofs : w->proofs.as<uint8_t>();
     uint8_t *d_dbg = dbg ? w->out48.as<uint8_t>() + 32 * groups : nullptr;
-    HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * groups, st));
     if (dev_prep) {
         int *m = w->q.as<int>() + 4 * (size_t)S;
         int *d_cidx = m + (G + 1) + N, *d_ucount = m + (G + 1) + 3 * N, *d_gtab = gtab_ints ? d_ucount + groups : nullptr;
@@ -332,21 +331,14 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, G, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from, s->miller_segments);
     tm.end();
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(w->h_ok.p, w->ok.p, sizeof(int) * groups, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * groups, hipMemcpyDeviceToHost, st));
+    if ((rc = launch_set_results(w, groups, true))) return rc;
     if (dbg) HIPCHK(hipMemcpyAsync(w->h_out.p, d_dbg, (size_t)CELL_DEBUG_BYTES * groups, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    w->in_flight = false;
-    tm.collect();
+    if ((rc = launch_set_wait(w, tm))) return rc;
     if (dbg) memcpy(dbg, w->h_out.p, (size_t)CELL_DEBUG_BYTES * groups);
-    int first = KZG355_OK;
-    for (int i = 0; i < G; i++) {
-        const int stt = !dev_prep && hp.hg[i].bad_index ? KZG355_BADARGS : status_from_err(w->h_err.as<int>()[i]);
-        if (status) status[i] = stt;
+    return launch_set_read(w, groups, status, 0, [&](size_t i, int &stt) {
+        if (!dev_prep && hp.hg[i].bad_index) stt = KZG355_BADARGS;            // the host's own finding (the device preparation sets the error word)
         ok[i] = stt == KZG355_OK && w->h_ok.as<int>()[i] != 0;
-        if (stt != KZG355_OK && first == KZG355_OK) first = stt;
-    }
-    return first;
+    });
 }
 
 // ---- a handle over several devices (multi_device.hip) ------------------------------------------------------------------------------------------
@@ -361,102 +353,77 @@ static int cell_multi_sharded(bool *ok, int *status, uint8_t *dbg, const uint8_t
     MultiDev *m = cs->multi;
     const size_t D = m->rep.size();
     const int G = (int)groups;
-    auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
+    auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
     DeviceScope keep; keep.hold();               // this thread visits every replica's device below
     std::vector<size_t> cnt(D), off(D);
     for (size_t d = 0; d < D; d++) { off[d] = npg * d / D; cnt[d] = npg * (d + 1) / D - off[d]; }
-    std::vector<std::unique_ptr<WsGuard>> gs;                    // (whatever device the last guard leaves current, `keep` puts the caller's back)
-    for (size_t d = 0; d < D; d++) {
-        gs.emplace_back(new WsGuard(m->rep[d]));
-        if (!gs[d]->w) return refuse(KZG355_NO_DEVICE);
-    }
+    GuardList gs;                                                 // (whatever device the last guard leaves current, `keep` puts the caller's back)
+    for (size_t d = 0; d < D; d++) if (!gs.add(m->rep[d])) return refuse(KZG355_NO_DEVICE);
     std::vector<uint8_t> h_dig(32 * groups);
     cell_host_digests(gs[0]->s, commitments, cell_indices, cells, proofs, npg, groups, h_dig.data());
-    auto join = [](std::vector<std::future<int>> &fut) {
-        int first = KZG355_OK;
-        for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
-        return first;
-    };
     // stage 1: the block's three sums per group in lc_partials, r of every group in out48, its status per group in st1
     std::vector<std::vector<int>> st1(D, std::vector<int>(groups, KZG355_OK));
     {
-        std::vector<std::future<int>> fut;
-        for (size_t d = 0; d < D; d++) {
-            fut.push_back(std::async(std::launch::async, [&, d]() -> int {
-                kzg355_settings *s = gs[d]->s; Workspace *w = gs[d]->w;
-                if (hipSetDevice(s->device) != hipSuccess) return KZG355_NO_DEVICE;
-                int rc;
-                if ((rc = ensure_cell_setup(s, w))) return rc;
-                s->n_cell_sets.fetch_add(1);
-                CellHostPrep hp;
-                cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, off[d], cnt[d]);
-                if ((rc = cell_reserve(w, true, (int)cnt[d], groups, hp.S, hp.meta.size()))) return rc;
-                hipStream_t st = w->stream;
-                w->in_flight = true;
-                Timed tm(s, w);
-                HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * groups, st));
-                if ((rc = cell_upload(w, hp, h_dig.data(), cells, proofs, npg, off[d], cnt[d], groups))) return rc;
-                cell_chain(s, w, tm, w->blobs.as<uint8_t>(), w->proofs.as<uint8_t>(), hp.S, (int)cnt[d], G, (int)off[d], false, nullptr);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * groups, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                w->in_flight = false;
-                tm.collect();
-                for (size_t g = 0; g < groups; g++) st1[d][g] = hp.hg[g].bad_index ? KZG355_BADARGS : status_from_err(w->h_err.as<int>()[g]);
-                return KZG355_OK;
-            }));
-        }
-        const int rc = join(fut);
-        if (rc != KZG355_OK) return refuse(rc);
+        const int rc1 = fan_out_guards(gs, D, [&](size_t d) -> int {
+            kzg355_settings *s = gs[d]->s; Workspace *w = gs[d]->w;
+            int rc;
+            if ((rc = ensure_cell_setup(s, w))) return rc;
+            s->n_cell_sets.fetch_add(1);
+            CellHostPrep hp;
+            cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, off[d], cnt[d]);
+            if ((rc = cell_reserve(w, true, (int)cnt[d], groups, hp.S, hp.meta.size()))) return rc;
+            if ((rc = launch_set_begin(w, groups))) return rc;
+            Timed tm(s, w);
+            if ((rc = cell_upload(w, hp, h_dig.data(), cells, proofs, npg, off[d], cnt[d], groups))) return rc;
+            cell_chain(s, w, tm, w->blobs.as<uint8_t>(), w->proofs.as<uint8_t>(), hp.S, (int)cnt[d], G, (int)off[d], false, nullptr);
+            HIPCHK(hipGetLastError());
+            if ((rc = launch_set_results(w, groups)) || (rc = launch_set_wait(w, tm))) return rc;
+            launch_set_read(w, groups, st1[d].data(), 0, [&](size_t g, int &stt) { if (hp.hg[g].bad_index) stt = KZG355_BADARGS; });
+            return KZG355_OK;
+        });
+        if (rc1 != KZG355_OK) return refuse(rc1);
     }
     m->n_peer_exchanges++;
     // stage 2: group g on device g mod D, over the sums of all blocks
     {
-        std::vector<std::future<int>> fut;
-        for (size_t t = 0; t < D && t < groups; t++) {
-            fut.push_back(std::async(std::launch::async, [&, t]() -> int {
-                kzg355_settings *s = gs[t]->s; Workspace *w = gs[t]->w;
-                if (hipSetDevice(s->device) != hipSuccess) return KZG355_NO_DEVICE;
-                const size_t Gt = (groups - t + D - 1) / D;              // groups t, t + D, ...
-                int rc;
-                DevBuf &gath = w->records;                                 // [group of this device][block][3 sums]
-                if ((rc = gath.ensure(sizeof(G1Jac) * 3 * D * Gt))) return rc;       // (pair_pts, ok, out48 ...: cell_reserve sized them for all groups)
-                Fp *f12 = nullptr;
-                if (w->pair_f.ensure(pairing_f12_bytes((int)Gt)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
-                hipStream_t st = w->stream;
-                w->in_flight = true;
-                Timed tm(s, w);
-                for (size_t k = 0; k < Gt; k++)
-                    for (size_t d = 0; d < D; d++) {
-                        G1Jac *dst = gath.as<G1Jac>() + 3 * (k * D + d);
-                        const G1Jac *src = gs[d]->w->lc_partials.as<G1Jac>() + 3 * (t + k * D);
-                        if (gs[d]->s->device == s->device) HIPCHK(hipMemcpyAsync(dst, src, sizeof(G1Jac) * 3, hipMemcpyDeviceToDevice, st));
-                        else HIPCHK(hipMemcpyPeerAsync(dst, s->device, src, gs[d]->s->device, sizeof(G1Jac) * 3, st));
-                    }
-                uint8_t *d_r = w->out48.as<uint8_t>(), *d_dbg = dbg ? d_r + 32 * groups : nullptr;
-                tm.begin("cell_merge");
-                if (!launch_cell_merge(gath.as<G1Jac>(), (int)D, (int)Gt, d_r, (int)t, (int)D, w->pair_pts.as<PairPt>(), d_dbg, st)) return KZG355_INTERNAL;
-                tm.end();
-                tm.begin("cell_pairing");
-                launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, (int)Gt, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from,
-                               s->miller_segments);
-                tm.end();
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(w->h_ok.p, w->ok.p, sizeof(int) * Gt, hipMemcpyDeviceToHost, st));
-                if (dbg) HIPCHK(hipMemcpyAsync(w->h_out.p, d_dbg, (size_t)CELL_DEBUG_BYTES * Gt, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                w->in_flight = false;
-                tm.collect();
-                for (size_t k = 0; k < Gt; k++) {
-                    const size_t g = t + k * D;
-                    if (dbg) memcpy(dbg + (size_t)CELL_DEBUG_BYTES * g, w->h_out.as<uint8_t>() + (size_t)CELL_DEBUG_BYTES * k, CELL_DEBUG_BYTES);
-                    ok[g] = w->h_ok.as<int>()[k] != 0;
+        const int rc2 = fan_out_guards(gs, D < groups ? D : groups, [&](size_t t) -> int {
+            kzg355_settings *s = gs[t]->s; Workspace *w = gs[t]->w;
+            const size_t Gt = (groups - t + D - 1) / D;              // groups t, t + D, ...
+            int rc;
+            DevBuf &gath = w->records;                                 // [group of this device][block][3 sums]
+            if ((rc = gath.ensure(sizeof(G1Jac) * 3 * D * Gt))) return rc;       // (pair_pts, ok, out48 ...: cell_reserve sized them for all groups)
+            Fp *f12 = nullptr;
+            if (w->pair_f.ensure(pairing_f12_bytes((int)Gt)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
+            hipStream_t st = w->stream;
+            w->in_flight = true;                                  // (no error words in this stage -- the blocks' are in st1 -- so of the frame only the wait)
+            Timed tm(s, w);
+            for (size_t k = 0; k < Gt; k++)
+                for (size_t d = 0; d < D; d++) {
+                    G1Jac *dst = gath.as<G1Jac>() + 3 * (k * D + d);
+                    const G1Jac *src = gs[d]->w->lc_partials.as<G1Jac>() + 3 * (t + k * D);
+                    if (gs[d]->s->device == s->device) HIPCHK(hipMemcpyAsync(dst, src, sizeof(G1Jac) * 3, hipMemcpyDeviceToDevice, st));
+                    else HIPCHK(hipMemcpyPeerAsync(dst, s->device, src, gs[d]->s->device, sizeof(G1Jac) * 3, st));
                 }
-                return KZG355_OK;
-            }));
-        }
-        const int rc = join(fut);
-        if (rc != KZG355_OK) return refuse(rc);
+            uint8_t *d_r = w->out48.as<uint8_t>(), *d_dbg = dbg ? d_r + 32 * groups : nullptr;
+            tm.begin("cell_merge");
+            if (!launch_cell_merge(gath.as<G1Jac>(), (int)D, (int)Gt, d_r, (int)t, (int)D, w->pair_pts.as<PairPt>(), d_dbg, st)) return KZG355_INTERNAL;
+            tm.end();
+            tm.begin("cell_pairing");
+            launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, (int)Gt, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from,
+                           s->miller_segments);
+            tm.end();
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(w->h_ok.p, w->ok.p, sizeof(int) * Gt, hipMemcpyDeviceToHost, st));
+            if (dbg) HIPCHK(hipMemcpyAsync(w->h_out.p, d_dbg, (size_t)CELL_DEBUG_BYTES * Gt, hipMemcpyDeviceToHost, st));
+            if ((rc = launch_set_wait(w, tm))) return rc;
+            for (size_t k = 0; k < Gt; k++) {
+                const size_t g = t + k * D;
+                if (dbg) memcpy(dbg + (size_t)CELL_DEBUG_BYTES * g, w->h_out.as<uint8_t>() + (size_t)CELL_DEBUG_BYTES * k, CELL_DEBUG_BYTES);
+                ok[g] = w->h_ok.as<int>()[k] != 0;
+            }
+            return KZG355_OK;
+        });
+        if (rc2 != KZG355_OK) return refuse(rc2);
     }
     // an Err in any block is the group's Err: the first one in block order
     int first = KZG355_OK;
@@ -484,10 +451,10 @@ static int cell_multi(bool *ok, int *status, uint8_t *dbg, const uint8_t *commit
     const bool force_sharded = cs->force_sharded && npg >= D;         // (test hook: kzg355_options.force_sharded)
     if (!force_sharded && (groups >= D || npg < CELL_SHARD_MIN_CELLS_PER_DEVICE * D)) {
         // as many replicas as there are groups; each range's WsGuard scopes its device on the range's own thread
-        return fan_out(groups < D ? groups : D, groups, [&](size_t d, size_t g0, size_t n) -> int {
+        return fan_out(cs, groups < D ? groups : D, groups, [&](const kzg355_settings *rep, size_t g0, size_t n) -> int {
             const size_t c0 = g0 * npg;
             return cell_single(ok + g0, status ? status + g0 : nullptr, dbg ? dbg + (size_t)CELL_DEBUG_BYTES * g0 : nullptr, commitments + 48 * c0,
-                               cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, npg, n, m->rep[d], false, 0);
+                               cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, npg, n, rep, false, 0);
         });
     }
     return cell_multi_sharded(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs);
@@ -498,7 +465,7 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
                      size_t npg, size_t groups, const kzg355_settings *cs, bool device = false, int prep_form = 0) {
     if (!cs || !ok) return KZG355_BADARGS;
     if (groups == 0) return KZG355_OK;
-    auto refuse = [&](int code) { for (size_t i = 0; i < groups; i++) { ok[i] = false; if (status) status[i] = code; } return code; };
+    auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
     if (device && (prep_form < 0 || prep_form > 2)) return refuse(KZG355_BADARGS);
     if (npg == 0) {                                               // verify_cell_kzg_proof_batch of no cells: true
         for (size_t i = 0; i < groups; i++) { ok[i] = true; if (status) status[i] = KZG355_OK; }
@@ -508,7 +475,7 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
     if (!commitments || !cell_indices || !cells || !proofs) return refuse(KZG355_BADARGS);
     if (device && (((uintptr_t)commitments & 15) || ((uintptr_t)cells & 15) || ((uintptr_t)proofs & 15) || ((uintptr_t)cell_indices & 7)))
         return refuse(KZG355_BADARGS);
-    if (npg > CELL_MAX_CELLS || groups > CELL_MAX_CELLS || npg * groups > CELL_MAX_CELLS) return refuse(KZG355_BADARGS);
+    if (out_of_range(npg, groups, CELL_MAX_CELLS)) return refuse(KZG355_BADARGS);
     if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
     // device-resident arrays live on the handle's first device and stay there
     if (cs->multi && !device) return cell_multi(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs);

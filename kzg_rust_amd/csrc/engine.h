@@ -1,12 +1,16 @@
 // engine.h -- the host side of libkzg355.so behind its C ABI (include/kzg355.h): per-call workspaces, the settings handle, and the
 // functions the translation units of the host code share.  Round 5 cut the single 2,200-line api.hip into
-//   workspace.hip      workspace pool, side streams, dispatch helpers
+//   workspace.hip      workspace pool, side streams, dispatch helpers, the launch-set frame (declared below: begin / results back / wait / read)
 //   verify_stages.hip  stage 1 / stage 2 of verification, launch sets, the device-resident call
 //   msm_ops.hip        the fixed-base MSM table and the commitment / proof chains
-//   host_pipeline.hip  host buffers -> chunks -> workspaces (H2D / kernels / results overlapped)
+//   host_pipeline.hip  host buffers -> chunks -> workspaces (H2D / kernels / results overlapped), the dispatch of the *_many host-buffer calls
 //   options.hip        kzg355_options, loading a handle on one device, the load-time self-test, getters / setters
-//   multi_device.hip   handles over several devices: replicas, the RCCL binding, the record exchange
+//   multi_device.hip   handles over several devices: replicas, the RCCL binding, the replica fan-out, the record exchange
 //   entry_points.hip   the C entry points: submit / collect, device-resident and host-buffer calls
+// and the EIP-7594 cell calls have come since, one file per call:
+//   cells.hip          verify_cell_kzg_proof_batch: host preparation, the launch set, a group cut over several devices
+//   cell_compute.hip   compute_cells_and_kzg_proofs: the setups, the chunk loop the recover call shares
+//   cell_recover.hip   recover_cells_and_kzg_proofs: index sets, the erasure decoding's field stage
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
 // entry point returns KZG355_NO_DEVICE (a HIP call that fails on a device that exists: KZG355_DEVICE_ERROR).
@@ -274,6 +278,17 @@ struct WsGuard {
     }
     ~WsGuard() { if (w) { w->quiesce(); ws_release(s, w); } }     // (scope is destroyed after this body: the device goes back last)
 };
+// the workspaces of a call that takes several; released last to first
+struct GuardList : std::vector<std::unique_ptr<WsGuard>> {
+    Workspace *add(const kzg355_settings *cs) { emplace_back(new WsGuard(cs)); return back()->w; }      // (null: no workspace on that device)
+    ~GuardList() { while (!empty()) pop_back(); }
+};
+// counts a call among the handle's calls in flight (ensure_side2 and the point kernels look at the count) from enter() to the end of its scope
+struct InFlight {
+    std::atomic<int> *n = nullptr;
+    void enter(std::atomic<int> &c) { n = &c; c++; }
+    ~InFlight() { if (n) (*n)--; }
+};
 
 // Optional per-kernel-family timing with HIP events on the launch stream (kzg355_set_kernel_timing).
 struct Timed {
@@ -341,15 +356,16 @@ struct HostFront {
 //                     Measured slower here (300 k against 395 k blobs/s on an 8 GiB call): the CPU copy and the DMA compete
 //                     for host memory bandwidth; kept for hosts where page locking is expensive.
 // Results are collected in chunk order; a failure waits for everything in flight before the workspaces go back to the pool.
+// HC_PROOF_AT_Z: a proof at a given z per blob (compute_kzg_proof: `commitments` is null, zs / ys_out set)
+enum HostKind { HC_VERIFY = 0, HC_COMMIT = 1, HC_BLOB_PROOF = 2, HC_PROOF_AT_Z = 3 };
 struct HostCall {
-    // 0 verify, 1 commit, 2 blob proof, 3 proof at a given z per blob (compute_kzg_proof: `commitments` is null, zs / ys_out set)
-    int kind;
+    HostKind kind;
     const uint8_t *blobs, *commitments, *proofs;
     size_t npg;                      // blobs per unit
     bool *ok; uint8_t *out48; int *status;
     uint8_t *records_out = nullptr;  // verify, single-chunk calls only (kzg355_debug_verify_host_records): the stage-1 records, copied back after the chunk
-    const uint8_t *zs = nullptr;     // kind 3: units x 32 bytes, the evaluation points (kzg.rs:446-457)
-    uint8_t *ys_out = nullptr;       // kind 3: units x 32 bytes, y = p(z) of every unit whose status is OK
+    const uint8_t *zs = nullptr;     // HC_PROOF_AT_Z: units x 32 bytes, the evaluation points (kzg.rs:446-457)
+    uint8_t *ys_out = nullptr;       // HC_PROOF_AT_Z: units x 32 bytes, y = p(z) of every unit whose status is OK
 };
 
 // the G1 generator, compressed: what every setup's derived points are checked against (the load-time self-test, the cell setups)
@@ -361,12 +377,38 @@ static const uint8_t G1_GEN[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x9
 extern thread_local bool tl_msm_inner;      // this thread is inside the table build (or the load-time self-test): its MSM calls take the handle as it is
 extern thread_local const kzg355_settings::WidePub *tl_wide_candidate;   // ... and, while the builder checks it, the table that is not published yet
 extern thread_local bool tl_force_bucket;   // the load-time self-test's second opinion: the bucket form although a table is published
-Workspace *ws_acquire(kzg355_settings *s);
-void ws_release(kzg355_settings *s, Workspace *w);
 bool ensure_side(kzg355_settings *s, Workspace *w);
 bool ensure_side2(kzg355_settings *s, Workspace *w);
 int lincomb_form(const kzg355_settings *s, int npg, int groups);
 int status_from_err(int err);
+// what an entry point accepts: each factor first, so that the product cannot wrap
+static const size_t MAX_BLOBS = (size_t)1 << 24, MAX_MSM_BLOBS = (size_t)1 << 20;
+inline bool out_of_range(size_t n, size_t groups, size_t limit) { return n > limit || groups > limit || n * groups > limit; }
+// a return that is a failure of the call (no device, no memory, a HIP error) and not the first non-OK status of its units
+inline bool call_failed(int rc) { return rc >= KZG355_NO_DEVICE; }
+// a call refused as a whole: every unit gets the code the call returns (and, with `ok`, a false verdict), so that a caller that reads per-unit
+// statuses cannot mistake it for success
+int refuse_call(int *status, size_t units, int code, bool *ok = nullptr);
+// ---- the launch-set frame (workspace.hip): what every launch set does around its own kernels, each step written once
+// begin: reserves the per-unit result words (err and h_err; with_ok: ok and h_ok too; res_cap: the pinned ones sized for several sets parked on one
+// workspace), THEN marks the workspace in flight -- from there a failing call has to drain its streams (quiesce()) -- and clears err
+int launch_set_begin(Workspace *w, size_t units, bool with_ok = false, size_t res_cap = 0);
+// queues the words' way back, to entry res_off of the pinned buffers
+int launch_set_results(Workspace *w, size_t units, bool with_ok = false, size_t res_off = 0);
+int launch_set_wait(Workspace *w, Timed &tm);
+// after the wait: the statuses of `units` units from the words at res_off, into status (or null); returns the first that is not OK.  unit(i, st) is
+// the site's own part: it may replace st (a finding the host made on its own) and takes unit i's results when st is OK
+template <class F> int launch_set_read(Workspace *w, size_t units, int *status, size_t res_off, F &&unit) {
+    int first = KZG355_OK;
+    for (size_t i = 0; i < units; i++) {
+        int st = status_from_err(w->h_err.as<int>()[res_off + i]);
+        unit(i, st);
+        if (status) status[i] = st;
+        if (st != KZG355_OK && first == KZG355_OK) first = st;
+    }
+    return first;
+}
+inline int launch_set_read(Workspace *w, size_t units, int *status) { return launch_set_read(w, units, status, 0, [](size_t, int &) {}); }
 int host_hash_from_device(kzg355_settings *s, Workspace *w, HostFront *hf, const uint8_t *d_blobs);
 int enqueue_points_beside(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_c, const uint8_t *d_p, int n_total, int npg, G1Affine *d_pts,
                           int *d_err, bool allow_preshift, int stride = 48 /* bytes between consecutive inputs: 48 packed, 160 inside records */);
@@ -385,6 +427,8 @@ int verify_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d
                    size_t res_off = 0, size_t res_cap = 0, HostFront *hf = nullptr, bool lone_call = false);
 int verify_collect(Workspace *w, Timed &tm, bool *ok, int *status, int G, size_t res_off = 0);
 bool device_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs);
+bool host_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs);
+HostFront *resident_front(kzg355_settings *s, HostFront &hf, const uint8_t *d_commitments, size_t n_blobs, InFlight *count = nullptr);
 int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, size_t npg, size_t groups,
                             const kzg355_settings *cs);
 int ensure_wide_table(kzg355_settings *s);
@@ -399,12 +443,13 @@ int msm_op_many_device_impl(uint8_t *out, int *status, const uint8_t *d_blobs, c
                             const uint8_t *d_zs = nullptr, uint8_t *ys_out = nullptr);
 int stage_to_device(Workspace *w, DevBuf &dst, const uint8_t *src, size_t bytes);
 int stage_via_pinned(kzg355_settings *s, Workspace *w, PinBuf &pin, size_t pin_off, DevBuf &dst, const uint8_t *src, size_t bytes);
+HostCall host_call_range(const HostCall &hc, size_t blob_bytes, size_t u0);
 int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs);
+int host_many(const HostCall &hc, size_t units, const kzg355_settings *cs);
 // cell_compute.hip: the monomial points of the cell setups (also cells.hip), and what compute_cells_and_kzg_proofs and
 // recover_cells_and_kzg_proofs (cell_recover.hip: its own field stage) share
 static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
 int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
-int cc_refuse(int *status, size_t units, int code);
 int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
@@ -467,9 +512,8 @@ std::vector<int> env_device_list();      // KZG355_DEVICES=0,1,...: the device l
 int load_on_device(const uint8_t *g1_bytes, size_t n1, const uint8_t *g2_bytes, size_t n2, int dev_or_minus1, const kzg355_options &opt, kzg355_settings **out);
 void free_single(kzg355_settings *s);
 std::vector<kzg355_settings *> replicas_of(kzg355_settings *s);
-int single_verify_many(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,
-                       const kzg355_settings *cs);
-int fan_out(size_t D, size_t units, const std::function<int(size_t, size_t, size_t)> &fn);
+int fan_out(const kzg355_settings *cs, size_t D, size_t units, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
+int fan_out_guards(const GuardList &gs, size_t tasks, const std::function<int(size_t)> &fn);
 int multi_verify_sharded(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,
                          const kzg355_settings *cs, uint8_t *dump = nullptr);
 int multi_verify_many(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,

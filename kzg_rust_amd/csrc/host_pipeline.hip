@@ -21,9 +21,34 @@ int stage_via_pinned(kzg355_settings *s, Workspace *w, PinBuf &pin, size_t pin_o
     return KZG355_OK;
 }
 
+// the call for units u0 onwards: every array moved on by its own stride
+HostCall host_call_range(const HostCall &hc, size_t blob_bytes, size_t u0) {
+    HostCall r = hc;
+    const size_t b0 = u0 * hc.npg;
+    r.blobs += blob_bytes * b0;
+    if (hc.commitments) r.commitments += 48 * b0;
+    if (hc.proofs) r.proofs += 48 * b0;
+    if (hc.zs) r.zs += 32 * b0;
+    if (hc.ok) r.ok += u0;
+    if (hc.out48) r.out48 += 48 * u0;
+    if (hc.ys_out) r.ys_out += 32 * u0;
+    if (hc.status) r.status += u0;
+    if (hc.records_out) r.records_out += (size_t)RECORD_BYTES * b0;
+    return r;
+}
+
+// The *_many host-buffer calls: independent units in contiguous ranges over the replicas of a handle over several devices, each range through the
+// pipeline below on its replica's own host thread, with no exchange at all; else the pipeline on this handle.
+int host_many(const HostCall &hc, size_t units, const kzg355_settings *cs) {
+    const size_t D = cs->multi ? cs->multi->rep.size() : 1, BB = blob_bytes_of(cs);
+    if (D == 1 || units < D) return host_pipeline(hc, units, cs);
+    return fan_out(cs, D, units, [&](const kzg355_settings *rep, size_t u0, size_t cnt) { return host_pipeline(host_call_range(hc, BB, u0), cnt, rep); });
+}
+
 int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs) {
     kzg355_settings *s = const_cast<kzg355_settings *>(cs);
-    struct InFlight { std::atomic<int> &n; InFlight(std::atomic<int> &c) : n(c) { n++; } ~InFlight() { n--; } } in_flight(s->calls_in_flight);
+    InFlight in_flight;
+    in_flight.enter(s->calls_in_flight);
     const size_t BB = blob_bytes_of(cs);
     const size_t unit_bytes = BB * hc.npg;
     size_t upc = s->chunk_bytes / unit_bytes;                                       // units per full-size chunk
@@ -46,16 +71,12 @@ int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs) {
     // a call that fits one small chunk (a single 64-blob batch is 8 MiB) goes straight from caller memory: the runtime's own
     // staged copy moves it at link speed (measured 52 GB/s for 8 MiB), one pass over the bytes instead of two
     const bool direct = !s->pinned_ring || (nchunks == 1 && unit_bytes * units <= ((size_t)32 << 20));
-    // Fiat-Shamir challenges hashed on the host (host_sha256.h): single-chunk verify / blob-proof calls of the mainnet preset, up to the
-    // measured crossover (the device hash is a 3.7 ms chain for ANY call of up to 32,768 blobs; T host threads take ~35 us x blobs / T)
-    const bool host_hash = nchunks == 1 && (hc.kind == 0 || hc.kind == 2) && !is_small(cs) && s->host_pool &&
-                           (s->host_hash > 0 || (s->host_hash == 0 && units * hc.npg <= (size_t)s->host_hash_max));
-    std::vector<WsGuard *> guards;
-    struct Cleanup { std::vector<WsGuard *> &g; ~Cleanup() { for (size_t i = g.size(); i-- > 0;) delete g[i]; } } cleanup{guards};
+    // Fiat-Shamir challenges hashed on the host: single-chunk verify / blob-proof calls of the mainnet preset (host_call_hashes_on_host)
+    const bool host_hash = nchunks == 1 && (hc.kind == HC_VERIFY || hc.kind == HC_BLOB_PROOF) && host_call_hashes_on_host(s, units * hc.npg);
+    GuardList guards;
     std::vector<Timed> tms;
     for (int i = 0; i < W; i++) {
-        guards.push_back(new WsGuard(cs));
-        if (!guards.back()->w) return KZG355_NO_DEVICE;
+        if (!guards.add(cs)) return KZG355_NO_DEVICE;
         tms.emplace_back(s, guards.back()->w);
     }
     struct Pending { size_t u0, cnt; };
@@ -64,14 +85,13 @@ int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs) {
     auto collect = [&](int slot) -> int {
         if (!pend[slot].cnt) return KZG355_OK;
         Workspace *w = guards[slot]->w;
-        const size_t u0 = pend[slot].u0, cnt = pend[slot].cnt;
+        const size_t cnt = pend[slot].cnt;
+        const HostCall r = host_call_range(hc, BB, pend[slot].u0);
         pend[slot].cnt = 0;
-        int rc = hc.kind == 0 ? verify_collect(w, tms[slot], hc.ok + u0, hc.status ? hc.status + u0 : nullptr, (int)cnt)
-                              : msm_op_collect(w, tms[slot], hc.out48 + 48 * u0, hc.status ? hc.status + u0 : nullptr, cnt,
-                                      hc.ys_out ? hc.ys_out + 32 * u0 : nullptr);
-        if (hc.records_out && hc.kind == 0 && hipMemcpy(hc.records_out + (size_t)RECORD_BYTES * hc.npg * u0, w->records.p, (size_t)RECORD_BYTES * hc.npg * cnt,
-                hipMemcpyDeviceToHost) != hipSuccess) return KZG355_DEVICE_ERROR;
-        if (rc == KZG355_NO_DEVICE || rc == KZG355_NO_MEMORY || rc == KZG355_DEVICE_ERROR) return rc;
+        int rc = hc.kind == HC_VERIFY ? verify_collect(w, tms[slot], r.ok, r.status, (int)cnt) : msm_op_collect(w, tms[slot], r.out48, r.status, cnt, r.ys_out);
+        if (hc.records_out && hc.kind == HC_VERIFY && hipMemcpy(r.records_out, w->records.p, (size_t)RECORD_BYTES * hc.npg * cnt, hipMemcpyDeviceToHost) !=
+                hipSuccess) return KZG355_DEVICE_ERROR;
+        if (call_failed(rc)) return rc;
         if (rc != KZG355_OK && first == KZG355_OK) first = rc;
         return KZG355_OK;
     };
@@ -90,14 +110,15 @@ int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs) {
         double t0 = now();
         if ((rc = collect(slot))) return rc;                                       // frees this slot's pinned and device buffers
         t_wait += now() - t0; t0 = now();
-        const size_t nb = cnt * hc.npg, off = u0 * hc.npg;
+        const size_t nb = cnt * hc.npg;
+        const HostCall r = host_call_range(hc, BB, u0);                            // this chunk of the call
         HostFront hf;
         if (direct && host_hash) {
             // Small call whose challenges need a hash of every blob (verify, blob proof): the host threads hash while the copies and the
             // point kernels are queued; the blobs themselves go to the device inside the enqueue below, behind the point kernels.
             if ((rc = w->h_digests.ensure(32 * nb)) || (rc = w->digests.ensure(32 * nb)) || (rc = w->blobs.ensure(BB * nb))) return rc;
             uint8_t *dig = w->h_digests.as<uint8_t>();
-            const uint8_t *hb = hc.blobs + BB * off, *hcm = hc.commitments + 48 * off;
+            const uint8_t *hb = r.blobs, *hcm = r.commitments;
             const uint64_t n_fe = (uint64_t)s->t.n_fe; const int impl = s->sha_impl;
             auto job = [=](size_t k) { kzg_host::challenge_digests(dig + 64 * k, hb + BB * 2 * k, BB, hcm + 96 * k, nb - 2 * k < 2 ? nb - 2 * k : 2, n_fe,
                     impl); };
@@ -108,30 +129,31 @@ int host_pipeline(const HostCall &hc, size_t units, const kzg355_settings *cs) {
             }
         }
         if (hf.running) {
-            if ((rc = stage_to_device(w, w->commitments, hc.commitments + 48 * off, 48 * nb))) return rc;
-            if (hc.proofs && (rc = stage_to_device(w, w->proofs, hc.proofs + 48 * off, 48 * nb))) return rc;
+            if ((rc = stage_to_device(w, w->commitments, r.commitments, 48 * nb))) return rc;
+            if (hc.proofs && (rc = stage_to_device(w, w->proofs, r.proofs, 48 * nb))) return rc;
         } else if (direct) {
-            if ((rc = stage_to_device(w, w->blobs, hc.blobs + BB * off, BB * nb))) return rc;
-            if (hc.commitments && (rc = stage_to_device(w, w->commitments, hc.commitments + 48 * off, 48 * nb))) return rc;
-            if (hc.proofs && (rc = stage_to_device(w, w->proofs, hc.proofs + 48 * off, 48 * nb))) return rc;
+            if ((rc = stage_to_device(w, w->blobs, r.blobs, BB * nb))) return rc;
+            if (hc.commitments && (rc = stage_to_device(w, w->commitments, r.commitments, 48 * nb))) return rc;
+            if (hc.proofs && (rc = stage_to_device(w, w->proofs, r.proofs, 48 * nb))) return rc;
         } else {
             if ((rc = w->h_stage.ensure(BB * nb))) return rc;
             if ((rc = w->h_stage_cp.ensure(96 * nb))) return rc;
             if ((rc = w->blobs.ensure(BB * nb))) return rc;
             t_alloc += now() - t0; t0 = now();
             if (dbg) (void)hipEventRecord(dev_ev[3 * k], w->stream);
-            if ((rc = stage_via_pinned(s, w, w->h_stage, 0, w->blobs, hc.blobs + BB * off, BB * nb))) return rc;
+            if ((rc = stage_via_pinned(s, w, w->h_stage, 0, w->blobs, r.blobs, BB * nb))) return rc;
             if (dbg) (void)hipEventRecord(dev_ev[3 * k + 1], w->stream);
-            if (hc.commitments && (rc = stage_via_pinned(s, w, w->h_stage_cp, 0, w->commitments, hc.commitments + 48 * off, 48 * nb))) return rc;
-            if (hc.proofs && (rc = stage_via_pinned(s, w, w->h_stage_cp, 48 * nb, w->proofs, hc.proofs + 48 * off, 48 * nb))) return rc;
+            if (hc.commitments && (rc = stage_via_pinned(s, w, w->h_stage_cp, 0, w->commitments, r.commitments, 48 * nb))) return rc;
+            if (hc.proofs && (rc = stage_via_pinned(s, w, w->h_stage_cp, 48 * nb, w->proofs, r.proofs, 48 * nb))) return rc;
         }
-        if (hc.kind == 3 && (rc = stage_to_device(w, w->small, hc.zs + 32 * off, 32 * nb))) return rc;      // the evaluation points (kzg.rs:446-457)
+        if (hc.kind == HC_PROOF_AT_Z && (rc = stage_to_device(w, w->small, r.zs, 32 * nb))) return rc;      // the evaluation points (kzg.rs:446-457)
         t_stage += now() - t0; t0 = now();
         HostFront *hfp = hf.running ? &hf : nullptr;
-        if (hc.kind == 0) rc = verify_enqueue(s, w, tms[slot], w->blobs.as<uint8_t>(), w->commitments.as<uint8_t>(), w->proofs.as<uint8_t>(), (int)hc.npg,
+        if (hc.kind == HC_VERIFY) rc = verify_enqueue(s, w, tms[slot], w->blobs.as<uint8_t>(), w->commitments.as<uint8_t>(), w->proofs.as<uint8_t>(),
+                (int)hc.npg,
                 (int)cnt, 0, 0, hfp, nchunks == 1);
-        else rc = msm_op_enqueue(s, w, tms[slot], w->blobs.as<uint8_t>(), hc.kind == 2 ? w->commitments.as<uint8_t>() : nullptr, cnt, hfp,
-                hc.kind == 3 ? w->small.as<uint8_t>() : nullptr);
+        else rc = msm_op_enqueue(s, w, tms[slot], w->blobs.as<uint8_t>(), hc.kind == HC_BLOB_PROOF ? w->commitments.as<uint8_t>() : nullptr, cnt, hfp,
+                hc.kind == HC_PROOF_AT_Z ? w->small.as<uint8_t>() : nullptr);
         if (rc) return rc;
         if (dbg && !direct) (void)hipEventRecord(dev_ev[3 * k + 2], w->stream);
         t_enq += now() - t0;

@@ -55,22 +55,36 @@ static int load_devices(const uint8_t *g1_bytes, size_t n1, const uint8_t *g2_by
 
 // ---- multi-device execution of the host-buffer entry points ------------------------------------------------------------
 
-int single_verify_many(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,
-                       const kzg355_settings *cs) {
-    HostCall hc{0, blobs, commitments, proofs, npg, ok, nullptr, status};
-    return host_pipeline(hc, groups, cs);
-}
-
-// contiguous ranges of `units` over D devices; the work of device d is fn(d, first unit, count) on its own host thread
-int fan_out(size_t D, size_t units, const std::function<int(size_t, size_t, size_t)> &fn) {
+// The replica fan-out: every task on a host thread of its own with its replica's device current (KZG355_NO_DEVICE where that fails); all of them
+// are waited for, and the first return that is not OK, in task order, is the call's.
+struct Tasks {
     std::vector<std::future<int>> fut;
+    void start(int device, std::function<int()> task) {
+        fut.push_back(std::async(std::launch::async, [device, task]() -> int { return hipSetDevice(device) != hipSuccess ? KZG355_NO_DEVICE : task(); }));
+    }
+    int join() {
+        int first = KZG355_OK;
+        for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
+        return first;
+    }
+};
+
+// contiguous ranges of `units` over the first D replicas of cs; the work of a replica is fn(its handle, first unit, count)
+int fan_out(const kzg355_settings *cs, size_t D, size_t units, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn) {
+    Tasks tasks;
     for (size_t d = 0; d < D; d++) {
         const size_t lo = units * d / D, hi = units * (d + 1) / D;
-        if (hi > lo) fut.push_back(std::async(std::launch::async, fn, d, lo, hi - lo));
+        const kzg355_settings *rep = cs->multi->rep[d];
+        if (hi > lo) tasks.start(rep->device, [&fn, rep, lo, hi] { return fn(rep, lo, hi - lo); });
     }
-    int first = KZG355_OK;
-    for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
-    return first;
+    return tasks.join();
+}
+
+// fn(t) for t < tasks, task t on the device of the workspace gs[t] that the caller has taken already
+int fan_out_guards(const GuardList &gs, size_t tasks, const std::function<int(size_t)> &fn) {
+    Tasks ts;
+    for (size_t t = 0; t < tasks; t++) ts.start(gs[t]->s->device, [&fn, t] { return fn(t); });
+    return ts.join();
 }
 
 // Fewer batches than devices: every batch is sharded over the devices in contiguous blocks of blobs.
@@ -83,66 +97,52 @@ int multi_verify_sharded(bool *ok, int *status, const uint8_t *blobs, const uint
     DeviceScope keep; keep.hold();               // this thread visits every replica's device below
     std::vector<size_t> cnt(D), off(D);
     for (size_t d = 0; d < D; d++) { off[d] = npg * d / D; cnt[d] = npg * (d + 1) / D - off[d]; }
-    std::vector<WsGuard *> gs(D, nullptr);
-    struct Cleanup { std::vector<WsGuard *> &g; ~Cleanup() { for (size_t i = g.size(); i-- > 0;) delete g[i]; } } cleanup{gs};
+    GuardList gs;
+    for (size_t d = 0; d < D; d++) if (!gs.add(m->rep[d])) return KZG355_NO_DEVICE;
     std::vector<std::vector<int>> st1(D, std::vector<int>(groups, KZG355_OK));
     // stage 1: device d takes blobs [off_d, off_d + cnt_d) of every batch (records in transcript order within the block)
     {
-        std::vector<std::future<int>> fut;
-        for (size_t d = 0; d < D; d++) {
-            gs[d] = new WsGuard(m->rep[d]);
-            if (!gs[d]->w) return KZG355_NO_DEVICE;
-            fut.push_back(std::async(std::launch::async, [&, d]() -> int {
-                kzg355_settings *rs = gs[d]->s; Workspace *w = gs[d]->w;
-                if (hipSetDevice(rs->device) != hipSuccess) return KZG355_NO_DEVICE;
-                const size_t n_loc = cnt[d], n_tot = n_loc * groups;
-                int rc;
-                if ((rc = w->records.ensure((size_t)RECORD_BYTES * (n_tot ? n_tot : 1)))) return rc;
-                if ((rc = w->pts.ensure(sizeof(G1Affine) * 2 * (n_tot ? n_tot : 1)))) return rc;       // the decoded points travel with the records
-                if (n_loc == 0) return KZG355_OK;
-                if ((rc = w->blobs.ensure(BB * n_tot)) || (rc = w->commitments.ensure(48 * n_tot)) || (rc = w->proofs.ensure(48 * n_tot))) return rc;
-                if ((rc = w->err.ensure(sizeof(int) * groups)) || (rc = w->h_err.ensure(sizeof(int) * groups))) return rc;
-                // A small block (BASELINE config 5: 64 blobs per device) has its Fiat-Shamir challenges hashed on this replica's host threads straight
-                // out of the caller's memory while the copies and the point kernels run, as a small single-device call has (host_pipeline.hip): the
-                // device's hash is a 3.7 ms chain whatever the block size.  Job k: the pair of blobs 2p, 2p + 1 of batch g, k = g * pairs + p.
-                HostFront hf;
-                const bool host_hash = !is_small(rs) && rs->host_pool && (rs->host_hash > 0 || (rs->host_hash == 0 && n_tot <= (size_t)rs->host_hash_max));
-                if (host_hash) {
-                    if ((rc = w->h_digests.ensure(32 * n_tot)) || (rc = w->digests.ensure(32 * n_tot))) return rc;
-                    uint8_t *dig = w->h_digests.as<uint8_t>();
-                    const size_t pairs = (n_loc + 1) / 2, o_d = off[d];
-                    const uint64_t n_fe = (uint64_t)rs->t.n_fe; const int impl = rs->sha_impl;
-                    auto job = [=](size_t k) {
-                        const size_t g = k / pairs, p = k % pairs, src = g * npg + o_d + 2 * p;
-                        kzg_host::challenge_digests(dig + 32 * (g * n_loc + 2 * p), blobs + BB * src, BB, commitments + 48 * src,
-                                n_loc - 2 * p < 2 ? n_loc - 2 * p : 2, n_fe, impl);
-                    };
-                    hf.job = rs->host_pool->begin(pairs * groups, job);
-                    hf.pool = rs->host_pool; hf.running = true;
-                    rs->n_host_hashed++;
-                }
-                for (size_t g = 0; g < groups; g++) {
-                    const size_t src = g * npg + off[d], dst = g * n_loc;
-                    HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + BB * dst, blobs + BB * src, BB * n_loc, hipMemcpyHostToDevice, w->stream));
-                    HIPCHK(hipMemcpyAsync(w->commitments.as<uint8_t>() + 48 * dst, commitments + 48 * src, 48 * n_loc, hipMemcpyHostToDevice, w->stream));
-                    HIPCHK(hipMemcpyAsync(w->proofs.as<uint8_t>() + 48 * dst, proofs + 48 * src, 48 * n_loc, hipMemcpyHostToDevice, w->stream));
-                }
-                w->in_flight = true;
-                HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * groups, w->stream));
-                Timed tm(rs, w);
-                if ((rc = run_stage1(rs, w, tm, w->blobs.as<uint8_t>(), w->commitments.as<uint8_t>(), w->proofs.as<uint8_t>(), (int)n_tot, (int)n_loc,
-                                     w->records.as<uint8_t>(), w->pts.as<G1Affine>(), w->err.as<int>(), false, host_hash ? &hf : nullptr))) return rc;
-                if ((rc = join_side(w))) return rc;
-                HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * groups, hipMemcpyDeviceToHost, w->stream));
-                HIPCHK(hipStreamSynchronize(w->stream));
-                w->in_flight = false;
-                tm.collect();
-                for (size_t g = 0; g < groups; g++) st1[d][g] = status_from_err(w->h_err.as<int>()[g]);
-                return KZG355_OK;
-            }));
-        }
-        int first = KZG355_OK;
-        for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
+        const int first = fan_out_guards(gs, D, [&](size_t d) -> int {
+            kzg355_settings *rs = gs[d]->s; Workspace *w = gs[d]->w;
+            const size_t n_loc = cnt[d], n_tot = n_loc * groups;
+            int rc;
+            if ((rc = w->records.ensure((size_t)RECORD_BYTES * (n_tot ? n_tot : 1)))) return rc;
+            if ((rc = w->pts.ensure(sizeof(G1Affine) * 2 * (n_tot ? n_tot : 1)))) return rc;       // the decoded points travel with the records
+            if (n_loc == 0) return KZG355_OK;
+            if ((rc = w->blobs.ensure(BB * n_tot)) || (rc = w->commitments.ensure(48 * n_tot)) || (rc = w->proofs.ensure(48 * n_tot))) return rc;
+            // A small block (BASELINE config 5: 64 blobs per device) has its Fiat-Shamir challenges hashed on this replica's host threads straight
+            // out of the caller's memory while the copies and the point kernels run, as a small single-device call has (host_pipeline.hip): the
+            // device's hash is a 3.7 ms chain whatever the block size.  Job k: the pair of blobs 2p, 2p + 1 of batch g, k = g * pairs + p.
+            HostFront hf;
+            const bool host_hash = host_call_hashes_on_host(rs, n_tot);
+            if (host_hash) {
+                if ((rc = w->h_digests.ensure(32 * n_tot)) || (rc = w->digests.ensure(32 * n_tot))) return rc;
+                uint8_t *dig = w->h_digests.as<uint8_t>();
+                const size_t pairs = (n_loc + 1) / 2, o_d = off[d];
+                const uint64_t n_fe = (uint64_t)rs->t.n_fe; const int impl = rs->sha_impl;
+                auto job = [=](size_t k) {
+                    const size_t g = k / pairs, p = k % pairs, src = g * npg + o_d + 2 * p;
+                    kzg_host::challenge_digests(dig + 32 * (g * n_loc + 2 * p), blobs + BB * src, BB, commitments + 48 * src,
+                            n_loc - 2 * p < 2 ? n_loc - 2 * p : 2, n_fe, impl);
+                };
+                hf.job = rs->host_pool->begin(pairs * groups, job);
+                hf.pool = rs->host_pool; hf.running = true;
+                rs->n_host_hashed++;
+            }
+            if ((rc = launch_set_begin(w, groups))) return rc;            // (in flight before the first copy from caller memory)
+            for (size_t g = 0; g < groups; g++) {
+                const size_t src = g * npg + off[d], dst = g * n_loc;
+                HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + BB * dst, blobs + BB * src, BB * n_loc, hipMemcpyHostToDevice, w->stream));
+                HIPCHK(hipMemcpyAsync(w->commitments.as<uint8_t>() + 48 * dst, commitments + 48 * src, 48 * n_loc, hipMemcpyHostToDevice, w->stream));
+                HIPCHK(hipMemcpyAsync(w->proofs.as<uint8_t>() + 48 * dst, proofs + 48 * src, 48 * n_loc, hipMemcpyHostToDevice, w->stream));
+            }
+            Timed tm(rs, w);
+            if ((rc = run_stage1(rs, w, tm, w->blobs.as<uint8_t>(), w->commitments.as<uint8_t>(), w->proofs.as<uint8_t>(), (int)n_tot, (int)n_loc,
+                                 w->records.as<uint8_t>(), w->pts.as<G1Affine>(), w->err.as<int>(), false, host_hash ? &hf : nullptr))) return rc;
+            if ((rc = join_side(w)) || (rc = launch_set_results(w, groups)) || (rc = launch_set_wait(w, tm))) return rc;
+            launch_set_read(w, groups, st1[d].data());
+            return KZG355_OK;
+        });
         if (first != KZG355_OK) return first;
     }
     // the exchange: ONE all-gather of the records (equal blocks: RCCL over xGMI) or peer copies into the batch's stage-2 device
@@ -168,82 +168,67 @@ int multi_verify_sharded(bool *ok, int *status, const uint8_t *blobs, const uint
     // stage 2: batch g on device g mod D, over the records of all blocks in transcript order
     std::vector<int> rc_dev(D, KZG355_OK);
     {
-        std::vector<std::future<int>> fut;
-        for (size_t t = 0; t < D && t < groups; t++) {
-            fut.push_back(std::async(std::launch::async, [&, t]() -> int {
-                kzg355_settings *rs = gs[t]->s; Workspace *w = gs[t]->w;
-                if (hipSetDevice(rs->device) != hipSuccess) return KZG355_NO_DEVICE;
-                std::vector<size_t> mine;
-                for (size_t g = t; g < groups; g += D) mine.push_back(g);
-                const size_t G = mine.size();
-                int rc;
-                DevBuf &gath = w->q;                                               // the gathered records of this device's batches
-                if ((rc = gath.ensure((size_t)RECORD_BYTES * npg * G))) return rc;
-                for (size_t k = 0; k < G; k++) {
-                    const size_t g = mine[k];
-                    for (size_t d = 0; d < D; d++) {
-                        if (!cnt[d]) continue;
-                        uint8_t *dst = gath.as<uint8_t>() + (size_t)RECORD_BYTES * (k * npg + off[d]);
-                        const size_t bytes = (size_t)RECORD_BYTES * cnt[d];
-                        if (use_rccl) {           // local permute out of the all-gathered [rank][batch][block] layout
-                            const uint8_t *src = w->small.as<uint8_t>() + shard_bytes * d + (size_t)RECORD_BYTES * cnt[d] * g;
-                            HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
-                        } else {
-                            const uint8_t *src = gs[d]->w->records.as<uint8_t>() + (size_t)RECORD_BYTES * cnt[d] * g;
-                            if (gs[d]->s->device == rs->device) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
-                            else HIPCHK(hipMemcpyPeerAsync(dst, rs->device, src, gs[d]->s->device, bytes, w->stream));
-                        }
+        const int first = fan_out_guards(gs, D < groups ? D : groups, [&](size_t t) -> int {
+            kzg355_settings *rs = gs[t]->s; Workspace *w = gs[t]->w;
+            std::vector<size_t> mine;
+            for (size_t g = t; g < groups; g += D) mine.push_back(g);
+            const size_t G = mine.size();
+            int rc;
+            DevBuf &gath = w->q;                                               // the gathered records of this device's batches
+            if ((rc = gath.ensure((size_t)RECORD_BYTES * npg * G))) return rc;
+            for (size_t k = 0; k < G; k++) {
+                const size_t g = mine[k];
+                for (size_t d = 0; d < D; d++) {
+                    if (!cnt[d]) continue;
+                    uint8_t *dst = gath.as<uint8_t>() + (size_t)RECORD_BYTES * (k * npg + off[d]);
+                    const size_t bytes = (size_t)RECORD_BYTES * cnt[d];
+                    if (use_rccl) {           // local permute out of the all-gathered [rank][batch][block] layout
+                        const uint8_t *src = w->small.as<uint8_t>() + shard_bytes * d + (size_t)RECORD_BYTES * cnt[d] * g;
+                        HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
+                    } else {
+                        const uint8_t *src = gs[d]->w->records.as<uint8_t>() + (size_t)RECORD_BYTES * cnt[d] * g;
+                        if (gs[d]->s->device == rs->device) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
+                        else HIPCHK(hipMemcpyPeerAsync(dst, rs->device, src, gs[d]->s->device, bytes, w->stream));
                     }
                 }
-                // the decoded points of every block, into [batch][commitments of all blocks | proofs of all blocks] (the stage-2 layout)
-                DevBuf &gpts = w->partials;
-                if ((rc = gpts.ensure(sizeof(G1Affine) * 2 * npg * G))) return rc;
-                for (size_t k = 0; k < G; k++) {
-                    const size_t g = mine[k];
-                    for (size_t d = 0; d < D; d++) {
-                        if (!cnt[d]) continue;
-                        for (int half = 0; half < 2; half++) {
-                            G1Affine *dst = gpts.as<G1Affine>() + (k * 2 + half) * npg + off[d];
-                            const G1Affine *src = gs[d]->w->pts.as<G1Affine>() + (g * 2 + half) * cnt[d];
-                            const size_t bytes = sizeof(G1Affine) * cnt[d];
-                            if (gs[d]->s->device == rs->device) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
-                            else HIPCHK(hipMemcpyPeerAsync(dst, rs->device, src, gs[d]->s->device, bytes, w->stream));
-                        }
+            }
+            // the decoded points of every block, into [batch][commitments of all blocks | proofs of all blocks] (the stage-2 layout)
+            DevBuf &gpts = w->partials;
+            if ((rc = gpts.ensure(sizeof(G1Affine) * 2 * npg * G))) return rc;
+            for (size_t k = 0; k < G; k++) {
+                const size_t g = mine[k];
+                for (size_t d = 0; d < D; d++) {
+                    if (!cnt[d]) continue;
+                    for (int half = 0; half < 2; half++) {
+                        G1Affine *dst = gpts.as<G1Affine>() + (k * 2 + half) * npg + off[d];
+                        const G1Affine *src = gs[d]->w->pts.as<G1Affine>() + (g * 2 + half) * cnt[d];
+                        const size_t bytes = sizeof(G1Affine) * cnt[d];
+                        if (gs[d]->s->device == rs->device) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, w->stream));
+                        else HIPCHK(hipMemcpyPeerAsync(dst, rs->device, src, gs[d]->s->device, bytes, w->stream));
                     }
                 }
-                if ((rc = w->err.ensure(sizeof(int) * G)) || (rc = w->ok.ensure(sizeof(int) * G))) return rc;
-                if ((rc = w->h_ok.ensure(sizeof(int) * G)) || (rc = w->h_err.ensure(sizeof(int) * G))) return rc;
-                w->in_flight = true;
-                HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * G, w->stream));
-                Timed tm(rs, w);
-                // (lone call: this thread owns the device's share of a synchronous call -- the batch challenge of few records may take its host round trip)
-                if ((rc = run_stage2(rs, w, tm, gath.as<uint8_t>(), (int)npg, (int)G, 0, gpts.as<G1Affine>(), w->err.as<int>(), w->ok.as<int>(),
-                        true))) return rc;
-                if (dump) {
-                    if ((rc = w->out48.ensure(128 * G)) || (rc = w->h_out.ensure(128 * G))) return rc;
-                    launch_dump_intermediates(w->scal_a.as<uint32_t>(), w->pair_pts.as<PairPt>(), (int)npg, (int)G, w->out48.as<uint8_t>(), w->stream);
-                    HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 128 * G, hipMemcpyDeviceToHost, w->stream));
-                }
-                HIPCHK(hipMemcpyAsync(w->h_ok.p, w->ok.p, sizeof(int) * G, hipMemcpyDeviceToHost, w->stream));
-                HIPCHK(hipMemcpyAsync(w->h_err.p, w->err.p, sizeof(int) * G, hipMemcpyDeviceToHost, w->stream));
-                HIPCHK(hipStreamSynchronize(w->stream));
-                w->in_flight = false;
-                tm.collect();
-                for (size_t k = 0; k < G; k++) {
-                    const size_t g = mine[k];
-                    if (dump) memcpy(dump + 128 * g, w->h_out.as<uint8_t>() + 128 * k, 128);
-                    int st = status_from_err(w->h_err.as<int>()[k]);
-                    // an Err on any block is an Err of the batch (the `?`s of kzg.rs:673-682)
-                    for (size_t d = 0; d < D; d++) if (st == KZG355_OK) st = st1[d][g];
-                    if (status) status[g] = st;
-                    if (st == KZG355_OK) ok[g] = w->h_ok.as<int>()[k] != 0;
-                    else if (rc_dev[t] == KZG355_OK) rc_dev[t] = st;
-                }
-                return KZG355_OK;
-            }));
-        }
-        int first = KZG355_OK;
-        for (auto &f : fut) { const int rc = f.get(); if (rc != KZG355_OK && first == KZG355_OK) first = rc; }
+            }
+            if ((rc = launch_set_begin(w, G, true))) return rc;
+            Timed tm(rs, w);
+            // (lone call: this thread owns the device's share of a synchronous call -- the batch challenge of few records may take its host round trip)
+            if ((rc = run_stage2(rs, w, tm, gath.as<uint8_t>(), (int)npg, (int)G, 0, gpts.as<G1Affine>(), w->err.as<int>(), w->ok.as<int>(),
+                    true))) return rc;
+            if (dump) {
+                if ((rc = w->out48.ensure(128 * G)) || (rc = w->h_out.ensure(128 * G))) return rc;
+                launch_dump_intermediates(w->scal_a.as<uint32_t>(), w->pair_pts.as<PairPt>(), (int)npg, (int)G, w->out48.as<uint8_t>(), w->stream);
+                HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 128 * G, hipMemcpyDeviceToHost, w->stream));
+            }
+            if ((rc = launch_set_results(w, G, true)) || (rc = launch_set_wait(w, tm))) return rc;
+            rc_dev[t] = launch_set_read(w, G, nullptr, 0, [&](size_t k, int &st) {      // (this device's batches are not neighbours in status[])
+                const size_t g = mine[k];
+                if (dump) memcpy(dump + 128 * g, w->h_out.as<uint8_t>() + 128 * k, 128);
+                // an Err on any block is an Err of the batch (the `?`s of kzg.rs:673-682)
+                for (size_t d = 0; d < D; d++) if (st == KZG355_OK) st = st1[d][g];
+                if (status) status[g] = st;
+                if (st == KZG355_OK) ok[g] = w->h_ok.as<int>()[k] != 0;
+            });
+            return KZG355_OK;
+        });
         if (first != KZG355_OK) return first;
     }
     for (size_t g = 0; g < groups; g++) {            // first failing batch in batch order
@@ -258,16 +243,10 @@ int multi_verify_sharded(bool *ok, int *status, const uint8_t *blobs, const uint
 int multi_verify_many(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,
                       const kzg355_settings *cs) {
     MultiDev *m = cs->multi;
-    const size_t D = m->rep.size(), BB = blob_bytes_of(cs);
+    const size_t D = m->rep.size();
     const bool force_sharded = cs->force_sharded && npg >= D;         // (test hook: kzg355_options.force_sharded)
     // enough independent batches (or batches too small to cut): ranges of batches, no exchange
-    if (!force_sharded && (groups >= D || npg < 2 * D)) {
-        return fan_out(D, groups, [&](size_t d, size_t g0, size_t n) -> int {
-            if (hipSetDevice(m->rep[d]->device) != hipSuccess) return KZG355_NO_DEVICE;
-            return single_verify_many(ok + g0, status ? status + g0 : nullptr, blobs + BB * npg * g0, commitments + 48 * npg * g0, proofs + 48 * npg * g0, npg,
-                    n, m->rep[d]);
-        });
-    }
+    if (!force_sharded && (groups >= D || npg < 2 * D)) return host_many(HostCall{HC_VERIFY, blobs, commitments, proofs, npg, ok, nullptr, status}, groups, cs);
     return multi_verify_sharded(ok, status, blobs, commitments, proofs, npg, groups, cs);
 }
 

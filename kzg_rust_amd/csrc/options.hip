@@ -182,7 +182,7 @@ static int device_self_test(kzg355_settings *s) {
     if (hipDeviceSynchronize() != hipSuccess) { blobs.release(); return KZG355_DEVICE_ERROR; }
     uint8_t c[96]; int st[2] = {0, 0};
     rc = msm_op_many_device_impl(c, st, blobs.as<uint8_t>(), nullptr, 2, s);
-    if (rc == KZG355_NO_DEVICE || rc == KZG355_NO_MEMORY || rc == KZG355_DEVICE_ERROR) { blobs.release(); return rc; }
+    if (call_failed(rc)) { blobs.release(); return rc; }
     if (rc != KZG355_OK) return fail("commitment kernels report an error on canonical blobs");
     if (memcmp(c, G1_GEN, 48) != 0) {
         // Either the arithmetic is wrong or the caller's points are not a Lagrange basis of this domain (the reference loads any
@@ -226,7 +226,7 @@ static int device_self_test(kzg355_settings *s) {
         bool oks[2] = {false, true}; int sts[2] = {0, 0};
         rc = verify_many_device_impl(oks, sts, bb.as<uint8_t>(), cc.as<uint8_t>(), pp.as<uint8_t>(), n, G, s);
         s->lincomb_mode = keep_mode; s->lc_chain_from = keep_chain; s->rhash_lanes_from = keep_lanes;
-        if (rc == KZG355_NO_DEVICE || rc == KZG355_NO_MEMORY || rc == KZG355_DEVICE_ERROR) return done(rc);
+        if (call_failed(rc)) return done(rc);
         bb.release(); cc.release(); pp.release();
         if (rc != KZG355_OK || !oks[0] || oks[1]) return fail("verify_blob_kzg_proof_batch through the many-batch kernels: expected (true, false)");
     }

@@ -249,15 +249,9 @@ int verify_enqueue_stage1(kzg355_settings *s, Workspace *w, Timed &tm, const uin
                           size_t res_cap, HostFront *hf, const std::function<int()> *after_challenge) {
     const int n_total = npg * G;
     int rc;
-    if (res_cap < (size_t)G) res_cap = (size_t)G;
     if ((rc = w->records.ensure((size_t)RECORD_BYTES * n_total))) return rc;
     if ((rc = w->pts.ensure(sizeof(G1Affine) * 2 * (size_t)n_total))) return rc;
-    if ((rc = w->err.ensure(sizeof(int) * (size_t)G))) return rc;
-    if ((rc = w->ok.ensure(sizeof(int) * (size_t)G))) return rc;
-    if ((rc = w->h_ok.ensure(sizeof(int) * res_cap))) return rc;
-    if ((rc = w->h_err.ensure(sizeof(int) * res_cap))) return rc;
-    w->in_flight = true;
-    HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * (size_t)G, w->stream));
+    if ((rc = launch_set_begin(w, (size_t)G, true, res_cap))) return rc;
     return run_stage1(s, w, tm, d_blobs, d_c, d_p, n_total, npg, w->records.as<uint8_t>(), w->pts.as<G1Affine>(), w->err.as<int>(), true, hf, after_challenge);
 }
 
@@ -265,9 +259,7 @@ int verify_enqueue_stage2(kzg355_settings *s, Workspace *w, Timed &tm, int npg, 
     int rc;
     if ((rc = run_stage2(s, w, tm, w->records.as<uint8_t>(), npg, G, 0, w->pts.as<G1Affine>(), w->err.as<int>(), w->ok.as<int>(), lone_call))) return rc;
     if ((rc = join_side(w))) return rc;                           // the subgroup verdicts, before the error words go back
-    HIPCHK(hipMemcpyAsync(w->h_ok.as<int>() + res_off, w->ok.p, sizeof(int) * (size_t)G, hipMemcpyDeviceToHost, w->stream));
-    HIPCHK(hipMemcpyAsync(w->h_err.as<int>() + res_off, w->err.p, sizeof(int) * (size_t)G, hipMemcpyDeviceToHost, w->stream));
-    return KZG355_OK;
+    return launch_set_results(w, (size_t)G, true, res_off);
 }
 
 int verify_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, int npg, int G,
@@ -279,17 +271,15 @@ int verify_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d
 
 // ... and wait for it: verdicts / statuses of its G batches.  Returns the first non-OK status.
 int verify_collect(Workspace *w, Timed &tm, bool *ok, int *status, int G, size_t res_off) {
-    HIPCHK(hipStreamSynchronize(w->stream));
-    w->in_flight = false;
-    tm.collect();
-    int first = KZG355_OK;
-    for (int i = 0; i < G; i++) {
-        int st = status_from_err(w->h_err.as<int>()[res_off + i]);
-        if (status) status[i] = st;
-        if (st == KZG355_OK) ok[i] = w->h_ok.as<int>()[res_off + i] != 0;
-        else if (first == KZG355_OK) first = st;
-    }
-    return first;
+    const int rc = launch_set_wait(w, tm);
+    if (rc) return rc;
+    return launch_set_read(w, (size_t)G, status, res_off, [&](size_t i, int &st) { if (st == KZG355_OK) ok[i] = w->h_ok.as<int>()[res_off + i] != 0; });
+}
+
+// Fiat-Shamir challenges of a host-buffer call hashed on the host threads (host_sha256.h), up to the measured crossover: the device hash is a 3.7 ms
+// chain for ANY call of up to 32,768 blobs; T host threads take ~35 us x blobs / T
+bool host_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs) {
+    return !is_small(s) && s->host_pool && (s->host_hash > 0 || (s->host_hash == 0 && n_blobs <= (size_t)s->host_hash_max));
 }
 
 // a device-resident call small enough that bringing its blobs back and hashing them on the host threads beats the device's 3.7 ms hash chain; not while
@@ -298,6 +288,13 @@ bool device_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs) {
     if (tl_msm_inner) return false;                               // the load-time self-test checks the DEVICE kernels: its calls keep the device hash
     return !is_small(s) && s->host_pool && s->host_hash >= 0 && s->host_hash_device_max > 0 && n_blobs <= (size_t)s->host_hash_device_max &&
            s->tickets_out.load() == 0;
+}
+// ... and the front of such a call (null: the device hashes).  count (or null): the call counts among the handle's calls in flight while it runs
+HostFront *resident_front(kzg355_settings *s, HostFront &hf, const uint8_t *d_commitments, size_t n_blobs, InFlight *count) {
+    if (!device_call_hashes_on_host(s, n_blobs)) return nullptr;
+    hf.from_device = true; hf.d_commitments = d_commitments; hf.n_blobs = n_blobs;
+    if (count) count->enter(s->calls_in_flight);
+    return &hf;
 }
 
 int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, size_t npg, size_t groups,
@@ -308,7 +305,7 @@ int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const
         for (size_t g = 0; g < groups; g++) { ok[g] = true; if (status) status[g] = KZG355_OK; }
         return KZG355_OK;
     }
-    if (npg > (size_t)1 << 24 || groups > (size_t)1 << 24 || npg * groups > (size_t)1 << 24) return KZG355_BADARGS;
+    if (out_of_range(npg, groups, MAX_BLOBS)) return KZG355_BADARGS;
     // 16-byte loads of the blobs
     if (!d_blobs || !d_c || !d_p || ((uintptr_t)d_blobs & 15) || ((uintptr_t)d_c & 3) || ((uintptr_t)d_p & 3)) return KZG355_BADARGS;
     // Optional (KZG355_SPLIT=parts[,streams]): cut the call into `parts` launch sets dealt round-robin to `streams` workspaces, so
@@ -326,19 +323,15 @@ int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const
         if (!g.w) return KZG355_NO_DEVICE;
         Timed tm(g.s, g.w);
         HostFront hf;
-        const bool via_host = device_call_hashes_on_host(g.s, npg * groups);
-        struct InFlight { std::atomic<int> *n; ~InFlight() { if (n) (*n)--; } } in_flight{nullptr};
-        if (via_host) { hf.from_device = true; hf.d_commitments = d_c; hf.n_blobs = npg * groups; g.s->calls_in_flight++; in_flight.n = &g.s->calls_in_flight; }
-        int rc = verify_enqueue(g.s, g.w, tm, d_blobs, d_c, d_p, (int)npg, (int)groups, 0, 0, via_host ? &hf : nullptr, true);
+        InFlight in_flight;
+        int rc = verify_enqueue(g.s, g.w, tm, d_blobs, d_c, d_p, (int)npg, (int)groups, 0, 0, resident_front(g.s, hf, d_c, npg * groups, &in_flight), true);
         if (rc) return rc;
         return verify_collect(g.w, tm, ok, status, (int)groups);
     }
-    std::vector<WsGuard *> gs;
-    struct Cleanup { std::vector<WsGuard *> &g; ~Cleanup() { for (size_t i = g.size(); i-- > 0;) delete g[i]; } } cleanup{gs};
+    GuardList gs;
     std::vector<Timed> tms;
     for (size_t l = 0; l < lanes; l++) {
-        gs.push_back(new WsGuard(cs));
-        if (!gs.back()->w) return KZG355_NO_DEVICE;
+        if (!gs.add(cs)) return KZG355_NO_DEVICE;
         tms.emplace_back(gs.back()->s, gs.back()->w);
     }
     const size_t BB = blob_bytes_of(cs);
@@ -358,7 +351,7 @@ int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const
     for (size_t k = 0; k < parts; k++) {          // a lane's stream is synchronised once; its sets are then read back in order
         const size_t l = k % lanes, cnt = g0[k + 1] - g0[k];
         const int rc = verify_collect(gs[l]->w, tms[l], ok + g0[k], status ? status + g0[k] : nullptr, (int)cnt, res_off[k]);
-        if (rc == KZG355_NO_DEVICE || rc == KZG355_NO_MEMORY || rc == KZG355_DEVICE_ERROR) return rc;
+        if (call_failed(rc)) return rc;
         if (rc != KZG355_OK && first == KZG355_OK) first = rc;
     }
     return first;

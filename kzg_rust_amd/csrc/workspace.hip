@@ -80,5 +80,38 @@ int status_from_err(int err) {
     return KZG355_BADARGS;   // validate_kzg_g1 / bytes_to_bls_field failures are Error::BadArgs (utils.rs:268, 292, 304)
 }
 
+int refuse_call(int *status, size_t units, int code, bool *ok) {
+    for (size_t i = 0; i < units; i++) {
+        if (ok) ok[i] = false;
+        if (status) status[i] = code;
+    }
+    return code;
+}
+
+// ---- the launch-set frame (engine.h)
+int launch_set_begin(Workspace *w, size_t units, bool with_ok, size_t res_cap) {
+    int rc;
+    if (res_cap < units) res_cap = units;
+    if ((rc = w->err.ensure(sizeof(int) * units))) return rc;
+    if (with_ok && ((rc = w->ok.ensure(sizeof(int) * units)) || (rc = w->h_ok.ensure(sizeof(int) * res_cap)))) return rc;
+    if ((rc = w->h_err.ensure(sizeof(int) * res_cap))) return rc;
+    w->in_flight = true;
+    HIPCHK(hipMemsetAsync(w->err.p, 0, sizeof(int) * units, w->stream));
+    return KZG355_OK;
+}
+
+int launch_set_results(Workspace *w, size_t units, bool with_ok, size_t res_off) {
+    if (with_ok) HIPCHK(hipMemcpyAsync(w->h_ok.as<int>() + res_off, w->ok.p, sizeof(int) * units, hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(hipMemcpyAsync(w->h_err.as<int>() + res_off, w->err.p, sizeof(int) * units, hipMemcpyDeviceToHost, w->stream));
+    return KZG355_OK;
+}
+
+int launch_set_wait(Workspace *w, Timed &tm) {
+    HIPCHK(hipStreamSynchronize(w->stream));
+    w->in_flight = false;
+    tm.collect();
+    return KZG355_OK;
+}
+
 }  // namespace kzg355_impl
 

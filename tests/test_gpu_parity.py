@@ -1131,6 +1131,30 @@ def test_device_entry_points_refuse_misaligned_pointers(kz, settings, random_set
     assert L.kzg355_verify_shard_records_device(rec.data_ptr() + 2, st, tb.data_ptr(), tc.data_ptr(), tp.data_ptr(), n, 1, settings.handle) == 1
 
 
+def test_record_entry_points_mark_every_status_on_a_whole_call_refusal(kz, settings):
+    """A call of the record entry points that is refused as a whole (a misaligned record pointer; n * groups past 2^24, each factor within it)
+    returns BadArgs, gives EVERY batch that status and writes no verdict.  kzg355_verify_blob_kzg_proof_batch_many_device refuses the same
+    arguments without touching the statuses.  Nothing is queued: the buffers are small and never read."""
+    import torch
+    L = kz.kzg.lib(); dev = torch.device("cuda", settings.device)
+    G, SENTINEL, BADARGS = 3, 77, 1
+    buf = torch.zeros(4096, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    p = buf.data_ptr()
+    assert p % 16 == 0
+    for rec, n in ((p + 4, 2), (p, 1 << 23)):
+        for fn in (L.kzg355_verify_records_device, L.kzg355_verify_records_checked_device):
+            ok = (C.c_bool * G)(True, False, True); st = (C.c_int * G)(*[SENTINEL] * G)
+            assert fn(ok, st, rec, n, G, settings.handle) == BADARGS
+            assert list(st) == [BADARGS] * G and list(ok) == [True, False, True]
+        st = (C.c_int * G)(*[SENTINEL] * G)
+        assert L.kzg355_verify_shard_records_device(rec, st, p, p, p, n, G, settings.handle) == BADARGS
+        assert list(st) == [BADARGS] * G
+        ok = (C.c_bool * G)(True, False, True); st = (C.c_int * G)(*[SENTINEL] * G)
+        assert L.kzg355_verify_blob_kzg_proof_batch_many_device(ok, st, rec, p, p, n, G, settings.handle) == BADARGS
+        assert list(st) == [SENTINEL] * G and list(ok) == [True, False, True]
+
+
 def test_many_small_batches_take_the_many_batch_kernels(kz, settings, lincomb_handles, random_set):
     """2100 batches of 8 blobs in one launch set: past the threshold of the lane-per-batch transcript hash (1024) with the default
     handle, and through the single-chain Horner tail (default from 6144 batches) with the handle that pins both thresholds to 1;
