@@ -102,7 +102,8 @@ typedef struct kzg355_options {
                                   device chain): 0 by size, -1 never                                                       KZG355_HOST_RHASH=off */
     int host_rhash_max_records;/* ... up to this many records per call (0 = 1024: one 512-blob batch is a 2.6 ms chain on the device)  KZG355_HOST_RHASH_MAX */
     int challenge_form;        /* device Fiat-Shamir kernel: 0 by size (two-wave form up to 2 workgroups per CU), 1 one wave, 2 two waves   KZG355_CHALLENGE=1w|2w */
-    int lincomb_form;          /* batch linear combination: 0 by size, 1 per-term windows, 2 buckets, 3 pre-shifted        KZG355_LINCOMB=window|bucket|preshift */
+    int lincomb_form;          /* batch linear combination: 0 by size, 1 per-term windows, 2 buckets, 3 pre-shifted,       KZG355_LINCOMB=window|bucket|preshift|bucket_halves
+                                  5 buckets on the scalars' halves even where the validation could supply the quarters' points (A/B runs, tests) */
     int pairing_lane;          /* 1: one-lane pairing kernel (A/B and tests)                                               KZG355_PAIRING=lane */
     int pairing_two_wave_upto; /* batches per launch set up to which a pairing runs its two Miller loops on two waves; 0 = 1 per CU; -1 never  KZG355_PAIRING_2W_UPTO */
     int lc_chain_from;         /* batches from which the bucket form ends in one Horner chain per class; 0 = 4 per CU       KZG355_LC_CHAIN_FROM */

@@ -105,8 +105,9 @@ struct Workspace {
     // words), the decoded points alone (ev_pts; recorded only when they are ready before the verdicts), the window shifts (ev_shift)
     bool side_pending = false, pts_pending = false, shift_pending = false;
     DevBuf blobs, commitments, proofs, records, z, y, pts, scal_a, scal_b, scal_c, pair_pts, pair_f, ok, err, digits, partials, q, out48, small, lc_partials,
-            shifts, digests, zpow, qprep;
+            shifts, digests, zpow, qprep, qpts;
     bool shift_ready = false;        // stage 1 has queued the window shifts of this launch set's points (pre-shifted lincomb)
+    bool q_ready = false;            // the validation of this launch set's points has left their [|x|]P in qpts (quarters form of the bucket lincomb)
     PinBuf h_ok, h_err, h_out, h_digests, h_records, h_rdig;
     PinBuf h_stage, h_stage_cp;      // pinned staging of caller memory (blobs; commitments | proofs): slot of the host pipeline
     hipEvent_t ev[32];
@@ -125,11 +126,11 @@ struct Workspace {
         }
         borrowed[0] = borrowed[1] = nullptr;
         stream = own_stream;
-        in_flight = false; side_pending = false; pts_pending = false; shift_pending = false; shift_ready = false;
+        in_flight = false; side_pending = false; pts_pending = false; shift_pending = false; shift_ready = false; q_ready = false;
     }
     ~Workspace() {
         for (DevBuf *b : {&blobs, &commitments, &proofs, &records, &z, &y, &pts, &scal_a, &scal_b, &scal_c, &pair_pts, &pair_f, &ok, &err, &digits, &partials,
-                &q, &out48, &small, &lc_partials, &shifts, &digests, &zpow, &qprep}) b->release();
+                &q, &out48, &small, &lc_partials, &shifts, &digests, &zpow, &qprep, &qpts}) b->release();
         h_ok.release(); h_err.release(); h_out.release(); h_stage.release(); h_stage_cp.release(); h_digests.release(); h_records.release(); h_rdig.release();
         if (ev_ok) for (auto &e : ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_fork, ev_join, ev_pts, ev_shift, ev_stage, ev_done, ev_fork2}) if (e) (void)hipEventDestroy(e);
@@ -161,7 +162,9 @@ struct kzg355_settings {
     // batches per launch set from which the r-transcripts are hashed one lane per batch (KZG355_RHASH_LANES_FROM); measured: 1024 batches of 512 records 6.75
     // -> 3.47 ms, 8192 of 64: 2.44 -> 0.57 ms
     int rhash_lanes_from = 1024;
-    int lincomb_mode = 0;     // 0 auto, 1 windowed per-term, 2 bucket method, 3 pre-shifted (KZG355_LINCOMB=window|bucket|preshift)
+    // 0 auto, 1 windowed per-term, 2 bucket method, 3 pre-shifted, 5 bucket method on halves whatever is at hand (KZG355_LINCOMB=window|bucket|preshift|
+    // bucket_halves)
+    int lincomb_mode = 0;
     int beside_max_blobs = 16384;  // blobs per launch set up to which the point kernels run on side streams beside the hash chain (64 per CU)
     int cu_count = 256;            // compute units of the device: the thresholds above and below are multiples of it (load_on_device)
     int pairing_two_wave_upto = 256;     // batches per launch set up to which a pairing runs its two Miller loops on two waves (1 per CU)
@@ -322,7 +325,8 @@ inline size_t blob_bytes_of(const kzg355_settings *s) { return (size_t)32 * s->t
 
 // which form the batch linear combination takes (KZG355_LINCOMB pins it: 1 window, 2 bucket, 3 pre-shifted)
 enum { LC_FORM_WINDOW = 1, LC_FORM_BUCKET = 2, LC_FORM_PRESHIFT = 3,
-        LC_FORM_SINGLE = 4 /* one record per batch, many batches: never pinned, chosen by shape */ };
+        LC_FORM_SINGLE = 4 /* one record per batch, many batches: never pinned, chosen by shape */,
+        LC_FORM_BUCKET_HALVES = 5 /* a pin only: lincomb_form() answers LC_FORM_BUCKET, and no launch set asks its validation for the Q's */ };
 
 // ---- stage drivers (all asynchronous on w->stream) -------------------------------------------------
 // Host-hashed challenges of a small host-buffer call (host_sha256.h): a job on the handle's host threads is writing the digests of
@@ -380,6 +384,9 @@ extern thread_local bool tl_force_bucket;   // the load-time self-test's second 
 bool ensure_side(kzg355_settings *s, Workspace *w);
 bool ensure_side2(kzg355_settings *s, Workspace *w);
 int lincomb_form(const kzg355_settings *s, int npg, int groups);
+// The Q = [|x|]P buffer of a launch set whose validation and stage 2 run on this workspace, when that stage 2 will take the bucket form and may split
+// its scalars four ways (null otherwise, or when the buffer cannot be had: stage 2 then keeps the halves).  Sets w->q_ready; run_stage2 consumes it.
+G1Jac *stage2_q_buffer(const kzg355_settings *s, Workspace *w, int npg, int groups);
 int status_from_err(int err);
 // what an entry point accepts: each factor first, so that the product cannot wrap
 static const size_t MAX_BLOBS = (size_t)1 << 24, MAX_MSM_BLOBS = (size_t)1 << 20;

@@ -73,11 +73,13 @@ static int verify_records_impl(bool *ok, int *status, uint8_t *dump, const uint8
     if (dump && ((rc = w->out48.ensure(128 * groups)) || (rc = w->h_out.ensure(128 * groups)))) return rc;
     if ((rc = launch_set_begin(w, groups, true))) return rc;
     Timed tm(s, w);
+    w->q_ready = false;                                           // (trusted records and handed-in points come without the validation's Q's: the halves form)
     if (d_points) {
         // nothing to decode
     } else if (validate) {   // full validate_kzg_g1 on C_i / proof_i (decompression + subgroup test) straight from the records
+        G1Jac *d_q = stage2_q_buffer(s, w, (int)n, G);
         tm.begin("validate_points");
-        launch_validate_points(d_records, d_records + 112, (int)(n * groups), (int)n, w->pts.as<G1Affine>(), w->err.as<int>(), w->stream, RECORD_BYTES);
+        launch_validate_points(d_records, d_records + 112, (int)(n * groups), (int)n, w->pts.as<G1Affine>(), w->err.as<int>(), w->stream, RECORD_BYTES, d_q);
         tm.end();
     } else {
         tm.begin("points_from_records"); launch_points_from_records(d_records, (int)(n * groups), (int)n, w->pts.as<G1Affine>(), w->err.as<int>(), w->stream);

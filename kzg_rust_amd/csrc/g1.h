@@ -383,11 +383,15 @@ KZG_HD bool g1_phi_matches(const G1Affine &p, const G1Jac &t) {
     fp_mul(lhs, p.y, z3); fp_neg(rhs, t.y);            // y Z^3 == -Y
     return fp_eq(lhs, rhs);
 }
-KZG_HD bool g1_in_subgroup(const G1Affine &p) {
+// q (or null): where the first ladder's result [|x|]P goes (canonical Jacobian) -- the second ladder starts from it, so it is at hand for
+// nothing; once the test has passed it is a point of G1, the one the fourth-of-a-scalar split below pairs with P.  Written whatever the
+// verdict: the caller puts the point at infinity there when the test fails.  Not written for P at infinity.
+KZG_HD bool g1_in_subgroup(const G1Affine &p, G1Jac *q = nullptr) {
     if (g1a_is_inf(p)) return true;
     G1Jac pj, t;
     g1_from_affine(pj, p);
     g1_mul_x_abs(t, pj);
+    if (q) *q = t;
     g1_mul_x_abs(t, t);                  // [x^2]P
     return g1_phi_matches(p, t);
 }
@@ -481,6 +485,37 @@ KZG_HD void glv_split_fast(uint32_t a[4], uint32_t b[4], const uint32_t k[8]) {
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) { a[i] = r5[i]; b[i] = q[i]; }
+}
+// The halves split once more, by m = |x| = 0xd201000000010000: r = m^4 - m^2 + 1 < m^4, so every k < r is
+//   k = a0 + a1 m + a2 m^2 + a3 m^3,  0 <= a_j < m < 2^64,   [k]P = [a0]P + [a1]Q + [a2](-phi P) + [a3](-phi Q)  with Q = [m]P
+// (the subgroup test leaves Q, g1_in_subgroup).  v = lo + hi m for v < m^2: v >> 64 < m^2 / 2^64 < m is the remainder the restoring
+// division starts from, 64 steps bring in the low word.  lo, hi: two 32-bit words each.
+KZG_HD void split_by_x_abs(uint32_t lo[2], uint32_t hi[2], const uint32_t v[4]) {
+    const uint64_t m = BLS_X_ABS;
+    uint64_t rem = (uint64_t)v[2] | ((uint64_t)v[3] << 32), low = (uint64_t)v[0] | ((uint64_t)v[1] << 32), quo = 0;
+    for (int i = 0; i < 64; i++) {
+        const uint64_t top = rem >> 63;                           // the 65th bit of 2 rem + bit
+        rem = (rem << 1) | (low >> 63); low <<= 1;
+        const bool ge = top != 0 || rem >= m;
+        rem = ge ? rem - m : rem;
+        quo = (quo << 1) | (ge ? 1u : 0u);
+    }
+    lo[0] = (uint32_t)rem; lo[1] = (uint32_t)(rem >> 32);
+    hi[0] = (uint32_t)quo; hi[1] = (uint32_t)(quo >> 32);
+}
+// a[j] = a_j above, for a canonical scalar k < r (the halves by the Barrett form of the GLV split: k < 2^255; the bit-serial form is two thirds of
+// k_lc_prep's instructions)
+KZG_HD void quarter_split(uint32_t a[4][2], const uint32_t k[8]) {
+    uint32_t lo[4], hi[4];
+    glv_split_fast(lo, hi, k);
+    split_by_x_abs(a[0], a[1], lo);
+    split_by_x_abs(a[2], a[3], hi);
+}
+// [|x|](-G): the Q of the term c (-G)
+KZG_HD G1Affine g1a_neg_gen_x_abs() {
+    const uint32_t gx[NFP] = G1_NEG_GEN_M_X_INIT, gy[NFP] = G1_NEG_GEN_M_Y_INIT;
+    G1Affine r; for (int i = 0; i < NFP; i++) { r.x.l[i] = gx[i]; r.y.l[i] = gy[i]; }
+    return r;
 }
 // -phi(P) = (beta x, -y)
 KZG_HD void g1a_neg_phi(G1Affine &r, const G1Affine &p) {

@@ -9,6 +9,7 @@
 #endif
 #include "kernels.h"
 #include "g1_quad.h"
+#include "lc_forms.h"
 
 namespace kzg {
 
@@ -20,9 +21,11 @@ namespace kzg {
 //                          stride 48: packed arrays; RECORD_BYTES: fields of records.
 //   subgroup_ladder_quad   [x^2] base by a DPP quad: two passes of the 63-step ladder for |x| = 0xd201000000010000, canonical result.  ONE loop with
 //                          one inlined instance of each quad routine; a kernel calls it once.
+//                          qs (SUBGROUP only, or null): a second array in the layout of pts that gets Q = [|x|]P of every point, canonical Jacobian,
+//                          straight out of the subgroup test's first ladder; the point at infinity for a point that is at infinity or failed a check.
 template <bool SUBGROUP>
 __device__ __forceinline__ void decode_point_to_slot(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group, G1Affine *pts, int *err,
-        int stride) {
+        int stride, G1Jac *qs = nullptr) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= 2 * n_total) return;
     const bool is_proof = j >= n_total;
@@ -33,10 +36,12 @@ __device__ __forceinline__ void decode_point_to_slot(const uint8_t *commitments,
     for (int k = 0; k < 48; k++) b[k] = src[k];
     G1Affine p;
     int rc = g1_decompress(p, b);
-    if (SUBGROUP && rc == 0 && !g1a_is_inf(p) && !g1_in_subgroup(p)) rc = 3;     // infinity is accepted (utils.rs:298-301)
     const int g = i / n_per_group, k = i % n_per_group;
+    const size_t slot = (size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k);
+    if (SUBGROUP && rc == 0 && !g1a_is_inf(p) && !g1_in_subgroup(p, qs ? qs + slot : nullptr)) rc = 3;     // infinity is accepted (utils.rs:298-301)
     if (rc != 0) { atomicOr(&err[g], ERR_BAD_POINT); p = g1a_inf(); }
-    if (!SUBGROUP || pts) pts[(size_t)g * 2 * n_per_group + (is_proof ? n_per_group + k : k)] = p;
+    if (!SUBGROUP || pts) pts[slot] = p;
+    if (SUBGROUP && qs && g1a_is_inf(p)) qs[slot] = g1_inf();     // (behind the ladder's own store, if there was one)
 }
 __device__ __forceinline__ G1Jac subgroup_ladder_quad(const G1Jac &start, int role) {
     G1Jac base = start, t = start;
@@ -52,8 +57,40 @@ __device__ __forceinline__ G1Jac subgroup_ladder_quad(const G1Jac &start, int ro
 }
 
 __global__ void __launch_bounds__(256, 2) k_validate_points(const uint8_t *commitments, const uint8_t *proofs, int n_total, int n_per_group,
-                                                         G1Affine *pts, int *err, int stride) {
-    decode_point_to_slot<true>(commitments, proofs, n_total, n_per_group, pts, err, stride);
+                                                         G1Affine *pts, int *err, int stride, G1Jac *qs) {
+    decode_point_to_slot<true>(commitments, proofs, n_total, n_per_group, pts, err, stride, qs);
+}
+// The Q's of k_validate_points made affine in place for the bucket kernel's mixed addition: (X, Y, Z) -> (X / Z^2, Y / Z^3, Z) in the same slot.
+// A lane takes QA_K consecutive slots and pays ONE inversion for them (Montgomery's trick: the running products of the Z's, parked in LDS limb-major,
+// then back down); a Q at infinity stays (0, 0, 0) and takes no part in the products.  ~13 products per point against ~1500 for validating it.
+constexpr int QA_K = 8;
+__global__ void __launch_bounds__(64) k_q_affine(G1Jac *qs, int n_points) {
+    __shared__ uint32_t pre[QA_K][NFP][64];
+    const int lane = threadIdx.x;
+    const size_t first = ((size_t)blockIdx.x * 64 + lane) * QA_K;
+    Fp run = fp_one();
+#pragma unroll 1
+    for (int k = 0; k < QA_K; k++) {
+#pragma unroll
+        for (int i = 0; i < NFP; i++) pre[k][i][lane] = run.l[i];
+        if (first + k < (size_t)n_points) { const Fp z = qs[first + k].z; if (!fp_is_zero(z)) fp_mul(run, run, z); }
+    }
+    Fp inv; fp_inv(inv, run);
+#pragma unroll 1
+    for (int k = QA_K - 1; k >= 0; k--) {
+        if (first + k >= (size_t)n_points) continue;
+        G1Jac *q = qs + first + k;
+        const Fp z = q->z;
+        if (fp_is_zero(z)) continue;
+        Fp p, zi, zi2, zi3, x, y;
+#pragma unroll
+        for (int i = 0; i < NFP; i++) p.l[i] = pre[k][i][lane];
+        fp_mul(zi, inv, p);                                       // 1 / Z_k
+        fp_mul(inv, inv, z);
+        fp_sqr(zi2, zi); fp_mul(zi3, zi2, zi);
+        fp_mul(x, q->x, zi2); fp_mul(y, q->y, zi3);
+        q->x = x; q->y = y;
+    }
 }
 
 // The two halves of k_validate_points as kernels of their own, for the single-proof entry point: the linear combination only needs
@@ -151,7 +188,6 @@ template <int WIDTH, bool XOR> __device__ __forceinline__ G1Jac g1_shfl(const G1
     return r;
 }
 __device__ __forceinline__ G1Jac g1_shfl_xor(const G1Jac &v, int mask) { return g1_shfl<64, true>(v, mask); }
-__device__ __forceinline__ G1Jac g1_shfl_down16(const G1Jac &v, int delta) { return g1_shfl<16, false>(v, delta); }     // within segments of 16 lanes
 __device__ __forceinline__ G1Jac g1_shfl_down_w(const G1Jac &v, int delta) { return g1_shfl<64, false>(v, delta); }
 __device__ __forceinline__ int ps_point_of_item(int j, int n) {
     const int t = j >> 1;
@@ -241,7 +277,7 @@ __global__ void __launch_bounds__(64) k_lincomb_single(const G1Affine *pts, cons
 // ------------------------------------------------------------------------------------------------ lincomb, bucket form
 // Throughput form of the same two sums: a variable-base Pippenger MSM per batch ("the batched G1 MSM" of
 // verify_kzg_proof_batch).  Independent scalar multiplications cost ~1830 field-product equivalents per lane whatever the
-// batch; the bucket method shares the doublings:
+// batch; the bucket method shares the doublings (described in the halves form; what the quarters form changes follows below):
 //   k_lc_prep     one lane per term: GLV split, signed 5-bit recoding of both halves (25 digits in [-16, 15] and an unsigned top
 //                 digit), the two points P and -phi(P)                             -> items[2(3n+1)], digits[item][26]
 //   k_lc_buckets  one 256-thread workgroup per batch, a wave = 13 (window, class) tasks x 16 buckets = 208 lists: LDS counting
@@ -253,45 +289,53 @@ __global__ void __launch_bounds__(64) k_lincomb_single(const G1Affine *pts, cons
 //   Horner chain per class
 // Window width: the bucket kernel's work is (items x windows) additions -- 4-bit digits 11.6 k per 64-blob batch, 5-bit 9.7 k,
 // 6-bit 8.4 k -- while the Horner tail has one chain per bucket index: 16 lanes per class at 5 bits still leave it a
-// latency-bound kernel of ~one wave per SIMD at 2048 batches; at 6 bits it would be as much work as the buckets.
+// latency-bound kernel of ~one wave per SIMD at 2048 batches; at 6 bits -- on halves -- it would be as much work as the buckets.
 // ~2.7x less issue work per batch than the windowed form above; its dependent chain is no shorter (the Horner tail),
 // so it is used when many batches are in flight and the windowed form otherwise.
-constexpr int LC_BITS = 5;
-constexpr int LC_BUCKETS = 1 << (LC_BITS - 1);       // |digit| in 1..16
-constexpr int LC_WINDOWS = 26;                       // 25 signed 5-bit digits + the top digit (3 value bits and the carry)
-constexpr int LC_DIG_STRIDE = 28;
-__host__ __device__ inline int lc_items(int n) { return 2 * (3 * n + 1); }
+// The quarters form (lc_forms.h; taken when stage 2 follows a validation on the same device, whose subgroup test leaves Q = [|x|]P): every scalar in
+// four 64-bit quarters on the items P, Q, -phi P, -phi Q (quarter_split, g1.h) -- half the windows, so the window is 6 bits wide with a tail no
+// larger than before: 8.4 k bucket additions per 64-blob batch, 704 bucket sums in 22 windows and 60 doublings in the chain, against 9.7 k, 832 in 52
+// and 125.  One body per kernel serves both forms (CFG); the pre-shifted form below keeps the halves' constants.
+constexpr int LC_BITS = LcHalves::BITS;
+constexpr int LC_BUCKETS = LcHalves::NB;             // |digit| in 1..16
+constexpr int LC_WINDOWS = LcHalves::WINDOWS;        // 25 signed 5-bit digits + the top digit (3 value bits and the carry)
+constexpr int LC_DIG_STRIDE = LcHalves::DIG_STRIDE;
+__host__ __device__ inline int lc_items(int n) { return lc_items_of<LcHalves>(n); }
 
-__global__ void __launch_bounds__(64) k_lc_prep(const G1Affine *pts, const uint32_t *scal_a, const uint32_t *scal_b, const uint32_t *scal_c, int n,
-                                                 G1Affine *items, int8_t *digits) {
+// qpts (quarters only): the Q's in the layout of pts, affine in the x, y of a Jacobian slot (k_q_affine)
+template <class CFG>
+__device__ __forceinline__ void lc_prep_body(const G1Affine *pts, const G1Jac *qpts, const uint32_t *scal_a, const uint32_t *scal_b, const uint32_t *scal_c,
+                                                 int n, G1Affine *items, int8_t *digits) {
+    constexpr int PT = CFG::PER_TERM;
     const int nt = 3 * n + 1, bpg = (nt + 63) / 64;
     const int g = blockIdx.x / bpg, t = (blockIdx.x % bpg) * 64 + threadIdx.x;
     if (t >= nt) return;
     const G1Affine *gp = pts + (size_t)g * 2 * n;
     G1Affine p; uint32_t k[8];
-    if (t < n) { p = gp[n + t]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + t) + q]; }
-    else if (t < 2 * n) { p = gp[n + (t - n)]; for (int q = 0; q < 8; q++) k[q] = scal_b[8 * ((size_t)g * n + (t - n)) + q]; }
-    else if (t < 3 * n) { p = gp[t - 2 * n]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + (t - 2 * n)) + q]; }
-    else { p = g1a_neg_gen(); for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q]; }
-    uint32_t half[2][4];
-    glv_split(half[0], half[1], k);
-    G1Affine q2; g1a_neg_phi(q2, p);
-    const size_t base = (size_t)g * lc_items(n) + 2 * (size_t)t;
-    items[base] = p; items[base + 1] = q2;
-    // k = sum_w d_w 32^w with d_w = chunk_w(k + BIAS) - 16 for w < 25 and d_25 = the remaining top bits: BIAS has bit 4 of every
-    // 5-bit chunk below the top one set (sum_{w<25} 16 * 32^w)
-    const uint32_t bias[4] = {0x21084210u, 0x08421084u, 0x42108421u, 0x10842108u};
-    for (int h = 0; h < 2; h++) {
-        uint32_t e[6]; uint64_t c = 0;
-        for (int i = 0; i < 4; i++) { c += (uint64_t)half[h][i] + bias[i]; e[i] = (uint32_t)c; c >>= 32; }
-        e[4] = (uint32_t)c; e[5] = 0;
-        int8_t *d = digits + (base + h) * LC_DIG_STRIDE;
-        for (int w = 0; w < LC_WINDOWS; w++) {
-            const int bit = LC_BITS * w;
-            const uint64_t two = (uint64_t)e[bit >> 5] | ((uint64_t)e[(bit >> 5) + 1] << 32);
-            const int chunk = (int)((two >> (bit & 31)) & 31u);
-            d[w] = (int8_t)(w < LC_WINDOWS - 1 ? chunk - 16 : chunk);
-        }
+    int src = -1;                                                 // the point's slot in the batch; -1: -G
+    if (t < n) { src = n + t; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + t) + q]; }
+    else if (t < 2 * n) { src = n + (t - n); for (int q = 0; q < 8; q++) k[q] = scal_b[8 * ((size_t)g * n + (t - n)) + q]; }
+    else if (t < 3 * n) { src = t - 2 * n; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * ((size_t)g * n + (t - 2 * n)) + q]; }
+    else { for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q]; }
+    if (src >= 0) p = gp[src]; else p = g1a_neg_gen();
+    const size_t base = (size_t)g * lc_items_of<CFG>(n) + PT * (size_t)t;
+    if constexpr (PT == 2) {
+        uint32_t half[2][4];
+        glv_split(half[0], half[1], k);
+        G1Affine q2; g1a_neg_phi(q2, p);
+        items[base] = p; items[base + 1] = q2;
+        for (int h = 0; h < 2; h++) lc_recode<CFG>(digits + (base + h) * CFG::DIG_STRIDE, half[h]);
+    } else {
+        uint32_t a[4][2];
+        quarter_split(a, k);
+        G1Affine q;
+        if (src >= 0) { const G1Jac *qs = qpts + (size_t)g * 2 * n + src; q.x = qs->x; q.y = qs->y; } else q = g1a_neg_gen_x_abs();
+        if (g1a_is_inf(p)) q = g1a_inf();                         // (the slot of a point at infinity holds the point at infinity already)
+        G1Affine f; g1a_neg_phi(f, p);
+        items[base] = p; items[base + 2] = f;
+        g1a_neg_phi(f, q);
+        items[base + 1] = q; items[base + 3] = f;
+        for (int h = 0; h < 4; h++) lc_recode<CFG>(digits + (base + h) * CFG::DIG_STRIDE, a[h]);
     }
 }
 
@@ -303,48 +347,48 @@ __global__ void __launch_bounds__(64) k_lc_prep(const G1Affine *pts, const uint3
 // sums B[window][b] are NOT weighted here: since
 //   sum_w 32^w sum_b b B[w][b] = sum_b b ( sum_w 32^w B[w][b] ),
 // the Horner kernel runs one chain per bucket index and applies the weights b once per class.
-constexpr int LC_TASKS = 13;                     // tasks (window x class) per wave: 26 windows x 2 classes over 4 waves
-constexpr int LC_LDS_LIST = 400;                 // LDS list entries per task: 13 x 400 >= 40 n + 14 entries of a wave for n <= 129
+// The tasks of a wave (which windows, classes and parts of the buckets), the LDS list capacity and the slab's stride: lc_forms.h.  Limits, for both
+// forms: a wave holds at most LC_MAXT x 16 = 208 lists (`order` is uint8_t); an item index is 15 bits beside the digit's sign (lc_items_fit: halves
+// n <= 5461, quarters n <= 2730 -- the dispatcher asks for less); the lists are in LDS while lc_max_entries(n) <= 5200: halves 40 n + 14, n <= 129.
 constexpr int LC_MAX_LISTS = 8;                  // lists one lane may be dealt
-__host__ __device__ inline int lc_list_stride(int n) { return 2 * (2 * n + 1) + 2; }
-// wave wid: class 1 (2 (2n+1) items per window) windows [c1w0, c1w0 + n1), class 0 (2n items) windows [c0w0, c0w0 + 13 - n1):
-// 7 + 6, 7 + 6, 6 + 7, 6 + 7 -- within 5 % of each other in additions (whole windows per wave: 7 against 6, 17 %)
-__host__ __device__ inline int lc_wave_n1(int wid) { return wid < 2 ? 7 : 6; }
-__host__ __device__ inline int lc_wave_c1w0(int wid) { return wid < 2 ? 7 * wid : 14 + 6 * (wid - 2); }
-__host__ __device__ inline int lc_wave_c0w0(int wid) { return wid < 2 ? 6 * wid : 12 + 7 * (wid - 2); }
 // A bucket sum's slot in the scratch: the bucket kernel parks the raw (lazy) accumulator there the moment a list ends and turns it
 // into a canonical Jacobian point -- in place, at the start of the slot -- after its loop; the Horner kernel reads the Jacobian point.
 union LcSlot { G1X raw; G1Jac jac; };
 // One 256-thread workgroup per batch -- one wave per SIMD of the CU (one-wave workgroups of long chains get placed unevenly, see
 // k_pairing.hip), each with its own slice of the LDS arrays; the waves only meet at workgroup barriers that all four reach
 // the same number of times.
-__global__ void __launch_bounds__(256) k_lc_buckets(const G1Affine *items, const int8_t *digits, int n, LcSlot *S, uint16_t *glists, int keep_raw) {
-    __shared__ uint16_t lists_all[4][LC_TASKS * LC_LDS_LIST];
-    __shared__ int cnt_all[4][LC_TASKS][LC_BUCKETS + 1], cursor_all[4][LC_TASKS][LC_BUCKETS + 1];
-    __shared__ uint8_t order_all[4][LC_BUCKETS * LC_TASKS];
+template <class CFG>
+__device__ __forceinline__ void lc_buckets_body(const G1Affine *items, const int8_t *digits, int n, LcSlot *S, uint16_t *glists, int keep_raw) {
+    __shared__ uint16_t lists_all[4][LC_MAXT * LC_LDS_LIST];
+    __shared__ int cnt_all[4][LC_MAXT][LC_TB + 1], cursor_all[4][LC_MAXT][LC_TB + 1];
+    __shared__ uint8_t order_all[4][LC_TB * LC_MAXT];
     __shared__ uint8_t seq_all[4][64][LC_MAX_LISTS];
+    constexpr LcDeal deal = LcDealOf<CFG>::value;
     const int g = blockIdx.x, wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n1 = lc_wave_n1(wid), c1w0 = lc_wave_c1w0(wid), c0w0 = lc_wave_c0w0(wid);
-    constexpr int ntasks = LC_TASKS, nlists = LC_BUCKETS * LC_TASKS;
-    int (*cnt)[LC_BUCKETS + 1] = cnt_all[wid], (*cursor)[LC_BUCKETS + 1] = cursor_all[wid];
+    const int ntasks = deal.ntasks[wid], nlists = LC_TB * ntasks;
+    int (*cnt)[LC_TB + 1] = cnt_all[wid], (*cursor)[LC_TB + 1] = cursor_all[wid];
     uint8_t *order = order_all[wid];
     uint8_t (*seq)[LC_MAX_LISTS] = seq_all[wid];
-    const int ni = lc_items(n);
+    const int ni = lc_items_of<CFG>(n), n0 = lc_class_items<CFG>(0, n);
     const G1Affine *it = items + (size_t)g * ni;
-    const int8_t *dg = digits + (size_t)g * ni * LC_DIG_STRIDE;
-    const bool in_lds = 40 * n + 14 <= LC_TASKS * LC_LDS_LIST;
-    // the wave's lists, back to back in the order its lanes walk them (at most 7 * 2 (2n+1) + 6 * 2n = 40 n + 14 entries)
-    uint16_t *lists = in_lds ? lists_all[wid] : glists + ((size_t)blockIdx.x * 4 + wid) * LC_TASKS * lc_list_stride(n);
-    LcSlot *out = S + (size_t)g * 2 * LC_WINDOWS * LC_BUCKETS;      // bucket sums [class][window][bucket - 1]; weighted by the Horner kernel
-    auto task_window = [&](int tk) { return tk < n1 ? c1w0 + tk : c0w0 + (tk - n1); };
-    auto slot_of = [&](int L) { const int tk = L / LC_BUCKETS; return ((tk < n1 ? 1 : 0) * LC_WINDOWS + task_window(tk)) * LC_BUCKETS + (L % LC_BUCKETS); };
-    auto len_of = [&](int L) { return cnt[L / LC_BUCKETS][(L % LC_BUCKETS) + 1]; };
-    for (int q = lane; q < (LC_BUCKETS + 1) * LC_TASKS; q += 64) cnt[q / (LC_BUCKETS + 1)][q % (LC_BUCKETS + 1)] = 0;
+    const int8_t *dg = digits + (size_t)g * ni * CFG::DIG_STRIDE;
+    const bool in_lds = lc_lists_in_lds<CFG>(n);
+    // the wave's lists, back to back in the order its lanes walk them (at most lc_wave_entries(wid, n) entries)
+    uint16_t *lists = in_lds ? lists_all[wid] : glists + ((size_t)blockIdx.x * 4 + wid) * LC_MAXT * lc_list_stride_of<CFG>(n);
+    LcSlot *out = S + (size_t)g * 2 * CFG::WINDOWS * CFG::NB;       // bucket sums [class][window][bucket - 1]; weighted by the Horner kernel
+    auto task_of = [&](int tk) { return (int)deal.task[wid][tk]; };
+    auto slot_of = [&](int L) { const int t = task_of(L / LC_TB);
+            return (lc_task_class(t) * CFG::WINDOWS + lc_task_window(t)) * CFG::NB + lc_task_part(t) * LC_TB + (L % LC_TB); };
+    auto len_of = [&](int L) { return cnt[L / LC_TB][(L % LC_TB) + 1]; };
+    // the bucket of a digit within the task's part: 1 .. 16, or 0 when the digit is zero or belongs to another part
+    auto local_bucket = [&](int d, int part) { const int b = (d < 0 ? -d : d) - part * LC_TB; return b >= 1 && b <= LC_TB ? b : 0; };
+    for (int q = lane; q < (LC_TB + 1) * LC_MAXT; q += 64) cnt[q / (LC_TB + 1)][q % (LC_TB + 1)] = 0;
     __syncthreads();
 #pragma unroll 1
     for (int tk = 0; tk < ntasks; tk++) {
-        const int w = task_window(tk), lo = tk < n1 ? 2 * n : 0, hi = tk < n1 ? ni : 2 * n;      // item range of the task's class (terms t < n are class 0)
-        for (int j = lo + lane; j < hi; j += 64) { const int d = dg[(size_t)j * LC_DIG_STRIDE + w]; if (d) atomicAdd(&cnt[tk][d < 0 ? -d : d], 1); }
+        const int t = task_of(tk), w = lc_task_window(t), part = lc_task_part(t);
+        const int lo = lc_task_class(t) ? n0 : 0, hi = lc_task_class(t) ? ni : n0;      // item range of the task's class (terms t < n are class 0)
+        for (int j = lo + lane; j < hi; j += 64) { const int b = local_bucket(dg[(size_t)j * CFG::DIG_STRIDE + w], part); if (b) atomicAdd(&cnt[tk][b], 1); }
     }
     __syncthreads();
     // rank the lists by length (ties by index): order[rank] = list; an empty list is the point at infinity
@@ -379,15 +423,16 @@ __global__ void __launch_bounds__(256) k_lc_buckets(const G1Affine *items, const
     {
         int run = lane_start;
 #pragma unroll 1
-        for (int k = 0; k < nmine; k++) { const int L = seq[lane][k]; cursor[L / LC_BUCKETS][(L % LC_BUCKETS) + 1] = run; run += len_of(L); }
+        for (int k = 0; k < nmine; k++) { const int L = seq[lane][k]; cursor[L / LC_TB][(L % LC_TB) + 1] = run; run += len_of(L); }
     }
     __syncthreads();
 #pragma unroll 1
     for (int tk = 0; tk < ntasks; tk++) {
-        const int w = task_window(tk), lo = tk < n1 ? 2 * n : 0, hi = tk < n1 ? ni : 2 * n;
+        const int t = task_of(tk), w = lc_task_window(t), part = lc_task_part(t);
+        const int lo = lc_task_class(t) ? n0 : 0, hi = lc_task_class(t) ? ni : n0;
         for (int j = lo + lane; j < hi; j += 64) {
-            const int d = dg[(size_t)j * LC_DIG_STRIDE + w];
-            if (d) { const int pos = atomicAdd(&cursor[tk][d < 0 ? -d : d], 1); lists[pos] = (uint16_t)(j | (d < 0 ? 0x8000 : 0)); }
+            const int d = dg[(size_t)j * CFG::DIG_STRIDE + w], b = local_bucket(d, part);
+            if (b) { const int pos = atomicAdd(&cursor[tk][b], 1); lists[pos] = (uint16_t)(j | (d < 0 ? 0x8000 : 0)); }
         }
     }
     __threadfence_block();                       // the global-slab form of the lists is read back by other lanes of this wave
@@ -440,30 +485,31 @@ __global__ void __launch_bounds__(256) k_lc_buckets(const G1Affine *items, const
 
 // 256-thread workgroups: four waves, one per SIMD of the CU the workgroup lands on (64-thread workgroups of this latency-bound chain
 // were placed two to a SIMD while other SIMDs idled: 2.9 instead of 1.9 ms per 2048 batches); the waves share nothing.
-__global__ void __launch_bounds__(256) k_lc_horner(const LcSlot *S, int groups, PairPt *pair_pts) {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;         // (batch, class, bucket - 1): 16-lane segments never straddle a wave
+template <class CFG>
+__device__ __forceinline__ void lc_horner_body(const LcSlot *S, int groups, PairPt *pair_pts) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;         // (batch, class, bucket - 1): the NB-lane segments never straddle a wave
     const int lane = threadIdx.x & 63;
-    const bool live = id < 2 * LC_BUCKETS * groups;
-    const int gc = live ? id / LC_BUCKETS : 0, bi = id % LC_BUCKETS;     // gc = 2 g + class
-    const LcSlot *s = S + (size_t)gc * LC_WINDOWS * LC_BUCKETS;
-    G1Jac acc = live ? s[(size_t)(LC_WINDOWS - 1) * LC_BUCKETS + bi].jac : g1_inf();
+    const bool live = id < 2 * CFG::NB * groups;
+    const int gc = live ? id / CFG::NB : 0, bi = id % CFG::NB;     // gc = 2 g + class
+    const LcSlot *s = S + (size_t)gc * CFG::WINDOWS * CFG::NB;
+    G1Jac acc = live ? s[(size_t)(CFG::WINDOWS - 1) * CFG::NB + bi].jac : g1_inf();
     // lazy chain (g1.h): no reductions until the end; one doubling body, one addition body
 #pragma unroll 1
-    for (int k = LC_BITS * (LC_WINDOWS - 1) - 1; k >= 0; k--) {
+    for (int k = CFG::BITS * (CFG::WINDOWS - 1) - 1; k >= 0; k--) {
         g1_dbl_lazy(acc, acc);
-        if (k % LC_BITS == 0) { G1Jac v = live ? s[(size_t)(k / LC_BITS) * LC_BUCKETS + bi].jac : g1_inf(); g1_add_lazy(acc, acc, v); }
+        if (k % CFG::BITS == 0) { G1Jac v = live ? s[(size_t)(k / CFG::BITS) * CFG::NB + bi].jac : g1_inf(); g1_add_lazy(acc, acc, v); }
     }
     g1_canon_lazy(acc, acc);
-    // sum_b b * A_b = sum_k T_k with the suffix sums T_k = sum_{b >= k} A_b: 4-step suffix scan over the 16 lanes, 4-step butterfly
+    // sum_b b * A_b = sum_k T_k with the suffix sums T_k = sum_{b >= k} A_b: suffix scan over the NB lanes, butterfly
     G1Jac r = acc;
 #pragma unroll 1
-    for (int off = 1; off < LC_BUCKETS; off <<= 1) {
-        G1Jac o = g1_shfl_down16(r, off), t;
+    for (int off = 1; off < CFG::NB; off <<= 1) {
+        G1Jac o = g1_shfl<CFG::NB, false>(r, off), t;
         g1_add(t, r, o);
-        if ((lane % LC_BUCKETS) + off < LC_BUCKETS) r = t;
+        if ((lane % CFG::NB) + off < CFG::NB) r = t;
     }
 #pragma unroll 1
-    for (int off = 1; off < LC_BUCKETS; off <<= 1) { G1Jac o = g1_shfl_xor(r, off); g1_add(r, r, o); }
+    for (int off = 1; off < CFG::NB; off <<= 1) { G1Jac o = g1_shfl_xor(r, off); g1_add(r, r, o); }
     if (!live || bi != 0) return;
     PairPt a; pairpt_from_jac(a, r, (gc & 1) == 0);               // pairings_verify negates its first G1 argument (utils.rs:198-201)
     pair_pts[gc] = a;
@@ -474,20 +520,21 @@ __global__ void __launch_bounds__(256) k_lc_horner(const LcSlot *S, int groups, 
 //   k_lc_wsum    one lane per (batch, class, window):  W = sum_b b B[b]  by running sums (acc += B[b]; W += acc, b = 16 .. 1)
 //   k_lc_hchain_quad  one DPP quad per (batch, class): Horner over the 26 W's (5 doublings + 1 addition each), to affine
 // ~200 k wave instructions per batch instead of ~390 k; the dependent chain is ~20 % longer, so the form above stays for fewer batches.
-__global__ void __launch_bounds__(256, 2) k_lc_wsum(const LcSlot *S, int groups, G1Jac *W) {
+template <class CFG>
+__device__ __forceinline__ void lc_wsum_body(const LcSlot *S, int groups, G1Jac *W) {
     // the running total is parked in LDS between its additions (limb-major: conflict-free): with acc, the total, the bucket being
     // added and the temporaries of an addition all in registers the kernel spills 68 VGPRs to scratch
     __shared__ uint32_t tot[4 * NFP][256];
     const int id = blockIdx.x * blockDim.x + threadIdx.x, tid = threadIdx.x;         // (batch, class, window)
-    if (id >= 2 * LC_WINDOWS * groups) return;                    // (no barrier below: every lane keeps to its own LDS column)
-    const LcSlot *s = S + (size_t)id * LC_BUCKETS;                // the bucket kernel's raw (lazy extended-Jacobian) sums; all-zero = infinity
+    if (id >= 2 * CFG::WINDOWS * groups) return;                    // (no barrier below: every lane keeps to its own LDS column)
+    const LcSlot *s = S + (size_t)id * CFG::NB;                // the bucket kernel's raw (lazy extended-Jacobian) sums; all-zero = infinity
     // Leading empty buckets are COMMON, not rare: the top window's digit has 3 value bits and a carry, so its buckets 9 .. 16 are empty in every
     // batch, and every wave holds two or three top-window lanes.  g1x_add_lazy2 sends an operand at infinity through the canonical complete
     // addition -- a divergent branch, so the whole wave ran it: 18 of a wave's 30 additions.  A lane now starts at its highest non-empty bucket
-    // and sits out the steps above it (the sums are the same: infinity + infinity); an empty bucket further down still takes the complete addition.
+    // and sits out the steps above it (the sums are the same: infinity + infinity).
     int start = -1;
 #pragma unroll 1
-    for (int b = LC_BUCKETS - 1; b >= 0 && start < 0; b--) {
+    for (int b = CFG::NB - 1; b >= 0 && start < 0; b--) {
         const Fp zz = s[b].raw.zz;
         uint32_t o = 0;
 #pragma unroll
@@ -500,9 +547,16 @@ __global__ void __launch_bounds__(256, 2) k_lc_wsum(const LcSlot *S, int groups,
     for (int i = 0; i < NFP; i++) { tot[i][tid] = acc.x.l[i]; tot[NFP + i][tid] = acc.y.l[i]; tot[2 * NFP + i][tid] = acc.zz.l[i];
             tot[3 * NFP + i][tid] = acc.zzz.l[i]; }
 #pragma unroll 1
-    for (int b = LC_BUCKETS - 2; b >= 0; b--) {
+    for (int b = CFG::NB - 2; b >= 0; b--) {
         if (b >= start) continue;
-        g1x_add_lazy2(acc, acc, s[b].raw);
+        {   // an empty bucket below the first one (the rule in small batches: at n = 8 a bucket of class 0 expects one item) adds nothing to acc: the
+            // lane sits the addition out instead of sending its whole wave through the complete one
+            const G1X bk = s[b].raw;
+            uint32_t o = 0;
+#pragma unroll
+            for (int i = 0; i < NFP; i++) o |= bk.zz.l[i];
+            if (o) g1x_add_lazy2(acc, acc, bk);
+        }
         asm volatile("" ::: "memory");                            // the total is fetched only now ...
         G1X sum;
 #pragma unroll
@@ -524,23 +578,37 @@ __global__ void __launch_bounds__(256, 2) k_lc_wsum(const LcSlot *S, int groups,
 }
 // The same chain walked by a DPP quad per (batch, class) (g1_quad.h): 256 waves of pure latency become 1024, each 3 + 3 + .. product stages
 // deep per window instead of 5 x 7 + 16 products on one lane (1.4 -> 0.85 ms per 8192 batches).
-__global__ void __launch_bounds__(256) k_lc_hchain_quad(const G1Jac *W, int groups, PairPt *pair_pts) {
+template <class CFG>
+__device__ __forceinline__ void lc_hchain_quad_body(const G1Jac *W, int groups, PairPt *pair_pts) {
     const int tid = blockIdx.x * blockDim.x + threadIdx.x, role = tid & 3;
     const bool live = (tid >> 2) < 2 * groups;
     const int gc = live ? (tid >> 2) : 2 * groups - 1;            // idle quads redo the last chain (every lane takes part in the DPP moves)
-    const G1Jac *w = W + (size_t)gc * LC_WINDOWS;
-    G1Jac acc = w[LC_WINDOWS - 1];
+    const G1Jac *w = W + (size_t)gc * CFG::WINDOWS;
+    G1Jac acc = w[CFG::WINDOWS - 1];
     // one loop, one inlined instance of each quad routine
 #pragma unroll 1
-    for (int k = LC_BITS * (LC_WINDOWS - 1) - 1; k >= 0; k--) {
+    for (int k = CFG::BITS * (CFG::WINDOWS - 1) - 1; k >= 0; k--) {
         g1_dbl_quad(acc, role);
-        if (k % LC_BITS == 0) { const G1Jac v = w[k / LC_BITS]; g1_add_quad(acc, acc, v, role); }      // (uniform branch)
+        if (k % CFG::BITS == 0) { const G1Jac v = w[k / CFG::BITS]; g1_add_quad(acc, acc, v, role); }      // (uniform branch)
     }
     if (!live || role != 0) return;
     G1Jac r; g1_canon_lazy(r, acc);
     PairPt a; pairpt_from_jac(a, r, (gc & 1) == 0);               // pairings_verify negates its first G1 argument (utils.rs:198-201)
     pair_pts[gc] = a;
 }
+
+// The kernels of the two forms: the bodies above at LcQuarters under the plain names (what the flagship call runs) and at LcHalves.
+#define LC_KERNEL_PAIR(BOUNDS, NAME, BODY, PARAMS, ARGS) \
+    __global__ void __launch_bounds__ BOUNDS NAME PARAMS { BODY<LcQuarters> ARGS; } \
+    __global__ void __launch_bounds__ BOUNDS NAME##_halves PARAMS { BODY<LcHalves> ARGS; }
+LC_KERNEL_PAIR((64), k_lc_prep, lc_prep_body, (const G1Affine *pts, const G1Jac *qpts, const uint32_t *scal_a, const uint32_t *scal_b, const uint32_t *scal_c,
+        int n, G1Affine *items, int8_t *digits), (pts, qpts, scal_a, scal_b, scal_c, n, items, digits))
+LC_KERNEL_PAIR((256), k_lc_buckets, lc_buckets_body, (const G1Affine *items, const int8_t *digits, int n, LcSlot *S, uint16_t *glists, int keep_raw),
+        (items, digits, n, S, glists, keep_raw))
+LC_KERNEL_PAIR((256), k_lc_horner, lc_horner_body, (const LcSlot *S, int groups, PairPt *pair_pts), (S, groups, pair_pts))
+LC_KERNEL_PAIR((256, 2), k_lc_wsum, lc_wsum_body, (const LcSlot *S, int groups, G1Jac *W), (S, groups, W))
+LC_KERNEL_PAIR((256), k_lc_hchain_quad, lc_hchain_quad_body, (const G1Jac *W, int groups, PairPt *pair_pts), (W, groups, pair_pts))
+#undef LC_KERNEL_PAIR
 
 // ------------------------------------------------------------------------------------------------ lincomb, pre-shifted form
 // Latency form for FEW batches.  The three sums need the batch challenge r, and r needs every y_i, i.e. the whole SHA-256 chain
@@ -735,10 +803,10 @@ __global__ void __launch_bounds__(64) k_ps_weights(const LcSlot *S, int groups, 
 
 // ------------------------------------------------------------------------------------------------ launchers
 void launch_validate_points(const uint8_t *d_commitments, const uint8_t *d_proofs, int n_total, int n_per_group, G1Affine *d_pts, int *d_err,
-                            hipStream_t st, int stride) {
+                            hipStream_t st, int stride, G1Jac *d_q) {
     if (n_total <= 0) return;
     hipLaunchKernelGGL(k_validate_points, dim3((2 * n_total + 255) / 256), dim3(256), 0, st, d_commitments, d_proofs, n_total, n_per_group, d_pts, d_err,
-            stride);
+            stride, d_q);
 }
 // Test / audit readback of stage 2 (tests/test_gpu_parity.py): per batch  r (32 bytes big-endian, utils.rs:472) | proof_lincomb (48) |
 // rhs (48), the latter two ZCash-compressed like bytes_from_g1 (utils.rs:221-227).  pair_pts holds -proof_lincomb (utils.rs:198-201).
@@ -804,50 +872,67 @@ void launch_lincomb_single(const G1Affine *d_pts, const uint32_t *d_scal_b, cons
     hipLaunchKernelGGL(k_lincomb_single, dim3((groups + 15) / 16), dim3(64), 0, st, d_pts, d_scal_b, d_scal_c, groups, d_pair_pts,
             reinterpret_cast<uint32_t *>(d_scratch));
 }
-// entries of the global list slab (16-byte aligned count; 0 when the lists fit the LDS)
-static size_t lc_glists_entries(int n_per_group, int groups) {
-    if (40 * (size_t)n_per_group + 14 <= (size_t)LC_TASKS * LC_LDS_LIST) return 0;
-    return (((size_t)groups * 4 * LC_TASKS * lc_list_stride(n_per_group)) + 7) & ~(size_t)7;
-}
-// The scratch of the bucket form, carved once: items | S | digits (padded to 256 bytes) | glists | W.  The pre-shifted form uses the first three.
+// The scratch of the bucket form, carved once: items | S | digits (padded to 256 bytes) | glists | W.  The pre-shifted form uses the first three, in
+// the halves' shape.  glists: the global list slab, a 16-byte aligned count of entries; none when the lists fit the LDS.
 struct LcScratch {
     G1Affine *items; LcSlot *S; int8_t *digits; uint16_t *glists; G1Jac *W;
     size_t bytes;                                                 // what the allocation has always been: the parts, the digits unpadded, + 512
-    LcScratch(void *d_scratch, int n_per_group, int groups) {
-        const size_t ni = (size_t)lc_items(n_per_group) * groups;
+    template <class CFG> void carve(void *d_scratch, int n_per_group, int groups) {
+        const size_t ni = (size_t)lc_items_of<CFG>(n_per_group) * groups;
         uintptr_t at = reinterpret_cast<uintptr_t>(d_scratch);    // (integer arithmetic: a null d_scratch asks for the size alone)
         auto take = [&](size_t nbytes) { const uintptr_t r = at; at += nbytes; return r; };
         items = reinterpret_cast<G1Affine *>(take(ni * sizeof(G1Affine)));
-        S = reinterpret_cast<LcSlot *>(take((size_t)2 * LC_WINDOWS * LC_BUCKETS * groups * sizeof(LcSlot)));
-        const size_t dig = ni * LC_DIG_STRIDE, dig_padded = (dig + 255) & ~(size_t)255;
+        S = reinterpret_cast<LcSlot *>(take((size_t)2 * CFG::WINDOWS * CFG::NB * groups * sizeof(LcSlot)));
+        const size_t dig = ni * CFG::DIG_STRIDE, dig_padded = (dig + 255) & ~(size_t)255;
         digits = reinterpret_cast<int8_t *>(take(dig_padded));
-        glists = reinterpret_cast<uint16_t *>(take(lc_glists_entries(n_per_group, groups) * sizeof(uint16_t)));
-        W = reinterpret_cast<G1Jac *>(take((size_t)2 * LC_WINDOWS * groups * sizeof(G1Jac)));
+        const size_t gl = lc_lists_in_lds<CFG>(n_per_group) ? 0 : (((size_t)groups * 4 * LC_MAXT * lc_list_stride_of<CFG>(n_per_group)) + 7) & ~(size_t)7;
+        glists = reinterpret_cast<uint16_t *>(take(gl * sizeof(uint16_t)));
+        W = reinterpret_cast<G1Jac *>(take((size_t)2 * CFG::WINDOWS * groups * sizeof(G1Jac)));
         bytes = (size_t)(at - reinterpret_cast<uintptr_t>(d_scratch)) - (dig_padded - dig) + 512;
+    }
+    LcScratch(void *d_scratch, int n_per_group, int groups, bool quarters = false) {
+        if (quarters) carve<LcQuarters>(d_scratch, n_per_group, groups); else carve<LcHalves>(d_scratch, n_per_group, groups);
     }
 };
 static void launch_lc_prep(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group, int groups,
         const LcScratch &sc, hipStream_t st) {
     const int nt = 3 * n_per_group + 1;
-    hipLaunchKernelGGL(k_lc_prep, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, sc.items, sc.digits);
+    hipLaunchKernelGGL(k_lc_prep_halves, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, (const G1Jac *)nullptr, d_scal_a, d_scal_b, d_scal_c,
+            n_per_group, sc.items, sc.digits);
 }
-void launch_lincomb_buckets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group,
-                            int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st, int stage, int chain_from) {
-    if (groups <= 0) return;
-    const LcScratch sc(d_scratch, n_per_group, groups);
-    if (stage == 0 || stage == 1) launch_lc_prep(d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, st);
-    if (stage == 0 || stage == 2) hipLaunchKernelGGL(k_lc_buckets, dim3(groups), dim3(256), 0, st, sc.items, sc.digits, n_per_group, sc.S, sc.glists,
-            groups >= chain_from ? 1 : 0);
+// the three stages in the form CFG; d_q: the Q's as k_validate_points left them (quarters only; made affine in place by stage 1)
+template <class CFG>
+static void launch_lc_stages(const G1Affine *d_pts, G1Jac *d_q, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group,
+        int groups, const LcScratch &sc, PairPt *d_pair_pts, hipStream_t st, int stage, int chain_from) {
+    constexpr bool Q = CFG::PER_TERM == 4;
+    if (stage == 0 || stage == 1) {
+        if constexpr (CFG::PER_TERM == 4) {
+            const int np = 2 * n_per_group * groups, nt = 3 * n_per_group + 1;
+            hipLaunchKernelGGL(k_q_affine, dim3((np + 64 * QA_K - 1) / (64 * QA_K)), dim3(64), 0, st, d_q, np);
+            hipLaunchKernelGGL(k_lc_prep, dim3(groups * ((nt + 63) / 64)), dim3(64), 0, st, d_pts, (const G1Jac *)d_q, d_scal_a, d_scal_b, d_scal_c,
+                    n_per_group, sc.items, sc.digits);
+        } else launch_lc_prep(d_pts, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, st);
+    }
+    if (stage == 0 || stage == 2) hipLaunchKernelGGL(Q ? k_lc_buckets : k_lc_buckets_halves, dim3(groups), dim3(256), 0, st, sc.items, sc.digits, n_per_group,
+            sc.S, sc.glists, groups >= chain_from ? 1 : 0);
     if (stage == 0 || stage == 3) {
         if (groups >= chain_from) {
-            hipLaunchKernelGGL(k_lc_wsum, dim3((2 * LC_WINDOWS * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, sc.W);
-            hipLaunchKernelGGL(k_lc_hchain_quad, dim3((8 * groups + 255) / 256), dim3(256), 0, st, sc.W, groups, d_pair_pts);
-        } else hipLaunchKernelGGL(k_lc_horner, dim3((2 * LC_BUCKETS * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, d_pair_pts);
+            hipLaunchKernelGGL(Q ? k_lc_wsum : k_lc_wsum_halves, dim3((2 * CFG::WINDOWS * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, sc.W);
+            hipLaunchKernelGGL(Q ? k_lc_hchain_quad : k_lc_hchain_quad_halves, dim3((8 * groups + 255) / 256), dim3(256), 0, st, sc.W, groups, d_pair_pts);
+        } else hipLaunchKernelGGL(Q ? k_lc_horner : k_lc_horner_halves, dim3((2 * CFG::NB * groups + 255) / 256), dim3(256), 0, st, sc.S, groups, d_pair_pts);
     }
 }
-size_t lincomb_buckets_scratch_bytes(int n_per_group, int groups) {
-    return LcScratch(nullptr, n_per_group, groups).bytes;
+void launch_lincomb_buckets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, int n_per_group,
+                            int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st, int stage, int chain_from, G1Jac *d_q) {
+    if (groups <= 0) return;
+    const LcScratch sc(d_scratch, n_per_group, groups, d_q != nullptr);
+    if (d_q) launch_lc_stages<LcQuarters>(d_pts, d_q, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, d_pair_pts, st, stage, chain_from);
+    else launch_lc_stages<LcHalves>(d_pts, nullptr, d_scal_a, d_scal_b, d_scal_c, n_per_group, groups, sc, d_pair_pts, st, stage, chain_from);
 }
+size_t lincomb_buckets_scratch_bytes(int n_per_group, int groups, bool quarters) {
+    return LcScratch(nullptr, n_per_group, groups, quarters).bytes;
+}
+bool lincomb_quarters_fit(int n_per_group) { return lc_items_fit<LcQuarters>(n_per_group); }
 bool lincomb_preshift_fits(int n_per_group, int groups) { return n_per_group >= 1 && n_per_group <= PS_MAX_N && groups >= 1 && groups < 64; }
 size_t lincomb_preshift_bytes(int n_per_group, int groups) { return sizeof(G1Jac) * (size_t)ps_points(n_per_group) * LC_WINDOWS * groups; }
 static void launch_ps_shift(const G1Affine *d_pts, const uint8_t *d_commitments, const uint8_t *d_proofs, int stride, int n_per_group, int groups,

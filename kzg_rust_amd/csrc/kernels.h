@@ -77,7 +77,9 @@ int launch_setup(const uint8_t *d_g1_bytes, const uint8_t *d_g2_bytes, DeviceTab
 // d_proofs may be null (commitments only, e.g. compute_blob_kzg_proof's challenge step, kzg.rs:321)
 void launch_validate_points(const uint8_t *d_commitments, const uint8_t *d_proofs, int n_total, int n_per_group,
                             G1Affine *d_pts /* [group][2*npg]: commitments then proofs; may be null */, int *d_err /* per group */,
-                            hipStream_t st, int stride = 48 /* bytes between consecutive inputs: 48 packed, 160 inside records */);
+                            hipStream_t st, int stride = 48 /* bytes between consecutive inputs: 48 packed, 160 inside records */,
+                            G1Jac *d_q = nullptr /* in the layout of d_pts: [|x|]P of every point, Jacobian -- the first ladder of the subgroup test, kept
+                                                    for the quarters form of launch_lincomb_buckets; infinity for a point at infinity or a failed one */);
 // validate_kzg_g1 in two launches: decoding (-> points, error on a bad encoding / off-curve x) and the subgroup test (-> error only)
 void launch_decompress_points(const uint8_t *d_commitments, const uint8_t *d_proofs, int n_total, int n_per_group, G1Affine *d_pts, int *d_err, hipStream_t st,
                               int stride = 48);
@@ -113,8 +115,11 @@ size_t lincomb_single_bytes(int groups);
 void launch_lincomb_buckets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c,
                             int n_per_group, int groups, void *d_scratch /* lincomb_buckets_scratch_bytes() */, PairPt *d_pair_pts, hipStream_t st,
                             int stage = 0 /* 0: all three kernels; 1 prep, 2 buckets, 3 horner (per-kernel timing) */,
-                            int chain_from = 6144 /* batches from which the tail is k_lc_wsum + k_lc_hchain instead of k_lc_horner */);
-size_t lincomb_buckets_scratch_bytes(int n_per_group, int groups);
+                            int chain_from = 6144 /* batches from which the tail is k_lc_wsum + k_lc_hchain instead of k_lc_horner */,
+                            G1Jac *d_q = nullptr /* what launch_validate_points left for these points: the quarters form (four 64-bit scalars per term,
+                                                    6-bit windows; lincomb_quarters_fit(n_per_group) must hold); stage 1 makes them affine IN PLACE */);
+size_t lincomb_buckets_scratch_bytes(int n_per_group, int groups, bool quarters = false);
+bool lincomb_quarters_fit(int n_per_group);
 // pre-shifted form for few batches: launch_lincomb_preshift needs only the validated points (it can run beside the Fiat-Shamir
 // hash), launch_lincomb_preshifted finishes once the r powers exist.  d_scratch: lincomb_buckets_scratch_bytes().
 bool lincomb_preshift_fits(int n_per_group, int groups);

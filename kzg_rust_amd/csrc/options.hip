@@ -338,7 +338,7 @@ void kzg355_options_from_env(kzg355_options *o) {
     num("KZG355_RHASH_LANES_FROM", 1, 1 << 24, &o->rhash_lanes_from);
     if (const char *e = getenv("KZG355_CHALLENGE")) o->challenge_form = strcmp(e, "1w") == 0 ? 1 : strcmp(e, "2w") == 0 ? 2 : 0;
     if (const char *e = getenv("KZG355_LINCOMB")) o->lincomb_form = strcmp(e, "bucket") == 0 ? 2 : strcmp(e, "window") == 0 ? 1 : strcmp(e,
-            "preshift") == 0 ? 3 : 0;
+            "preshift") == 0 ? 3 : strcmp(e, "bucket_halves") == 0 ? 5 : 0;
     if (const char *e = getenv("KZG355_EXCHANGE")) o->exchange = strcmp(e, "peer") == 0 ? 1 : strcmp(e, "rccl") == 0 ? 2 : 0;
     num("KZG355_VERIFY_ONLY", 0, 1, &o->verify_only);
     if (const char *e = getenv("KZG355_SUBMIT")) o->submit_sets = strcmp(e, "sets") == 0 ? 1 : strcmp(e, "pipeline") == 0 ? 2 : 0;

@@ -82,7 +82,8 @@ int enqueue_points_beside(kzg355_settings *s, Workspace *w, Timed &tm, const uin
         tm.begin("validate_points", w->side); launch_subgroup_points(d_pts, n_total, npg, d_err, w->side); tm.end(w->side);
         w->shift_ready = true;
     } else {
-        tm.begin("validate_points", w->side); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->side, stride); tm.end(w->side);
+        G1Jac *d_q = allow_preshift && d_pts && d_p ? stage2_q_buffer(s, w, npg, n_total / npg) : nullptr;
+        tm.begin("validate_points", w->side); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->side, stride, d_q); tm.end(w->side);
     }
     HIPCHK(hipEventRecord(w->ev_join, w->side));
     return KZG355_OK;
@@ -113,7 +114,9 @@ int run_stage1(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blo
                int npg, uint8_t *d_records, G1Affine *d_pts, int *d_err, bool allow_preshift, HostFront *hf,
                const std::function<int()> *after_challenge) {
     int rc;
-    w->shift_ready = false;
+    w->shift_ready = false; w->q_ready = false;
+    // allow_preshift says that stage 2 follows on this workspace with these points: the validation may then leave what that stage 2 can use
+    auto q_buffer = [&]() -> G1Jac * { return allow_preshift && d_pts && d_p ? stage2_q_buffer(s, w, npg, n_total / npg) : nullptr; };
     if ((rc = w->z.ensure(sizeof(Fr) * (size_t)n_total))) return rc;
     if (!is_small(s) && (rc = w->zpow.ensure(sizeof(Fr) * EVAL_ZPOWERS * (size_t)n_total))) return rc;
     if (is_small(s)) {   // minimal preset: one lane per blob does conversion, challenge and evaluation (k_small.hip)
@@ -129,7 +132,8 @@ int run_stage1(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blo
     if (beside) {
         if ((rc = enqueue_points_beside(s, w, tm, d_c, d_p, n_total, npg, d_pts, d_err, allow_preshift))) return rc;
     } else if (!after_challenge) {
-        tm.begin("validate_points"); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->stream); tm.end();
+        G1Jac *d_q = q_buffer();
+        tm.begin("validate_points"); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->stream, 48, d_q); tm.end();
     }
     if (hf) {
         // the blobs follow the point kernels into their queues (the copy from pageable memory holds the host thread for its duration);
@@ -147,7 +151,8 @@ int run_stage1(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blo
     }
     if (after_challenge) {
         if ((rc = (*after_challenge)())) return rc;
-        if (!beside) { tm.begin("validate_points"); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->stream); tm.end(); }
+        if (!beside) { G1Jac *d_q = q_buffer(); tm.begin("validate_points"); launch_validate_points(d_c, d_p, n_total, npg, d_pts, d_err, w->stream, 48, d_q);
+                tm.end(); }
     }
     tm.begin("eval"); launch_eval(d_blobs, w->z.as<Fr>(), w->zpow.as<Fr>(), s->t, n_total, npg, nullptr, d_records, d_err, w->stream); tm.end();
     return KZG355_OK;
@@ -159,8 +164,8 @@ int run_stage2(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_rec
                int *d_err, int *d_ok, bool lone_call) {
     int rc;
     const size_t n_total = (size_t)npg * groups;
-    const bool shift_ready = w->shift_ready;                      // consumed here whatever happens below
-    w->shift_ready = false;
+    const bool shift_ready = w->shift_ready, q_ready = w->q_ready;       // consumed here whatever happens below
+    w->shift_ready = false; w->q_ready = false;
     if ((rc = w->scal_a.ensure(32 * n_total))) return rc;
     if ((rc = w->scal_b.ensure(32 * n_total))) return rc;
     if ((rc = w->scal_c.ensure(32 * (size_t)groups))) return rc;
@@ -193,8 +198,10 @@ int run_stage2(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_rec
             w->stream, s->t.n_fe, s->rhash_lanes_from, host_rhash ? 1 : 0); tm.end();
     const int form = lincomb_form(s, npg, groups);
     const bool buckets = form == LC_FORM_BUCKET;
+    // the quarters form: this launch set's validation ran on this workspace and left the Q's (stage2_q_buffer)
+    G1Jac *d_q = buckets && q_ready && s->lincomb_mode != LC_FORM_BUCKET_HALVES && lincomb_quarters_fit(npg) ? w->qpts.as<G1Jac>() : nullptr;
     if ((rc = w->lc_partials.ensure(form == LC_FORM_WINDOW ? lincomb_partials_bytes(npg, groups) : form == LC_FORM_SINGLE ? lincomb_single_bytes(groups) :
-            lincomb_buckets_scratch_bytes(npg, groups)))) return rc;
+            lincomb_buckets_scratch_bytes(npg, groups, d_q != nullptr)))) return rc;
     if ((rc = join_points(w, form != LC_FORM_PRESHIFT))) return rc;       // the decoded points (and their shifts) are needed from here on
     if (form == LC_FORM_PRESHIFT) {
         if (!shift_ready) {                                       // entry points without a stage 1 (single proofs, gathered records)
@@ -217,7 +224,7 @@ int run_stage2(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_rec
             if (stage > 1) tm.end();
             tm.begin(names[stage - 1]);
             launch_lincomb_buckets(d_pts, w->scal_a.as<uint32_t>(), w->scal_b.as<uint32_t>(), w->scal_c.as<uint32_t>(), npg, groups, w->lc_partials.p,
-                    w->pair_pts.as<PairPt>(), w->stream, stage, s->lc_chain_from);
+                    w->pair_pts.as<PairPt>(), w->stream, stage, s->lc_chain_from, d_q);
         }
     } else if (form == LC_FORM_SINGLE) {
         tm.begin("lincomb");

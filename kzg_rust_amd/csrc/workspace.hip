@@ -66,13 +66,21 @@ bool ensure_side2(kzg355_settings *s, Workspace *w) {
 int lincomb_form(const kzg355_settings *s, int npg, int groups) {
     const bool bucket_ok = npg >= 8 && npg <= 4096, pre_ok = lincomb_preshift_fits(npg, groups);
     if (s->lincomb_mode == LC_FORM_PRESHIFT) return pre_ok ? LC_FORM_PRESHIFT : LC_FORM_WINDOW;
-    if (s->lincomb_mode == LC_FORM_BUCKET) return bucket_ok ? LC_FORM_BUCKET : LC_FORM_WINDOW;
+    if (s->lincomb_mode == LC_FORM_BUCKET || s->lincomb_mode == LC_FORM_BUCKET_HALVES) return bucket_ok ? LC_FORM_BUCKET : LC_FORM_WINDOW;
     if (s->lincomb_mode == LC_FORM_WINDOW) return LC_FORM_WINDOW;
     // many independent single-proof checks (the *_many forms of verify_kzg_proof / verify_blob_kzg_proof): four ladder lanes per check
     if (npg == 1 && !pre_ok) return LC_FORM_SINGLE;
     // few batches: shift every point under the hash, finish with ~25 additions; many: least issue work (buckets); in between: per-term ladders
     if (pre_ok) return LC_FORM_PRESHIFT;
     return bucket_ok && groups >= 64 ? LC_FORM_BUCKET : LC_FORM_WINDOW;
+}
+
+G1Jac *stage2_q_buffer(const kzg355_settings *s, Workspace *w, int npg, int groups) {
+    w->q_ready = false;
+    if (s->lincomb_mode == LC_FORM_BUCKET_HALVES || is_small(s) || lincomb_form(s, npg, groups) != LC_FORM_BUCKET || !lincomb_quarters_fit(npg)) return nullptr;
+    if (w->qpts.ensure(sizeof(G1Jac) * 2 * (size_t)npg * groups) != KZG355_OK) return nullptr;
+    w->q_ready = true;
+    return w->qpts.as<G1Jac>();
 }
 
 int status_from_err(int err) {

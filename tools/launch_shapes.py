@@ -22,7 +22,11 @@ def blobs_of_launch(kernel, grid, npg=64):
         "k_lc_wsum": 52, "k_lc_hchain_quad": 8, "k_ps_shift": 4 * (2 * npg + 1), "k_ps_buckets": 2 * 4 * 256, "k_ps_weights": 32,
         "k_lincomb_terms": 64 * math.ceil(2 * (3 * npg + 1) / 64), "k_lincomb_finish": 64, "k_pairing_coop": 64, "k_pairing_coop<1>": 64, "k_pairing_coop<3>": 64, "k_pairing_coop2": 128, "k_pairing_hard12": 256 / 20,
         "k_pairing": 1, "k_dump_intermediates": 2,
+        # the plain k_lc_* names are the quarters form (11 six-bit windows, 32 buckets); *_halves: 26 five-bit windows, 16 buckets
+        "k_lc_prep_halves": 64 * math.ceil((3 * npg + 1) / 64), "k_lc_buckets_halves": 256, "k_lc_horner_halves": 32, "k_lc_wsum_halves": 52,
+        "k_lc_hchain_quad_halves": 8, "k_q_affine": 2 * npg / 8,
     }
+    per_batch.update({"k_lc_horner": 64, "k_lc_wsum": 22})
     if kernel in per_blob:
         return grid / per_blob[kernel]
     if kernel in per_batch:
