@@ -449,6 +449,44 @@ long kzg355_settings_cell_device_prep_calls(const kzg355_settings *s);
  * device that ran it, a verify call cut into blocks one on every device.  A call refused as a whole counts nowhere.  A NULL handle, or a NULL out
  * with cap > 0, is KZG355_BADARGS. */
 int kzg355_settings_cell_calls_per_device(const kzg355_settings *s, long *out /* cap */, size_t cap);
+/* ---- blobs against their EIP-7594 cell proofs ----------------------------------------------------------------------------------------------
+ * The Fulu counterpart of kzg355_verify_blob_kzg_proof_batch: since EIP-7594 a blob transaction (or a builder's blobs bundle) carries the 128 cell
+ * proofs of each blob instead of one blob proof, and is checked by VerifyCellProofs(blobs, commitments, cell_proofs).  For n blobs with their n
+ * commitments and 128 n cell proofs (blob after blob, cell order) the answer is EXACTLY that of kzg355_verify_cell_kzg_proof_batch on 128 n
+ * cells, the cell at position 128 b + k having commitment b, cell index k, cell k of kzg355_compute_cells_and_kzg_proofs(blob b) and proof
+ * 128 b + k: the same verdict, the same statuses and the same challenge r (the commitments deduplicated by their bytes in order of first
+ * appearance; the transcript hashes the computed cells).  n == 0 -> true.  A blob element >= r, or a commitment or proof that fails
+ * validate_kzg_g1 -> KZG355_BADARGS.  n_commitments != n_blobs or n_cell_proofs != 128 n_blobs -> KZG355_BADARGS.  Mainnet handles only.
+ * The blobs cross PCIe once (128 KiB each); their cells are computed and checked on the device, and the call builds no proof setup (the 384 MiB
+ * table of kzg355_compute_cells_and_kzg_proofs is not needed). */
+int kzg355_verify_blob_cell_proofs_batch(bool *ok, const uint8_t *blobs, size_t n_blobs, const uint8_t *commitments, size_t n_commitments,
+                                         const uint8_t *cell_proofs, size_t n_cell_proofs, const kzg355_settings *s);
+/* `groups` independent calls of the above (one verdict per transaction) in one set of launches: the three arrays group-major, n_per_group blobs
+ * (and commitments, and 128 n_per_group proofs) each.  ok[g] / status[g] per group; the return value is the first non-OK status; what is wrong
+ * with one group is that group's status and leaves the others alone.  A refusal of the call as a whole marks every group: a NULL handle or array,
+ * a handle of another FIELD_ELEMENTS_PER_BLOB, n_per_group above 2048 blobs (262144 cells, the most one set of launches takes), groups above
+ * 2^24.  groups == 0 -> OK and nothing is touched; n_per_group == 0 -> every group true.  More groups than fit one set of launches (2048 blobs)
+ * run in chunks of whole groups inside the call.  A handle over several devices spreads the groups over them in contiguous ranges, as the other
+ * host-buffer cell calls do (a group is never cut), and counts its launch sets in kzg355_settings_cell_calls_per_device. */
+int kzg355_verify_blob_cell_proofs_batch_many(bool *ok /* groups */, int *status /* groups or NULL */, const uint8_t *blobs, const uint8_t *commitments,
+                                              const uint8_t *cell_proofs, size_t n_per_group, size_t groups, const kzg355_settings *s);
+/* The same with the three bulk arrays in HBM: device pointers on the handle's device (its first device, for a handle over several), 16-byte
+ * aligned (a misaligned pointer is KZG355_BADARGS); ok / status are host pointers.  The 48 bytes of every commitment come back for the
+ * deduplication; calls of few groups also copy the cells and proofs back and hash their transcripts on the host, by the rule of
+ * kzg355_verify_cell_kzg_proof_batch_many_device (always above 128 blobs per group). */
+int kzg355_verify_blob_cell_proofs_batch_many_device(bool *ok /* host, groups */, int *status /* host, groups or NULL */, const uint8_t *d_blobs,
+                                                     const uint8_t *d_commitments, const uint8_t *d_cell_proofs, size_t n_per_group, size_t groups,
+                                                     const kzg355_settings *s);
+/* Test forms: out[176 g ..] receives r | [I(tau)]_1 | LL | RL of group g as kzg355_debug_cell_batch_intermediates lays them out.  interp_form pins
+ * how [I(tau)]_1's scalars are found: 0 what the calls above do, 1 from the blobs' monomial coefficients, 2 by the column
+ * kernel of kzg355_verify_cell_kzg_proof_batch over the computed cells; prep_form as in kzg355_debug_cell_batch_intermediates_device (1: the
+ * transcripts are hashed on the device, 2: on the host).  Any other value of either is KZG355_BADARGS. */
+int kzg355_debug_blob_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *ok /* groups */, int *status /* groups or NULL */, const uint8_t *blobs,
+                                               const uint8_t *commitments, const uint8_t *cell_proofs, size_t n_per_group, size_t groups, int interp_form,
+                                               const kzg355_settings *s);
+int kzg355_debug_blob_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,
+                                                      const uint8_t *d_blobs, const uint8_t *d_commitments, const uint8_t *d_cell_proofs, size_t n_per_group,
+                                                      size_t groups, int interp_form, int prep_form, const kzg355_settings *s);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

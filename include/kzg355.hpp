@@ -187,6 +187,20 @@ struct Kzg {
         return ok;
     }
 
+    // blobs against their EIP-7594 cell proofs (128 per blob, blob after blob in cell order): the Fulu counterpart of verify_blob_kzg_proof_batch,
+    // exactly verify_cell_kzg_proof_batch over all 128 cells of every blob with the cells computed on the device
+    static Result<bool> verify_blob_cell_proofs_batch(const std::vector<Blob> &blobs, const std::vector<KzgCommitment> &cs,
+                                                      const std::vector<KzgProof> &cell_proofs, const KzgSettings &s) {
+        std::vector<uint8_t> b(blobs.size() * BYTES_PER_BLOB), c(cs.size() * 48), p(cell_proofs.size() * 48);
+        for (size_t i = 0; i < blobs.size(); i++) std::memcpy(&b[i * BYTES_PER_BLOB], blobs[i].data(), BYTES_PER_BLOB);
+        for (size_t i = 0; i < cs.size(); i++) std::memcpy(&c[i * 48], cs[i].data(), 48);
+        for (size_t i = 0; i < cell_proofs.size(); i++) std::memcpy(&p[i * 48], cell_proofs[i].data(), 48);
+        bool ok = false;
+        int rc = kzg355_verify_blob_cell_proofs_batch(&ok, b.data(), blobs.size(), c.data(), cs.size(), p.data(), cell_proofs.size(), s.raw());
+        if (rc) return from_status(rc, "verify_blob_cell_proofs_batch");
+        return ok;
+    }
+
     // EIP-7594 compute_cells_and_kzg_proofs: the 128 cells of the blob's 2x extension and their 128 proofs, in cell order
     static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cells_and_kzg_proofs(const Blob &blob, const KzgSettings &s) {
         std::vector<uint8_t> c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48);

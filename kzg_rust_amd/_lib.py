@@ -108,6 +108,11 @@ def load():
         "kzg355_recover_cells_and_kzg_proofs_many_sets_device": [vp, vp, ip, szp, szp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
         "kzg355_settings_cell_calls_per_device": [vp, C.POINTER(C.c_long), sz],
+        "kzg355_verify_blob_cell_proofs_batch": [bp, u8p, sz, u8p, sz, u8p, sz, vp],
+        "kzg355_verify_blob_cell_proofs_batch_many": [bp, ip, u8p, u8p, u8p, sz, sz, vp],
+        "kzg355_verify_blob_cell_proofs_batch_many_device": [bp, ip, vp, vp, vp, sz, sz, vp],
+        "kzg355_debug_blob_cell_batch_intermediates": [u8p, bp, ip, u8p, u8p, u8p, sz, sz, C.c_int, vp],
+        "kzg355_debug_blob_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, sz, sz, C.c_int, C.c_int, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -157,4 +162,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_recover_cells_and_kzg_proofs_many_device", "kzg355_debug_cell_batch_intermediates_device", "kzg355_settings_cell_device_prep_calls",
     "kzg355_recover_cells_and_kzg_proofs_many_sets", "kzg355_recover_cells_and_kzg_proofs_many_sets_device",
     "kzg355_settings_cell_calls_per_device",
+    "kzg355_verify_blob_cell_proofs_batch", "kzg355_verify_blob_cell_proofs_batch_many", "kzg355_verify_blob_cell_proofs_batch_many_device",
+    "kzg355_debug_blob_cell_batch_intermediates", "kzg355_debug_blob_cell_batch_intermediates_device",
 ]

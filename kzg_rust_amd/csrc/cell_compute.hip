@@ -7,7 +7,7 @@
 namespace kzg355_impl {
 
 // Constants of the field stage (w4096 powers, twiddle splits): the first compute call of a handle.  Under cc_mu.
-static int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
+int ensure_cc_consts(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cc_mu);
     if (s->cc_consts_ready) return KZG355_OK;
     int rc;

@@ -8,14 +8,9 @@
 
 namespace kzg355_impl {
 
-static const char *const CELL_DOMAIN = "RCKZGCBATCH__V1_";
-static const size_t CELL_MAX_CELLS = (size_t)1 << 18;   // cells per call (512 MiB of cells)
-
-static void put_u64be(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (56 - 8 * i)); }
-
 // The first cell call of a handle: constants, the 64 monomial points [tau^t]_1 (build_monomial_points, cell_compute.hip) and the line table of
 // [tau^64]_2.  Under cell_mu.  A failure releases what was being filled and is not remembered: the next call tries again (engine.h, at cell_mu).
-static int ensure_cell_setup(kzg355_settings *s, Workspace *w) {
+int ensure_cell_setup(kzg355_settings *s, Workspace *w) {
     std::lock_guard<std::mutex> lk(s->cell_mu);
     if (s->cell_ready) return KZG355_OK;
     DevBuf err, g2b;
@@ -70,7 +65,7 @@ struct CellHostPrep {
 // ranges of their own.
 // the unique commitments among `count` in order of first appearance into uc (48 per slot, padded to `count` slots with the encoding of infinity),
 // every entry's slot into cidx; returns how many there are
-static int cell_dedup(const uint8_t *commitments, size_t count, uint8_t *uc, int *cidx) {
+int cell_dedup(const uint8_t *commitments, size_t count, uint8_t *uc, int *cidx) {
     std::unordered_map<std::string_view, int> seen;
     seen.reserve(count * 2);
     int u = 0;
@@ -191,7 +186,7 @@ static void cell_host_prep(kzg355_settings *s, const uint8_t *commitments, const
 // (profiles/r05/device_host_hash_crossover.txt), where the one-lane-per-message form has taken over.
 static const size_t CELL_PREP_HOST_FROM_BYTES = (size_t)4 << 10;
 static const int CELL_PREP_HOST_UPTO_GROUPS_PER_CU = 6;
-static bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, size_t groups, int prep_form) {
+bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, size_t groups, int prep_form) {
     if (npg > (size_t)CELL_PREP_MAX_CELLS) return true;           // above the device preparation's cap every form takes the host's
     if (prep_form) return prep_form == 2;
     const size_t bytes = 16 + 32 + 48 + npg * (16 + CELL_BYTES + 48);          // (48 more per further unique commitment)
@@ -202,7 +197,7 @@ static bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t n
 // The workspace's buffers by role: blobs = cells, commitments = unique commitments, q = meta, z = r powers, y = column coefficients, scal_a =
 // lincomb scalars, partials = lincomb terms, lc_partials = the three sums per group, out48 = r | debug output.  N = n * groups cells, S segments;
 // host_input: cells and proofs are uploaded (else read where the caller has them).
-static int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints) {
+int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints) {
     const size_t N = (size_t)n * groups, T = (size_t)cell_terms(n);
     int rc;
     if ((host_input && ((rc = w->blobs.ensure((size_t)CELL_BYTES * N)) || (rc = w->proofs.ensure(48 * N)))) || (rc = w->commitments.ensure(48 * N)) ||
@@ -235,22 +230,30 @@ static int cell_upload(Workspace *w, const CellHostPrep &hp, const uint8_t *dig,
 }
 // The chain on prepared buffers: points, scalars with weights r^(k0 + k), interpolation, then the three sums per group in lc_partials -- and, with
 // finish, the pairing arguments (d_dbg or null: the debug bytes).  A block of a cut group stops at the sums (k_cell_merge ends it elsewhere).
-static void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
-                       uint8_t *d_dbg) {
+// The points need no digest: a caller that hashes on the host while they run (blob_cells.hip) queues cell_chain_points itself and says so
+// (points_queued).  bi: the groups are whole blobs and the interpolation starts from their coefficients (k_blob_cells.hip), not from the cells.
+void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, int G) {
+    const size_t N = (size_t)n * G;
+    hipStream_t st = w->stream;
+    tm.begin("cell_points");
+    launch_decompress_points(w->commitments.as<uint8_t>(), d_proofs, (int)N, n, w->pts.as<G1Affine>(), w->err.as<int>(), st);
+    launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
+    tm.end();
+}
+void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
+                uint8_t *d_dbg, bool points_queued, const BlobInterp *bi) {
     const size_t N = (size_t)n * G;
     hipStream_t st = w->stream;
     const int4 *d_segs = w->q.as<int4>();
     const int *d_gseg = w->q.as<int>() + 4 * (size_t)S, *d_cell = d_gseg + G + 1, *d_cidx = d_cell + N, *d_perm = d_cidx + N;
     uint8_t *d_r = w->out48.as<uint8_t>();
-    tm.begin("cell_points");
-    launch_decompress_points(w->commitments.as<uint8_t>(), d_proofs, (int)N, n, w->pts.as<G1Affine>(), w->err.as<int>(), st);
-    launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
-    tm.end();
+    if (!points_queued) cell_chain_points(w, tm, d_proofs, n, G);
     tm.begin("cell_scalars");
     launch_cell_scalars(w->digests.as<uint8_t>(), d_cell, d_cidx, n, G, k0, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(), w->scal_a.as<uint32_t>(), d_r, st);
     tm.end();
     tm.begin("cell_interp");
-    launch_cell_interp(d_cells, d_perm, d_segs, S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), n, G, w->y.as<Fr>(),
+    if (bi) launch_blob_cell_coefs(bi->f, w->z.as<Fr>(), s->cc_consts.as<CellComputeConsts>(), bi->n_blobs, G, bi->W, w->y.as<Fr>(), st);
+    launch_cell_interp(d_cells, d_perm, d_segs, bi ? 0 : S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), n, G, w->y.as<Fr>(),
                        w->scal_a.as<uint32_t>(), w->err.as<int>(), st);
     tm.end();
     tm.begin("cell_lincomb");

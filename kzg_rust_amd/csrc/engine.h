@@ -11,6 +11,7 @@
 //   cells.hip          verify_cell_kzg_proof_batch: host preparation, the launch set, a group cut over several devices
 //   cell_compute.hip   compute_cells_and_kzg_proofs: the setups, the chunk loop the recover call shares
 //   cell_recover.hip   recover_cells_and_kzg_proofs: index sets, the erasure decoding's field stage
+//   blob_cells.hip     verify_blob_cell_proofs_batch: blobs against all their cell proofs, the extension and the check in one launch set
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
 // entry point returns KZG355_NO_DEVICE (a HIP call that fails on a device that exists: KZG355_DEVICE_ERROR).
@@ -457,10 +458,26 @@ int host_many(const HostCall &hc, size_t units, const kzg355_settings *cs);
 // recover_cells_and_kzg_proofs (cell_recover.hip: its own field stage) share
 static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
 int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
+int ensure_cc_consts(kzg355_settings *s, Workspace *w);
 int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
            const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells)> &stage, bool dev_out = false);
+
+// cells.hip: what verify_cell_kzg_proof_batch shares with verify_blob_cell_proofs_batch (blob_cells.hip) -- the setup, the dedup, the buffers of
+// a launch set and the chain on prepared buffers
+static const char *const CELL_DOMAIN = "RCKZGCBATCH__V1_";
+static const size_t CELL_MAX_CELLS = (size_t)1 << 18;   // cells per call of the cell batch check, per launch set of the blob form (512 MiB of cells)
+inline void put_u64be(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (56 - 8 * i)); }
+// groups of whole blobs: their coefficients (groups * n_blobs * 4096 Fr) and the 64 weights per group the interpolation takes from them
+struct BlobInterp { const Fr *f; int n_blobs; Fr *W; };
+int ensure_cell_setup(kzg355_settings *s, Workspace *w);
+int cell_dedup(const uint8_t *commitments, size_t count, uint8_t *uc, int *cidx);
+bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, size_t groups, int prep_form);
+int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints);
+void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, int G);
+void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
+                uint8_t *d_dbg, bool points_queued = false, const BlobInterp *bi = nullptr);
 
 }  // namespace kzg355_impl
 

@@ -230,6 +230,17 @@ void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int
 // (many groups), else one wave per group
 void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx, const int *d_ucount,
                        int npg, int groups, bool lanes, uint8_t *d_digests, hipStream_t st);
+// ---- k_blob_cells.hip: verify_blob_cell_proofs_batch -- groups of n blobs, each with all its 128 cells in cell order (npg = 128 n)
+// What the preparation leaves, from d_pos (groups * n: the position of each blob's commitment among its group's unique ones), d_ucount (how many
+// those are) and d_uc_in (groups * n * 48: the unique commitments of a group first): d_cell, d_cidx, d_uc (padded to npg per group with the
+// encoding of infinity), d_gseg, d_indices (or null: the index array launch_cell_rhash reads) and, with columns, the column sort (d_segs: 128 per
+// group, d_perm); without, d_gseg counts the 64 segments per group of launch_blob_cell_coefs.  d_blob_err (per blob) is folded into d_err (per group).
+void launch_blob_cell_meta(const int *d_pos, const int *d_ucount, const uint8_t *d_uc_in, const int *d_blob_err, int n, int groups, bool columns, int4 *d_segs,
+                           int *d_gseg, int *d_cell, int *d_cidx, int *d_perm, size_t *d_indices, uint8_t *d_uc, int *d_err, hipStream_t st);
+struct CellComputeConsts;
+// the interpolation from the blobs' coefficients (d_f: groups * n * 4096 Fr as launch_cc_field leaves them; d_rpow as launch_cell_scalars does):
+// d_W: groups * 64 Fr, d_coef: groups * 64 * 64 Fr in launch_cell_interp's segment layout (which finishes with n_segs = 0)
+void launch_blob_cell_coefs(const Fr *d_f, const Fr *d_rpow, const CellComputeConsts *d_cc, int n, int groups, Fr *d_W, Fr *d_coef, hipStream_t st);
 
 
 // ---- k_cell_compute.hip: compute_cells_and_kzg_proofs (the cells of the 2x extension and their proofs by FK20; mainnet handles only)

@@ -805,3 +805,93 @@ class Kzg:
         if _whole_call_failed(rc, st, m):
             _check(rc, "recover_cells_and_kzg_proofs_many_sets_device")
         return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]
+
+    # ---- blobs against their EIP-7594 cell proofs (what a Fulu blob transaction or blobs bundle carries): verify_cell_kzg_proof_batch over all
+    # 128 cells of every blob, the cells computed on the device ----
+    @staticmethod
+    def verify_blob_cell_proofs_batch(blobs, commitments, cell_proofs, s):
+        """One blob transaction: its blobs, their commitments and 128 cell proofs per blob (blob after blob, cell order); True / False, BadArgs
+        on bad input or when the three lengths do not fit."""
+        bl = [_b(x, Blob) for x in blobs]
+        cs = [_b(x, KzgCommitment) for x in commitments]
+        ps = [_b(x, KzgProof) for x in cell_proofs]
+        ok = C.c_bool()
+        _check(lib().kzg355_verify_blob_cell_proofs_batch(C.byref(ok), b"".join(bl), len(bl), b"".join(cs), len(cs), b"".join(ps), len(ps), s.handle),
+               "verify_blob_cell_proofs_batch")
+        return bool(ok.value)
+
+    @staticmethod
+    def _blob_cells_many(groups, s, debug, interp_form=0):
+        if not groups:
+            return [], b""
+        if interp_form not in (0, 1, 2):
+            raise BadArgs("interp_form out of range")
+        n = len(groups[0][0])
+        flat = [[], [], []]
+        for blobs, commitments, cell_proofs in groups:
+            arrs = ([_b(x, Blob) for x in blobs], [_b(x, KzgCommitment) for x in commitments], [_b(x, KzgProof) for x in cell_proofs])
+            if len(arrs[0]) != n:
+                raise BadArgs("all groups must have the same number of blobs")
+            if len(arrs[1]) != n or len(arrs[2]) != CELLS_PER_EXT_BLOB * n:
+                raise BadArgs("length mismatch")
+            for f, a in zip(flat, arrs):
+                f += a
+        G = len(groups)
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        args = (ok, st, b"".join(flat[0]), b"".join(flat[1]), b"".join(flat[2]), n, G)
+        out = C.create_string_buffer(176 * G) if debug else None
+        rc = (lib().kzg355_debug_blob_cell_batch_intermediates(out, *args, interp_form, s.handle) if debug
+              else lib().kzg355_verify_blob_cell_proofs_batch_many(*args, s.handle))
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_cell_proofs_batch_many")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_blob_cells") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_cell_proofs_batch_many(groups, s):
+        """groups: list of (blobs, commitments, cell_proofs), every group the same number of blobs; one independent
+        verify_blob_cell_proofs_batch per group in one call.  Returns a list of bool / Error."""
+        return Kzg._blob_cells_many(groups, s, False)[0]
+
+    @staticmethod
+    def debug_blob_cell_batch_intermediates(groups, s, interp_form=0):
+        """(verdicts as verify_blob_cell_proofs_batch_many, [r (32) | [I(tau)]_1 | LL | RL (48 each) per group]); interp_form 0 what the call
+        does, 1 the interpolation from the blobs' coefficients, 2 the column kernel over the computed cells."""
+        res, raw = Kzg._blob_cells_many(groups, s, True, interp_form)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
+    def _blob_cells_many_device(blobs, commitments, cell_proofs, n_per_group, groups, s, interp_form, prep_form, debug):
+        n, G = int(n_per_group), int(groups)
+        if n < 0 or G < 0 or interp_form not in (0, 1, 2) or prep_form not in (0, 1, 2):
+            raise BadArgs("n_per_group, groups, interp_form or prep_form out of range")
+        nb = n * G
+        ptrs = (Kzg._dev(blobs, "blobs", BYTES_PER_BLOB * nb, optional=nb == 0), Kzg._dev(commitments, "commitments", 48 * nb, optional=nb == 0),
+                Kzg._dev(cell_proofs, "cell_proofs", 48 * CELLS_PER_EXT_BLOB * nb, optional=nb == 0))
+        if G == 0:
+            return [], b""
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        if debug:
+            out = C.create_string_buffer(176 * G)
+            rc = lib().kzg355_debug_blob_cell_batch_intermediates_device(out, ok, st, *ptrs, n, G, interp_form, prep_form, s.handle)
+        else:
+            rc = lib().kzg355_verify_blob_cell_proofs_batch_many_device(ok, st, *ptrs, n, G, s.handle)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_cell_proofs_batch_many_device")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_blob_cells") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_cell_proofs_batch_many_device(blobs, commitments, cell_proofs, n_per_group, groups, s):
+        """verify_blob_cell_proofs_batch_many on device memory: blobs (groups * n_per_group * 131072 bytes, uint8), commitments (* 48) and
+        cell_proofs (* 128 * 48), group-major.  Returns a list of bool / Error, one per group, as the host form does."""
+        return Kzg._blob_cells_many_device(blobs, commitments, cell_proofs, n_per_group, groups, s, 0, 0, False)[0]
+
+    @staticmethod
+    def debug_blob_cell_batch_intermediates_device(blobs, commitments, cell_proofs, n_per_group, groups, s, interp_form=0, prep_form=0):
+        """(verdicts, [176 bytes per group]) as debug_blob_cell_batch_intermediates; prep_form 0 by shape, 1 transcripts hashed on the device,
+        2 on the host."""
+        res, raw = Kzg._blob_cells_many_device(blobs, commitments, cell_proofs, n_per_group, groups, s, interp_form, prep_form, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]

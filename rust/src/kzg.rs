@@ -445,6 +445,49 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
     }
 
+    /// Blobs against their EIP-7594 cell proofs, the Fulu counterpart of `verify_blob_kzg_proof_batch`: `cell_proofs` holds the 128 proofs of
+    /// every blob, blob after blob in cell order.  Exactly `verify_cell_kzg_proof_batch` over all 128 cells of every blob, the cells computed on
+    /// the device.
+    pub fn verify_blob_cell_proofs_batch(blobs: &[Blob], commitments: &[KzgCommitment], cell_proofs: &[KzgProof], s: &KzgSettings) -> Result<bool, Error> {
+        let staged = stage_blobs(blobs);
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let p: Vec<u8> = cell_proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = false;
+        // all three lengths cross the boundary: the mismatch check is the library's
+        check(
+            unsafe {
+                ffi::kzg355_verify_blob_cell_proofs_batch(&mut ok, staged.as_ptr(), blobs.len(), c.as_ptr(), commitments.len(), p.as_ptr(), cell_proofs.len(), s.raw)
+            },
+            "verify_blob_cell_proofs_batch",
+        )?;
+        Ok(ok)
+    }
+
+    /// `groups` independent `verify_blob_cell_proofs_batch` calls of `n_per_group` blobs each (inputs group-major): one verdict per transaction.
+    pub fn verify_blob_cell_proofs_batch_many(
+        blobs: &[Blob],
+        commitments: &[KzgCommitment],
+        cell_proofs: &[KzgProof],
+        n_per_group: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let n = blobs.len();
+        if commitments.len() != n || cell_proofs.len() != CELLS_PER_EXT_BLOB * n || n_per_group == 0 || n % n_per_group != 0 {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let groups = n / n_per_group;
+        let staged = stage_blobs(blobs);
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let p: Vec<u8> = cell_proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_verify_blob_cell_proofs_batch_many(ok.as_mut_ptr(), st.as_mut_ptr(), staged.as_ptr(), c.as_ptr(), p.as_ptr(), n_per_group, groups, s.raw)
+        };
+        whole_call(rc, &st[..groups], "verify_blob_cell_proofs_batch_many")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_blob_cells").map(|_| ok[g])).collect())
+    }
+
     /// EIP-7594 `compute_cells_and_kzg_proofs`: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their 128 proofs,
     /// in cell order (FK20 on the device).
     pub fn compute_cells_and_kzg_proofs(blob: &Blob, s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
