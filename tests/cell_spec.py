@@ -135,10 +135,10 @@ def challenge(commitments, cell_indices, cells, proofs):
             uniq.append(c)
         pos.append(uniq.index(c))
     n = len(commitments)
-    t = DOMAIN + N_FE.to_bytes(8, "big") + CELL_FE.to_bytes(8, "big") + len(uniq).to_bytes(8, "big") + n.to_bytes(8, "big") + b"".join(uniq)
-    for k in range(n):
-        t += pos[k].to_bytes(8, "big") + int(cell_indices[k]).to_bytes(8, "big") + bytes(cells[k]) + bytes(proofs[k])
-    return int.from_bytes(hashlib.sha256(t).digest(), "big") % R, uniq, pos
+    t = [DOMAIN + N_FE.to_bytes(8, "big") + CELL_FE.to_bytes(8, "big") + len(uniq).to_bytes(8, "big") + n.to_bytes(8, "big") + b"".join(uniq)]
+    for k in range(n):                                            # (joined once: appending to one bytes object copies it per cell)
+        t.append(pos[k].to_bytes(8, "big") + int(cell_indices[k]).to_bytes(8, "big") + bytes(cells[k]) + bytes(proofs[k]))
+    return int.from_bytes(hashlib.sha256(b"".join(t)).digest(), "big") % R, uniq, pos
 
 
 def verify_cell_kzg_proof_batch(o, commitments, cell_indices, cells, proofs, mono=None, g2=None, intermediates=False):
