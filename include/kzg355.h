@@ -360,6 +360,33 @@ int kzg355_verify_cell_kzg_proof_batch_many(bool *ok /* groups */, int *status /
 int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *ok /* groups */, int *status /* groups or NULL */, const uint8_t *commitments,
                                           const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t n_per_group, size_t groups,
                                           const kzg355_settings *s);
+/* Groups of DIFFERENT sizes in one call, one set of launches for all non-empty groups (the data-column sidecars of many blocks: a sidecar has one
+ * cell per blob of its block).  Layout: with off_g = cell_counts[0] + ... + cell_counts[g-1], group g is entries [off_g, off_g + cell_counts[g]) of
+ * the four arrays, which hold sum of the counts entries each, group after group.
+ * Result per group: EXACTLY that of kzg355_verify_cell_kzg_proof_batch on that slice -- the same verdict, status and challenge r; commitments
+ * deduplicated inside the group only, in order of first appearance; the transcript carries the group's own n.  A count of 0: that group is true /
+ * KZG355_OK.  A cell index >= 128, a cell element >= r, a commitment or proof that fails validate_kzg_g1: that group's KZG355_BADARGS, the others
+ * are left alone; the return value is the first non-OK status in group order.
+ * Refused as a whole (every status marked, every verdict false), decided before any array is read and before any device is touched: a NULL
+ * handle, NULL ok, or NULL cell_counts with groups > 0; a NULL array while the sum of the counts is > 0; a handle of another
+ * FIELD_ELEMENTS_PER_BLOB; groups above 2^24; a sum of the counts that overflows size_t or exceeds 2^18 (the uniform form's limit on
+ * n_per_group * groups).  groups == 0: KZG355_OK, nothing is touched.
+ * Work and device memory are proportional to the sum of the counts (a group of n cells costs its own 3 n + 64 scalar multiplications), not to
+ * groups times the largest.
+ * A handle over several devices: the non-empty groups go to the devices in contiguous ranges, equal in GROUPS -- so the ranges can be uneven in
+ * cells (not measured on several cards).  A group of this call is never cut into blocks, and kzg355_options.force_sharded does not apply to it.
+ * kzg355_settings_cell_calls_per_device counts one launch set per device that received a non-empty group.
+ * Not offered: a device-resident form (the device preparation, k_cell_prep, is built on one n per call), per-transaction blob counts for
+ * kzg355_verify_blob_cell_proofs_batch_many (it needs this call's chain plus ragged forms of its own kernels), cutting a group of this call
+ * over several devices. */
+int kzg355_verify_cell_kzg_proof_batch_many_sets(bool *ok /* groups */, int *status /* groups or NULL */, const size_t *cell_counts /* groups */,
+                                                 const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
+                                                 const uint8_t *proofs /* each: sum of the counts entries, group after group */, size_t groups,
+                                                 const kzg355_settings *s);
+/* Test form of the _many_sets call: out[176 g ..] as kzg355_debug_cell_batch_intermediates lays it out; zero bytes for a group of count 0. */
+int kzg355_debug_cell_batch_intermediates_sets(uint8_t *out /* groups*176 */, bool *ok, int *status, const size_t *cell_counts, const uint8_t *commitments,
+                                               const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t groups,
+                                               const kzg355_settings *s);
 /* The 64 monomial points [tau^t]_1 (t < 64) the handle derived from its Lagrange setup, compressed (building them first if no cell call has). */
 int kzg355_debug_cell_setup_monomial(uint8_t *out /* 64*48 */, const kzg355_settings *s);
 /* compute_cells_and_kzg_proofs of the consensus specs: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their

@@ -187,6 +187,44 @@ struct Kzg {
         return ok;
     }
 
+    // One independent verify_cell_kzg_proof_batch per group, the groups of any sizes (an empty one is true), all in one set of launches.  One
+    // Result per group; a group whose four lengths differ is BadArgs for the call.
+    struct CellGroup {
+        std::vector<KzgCommitment> commitments;
+        std::vector<size_t> cell_indices;
+        std::vector<Cell> cells;
+        std::vector<KzgProof> proofs;
+    };
+    static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_sets(const std::vector<CellGroup> &groups, const KzgSettings &s) {
+        const size_t G = groups.size();
+        std::vector<size_t> counts, indices;
+        std::vector<uint8_t> c, cl, p;
+        for (const CellGroup &g : groups) {
+            const size_t n = g.commitments.size();
+            if (g.cell_indices.size() != n || g.cells.size() != n || g.proofs.size() != n) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(n);
+            indices.insert(indices.end(), g.cell_indices.begin(), g.cell_indices.end());
+            for (size_t i = 0; i < n; i++) {
+                c.insert(c.end(), g.commitments[i].data(), g.commitments[i].data() + 48);
+                cl.insert(cl.end(), g.cells[i].data(), g.cells[i].data() + KZG355_BYTES_PER_CELL);
+                p.insert(p.end(), g.proofs[i].data(), g.proofs[i].data() + 48);
+            }
+        }
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        indices.push_back(0);
+        c.push_back(0); cl.push_back(0); p.push_back(0);
+        std::unique_ptr<bool[]> ok(new bool[G + 1]());
+        std::vector<int> st(G + 1, 0);
+        int rc = kzg355_verify_cell_kzg_proof_batch_many_sets(ok.get(), st.data(), counts.data(), c.data(), indices.data(), cl.data(), p.data(), G, s.raw());
+        st.resize(G);
+        if (whole_call_failed(rc, st)) return from_status(rc, "verify_cell_kzg_proof_batch_many_sets");
+        std::vector<Result<bool>> out;
+        for (size_t g = 0; g < G; g++) {
+            if (st[g]) out.push_back(from_status(st[g], "verify_cell")); else out.push_back(bool(ok[g]));
+        }
+        return out;
+    }
+
     // blobs against their EIP-7594 cell proofs (128 per blob, blob after blob in cell order): the Fulu counterpart of verify_blob_kzg_proof_batch,
     // exactly verify_cell_kzg_proof_batch over all 128 cells of every blob with the cells computed on the device
     static Result<bool> verify_blob_cell_proofs_batch(const std::vector<Blob> &blobs, const std::vector<KzgCommitment> &cs,

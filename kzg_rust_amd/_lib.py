@@ -94,6 +94,8 @@ def load():
         "kzg355_verify_cell_kzg_proof_batch": [bp, u8p, szp, u8p, u8p, sz, vp],
         "kzg355_verify_cell_kzg_proof_batch_many": [bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
         "kzg355_debug_cell_batch_intermediates": [u8p, bp, ip, u8p, szp, u8p, u8p, sz, sz, vp],
+        "kzg355_verify_cell_kzg_proof_batch_many_sets": [bp, ip, szp, u8p, szp, u8p, u8p, sz, vp],
+        "kzg355_debug_cell_batch_intermediates_sets": [u8p, bp, ip, szp, u8p, szp, u8p, u8p, sz, vp],
         "kzg355_debug_cell_setup_monomial": [u8p, vp],
         "kzg355_compute_cells_and_kzg_proofs": [u8p, u8p, u8p, vp],
         "kzg355_compute_cells_and_kzg_proofs_many": [u8p, u8p, ip, u8p, sz, vp],
@@ -164,4 +166,5 @@ EXPORTED_SYMBOLS = [
     "kzg355_settings_cell_calls_per_device",
     "kzg355_verify_blob_cell_proofs_batch", "kzg355_verify_blob_cell_proofs_batch_many", "kzg355_verify_blob_cell_proofs_batch_many_device",
     "kzg355_debug_blob_cell_batch_intermediates", "kzg355_debug_blob_cell_batch_intermediates_device",
+    "kzg355_verify_cell_kzg_proof_batch_many_sets", "kzg355_debug_cell_batch_intermediates_sets",
 ]

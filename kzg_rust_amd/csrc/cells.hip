@@ -117,22 +117,28 @@ static void cell_host_digests(kzg355_settings *s, const uint8_t *commitments, co
 // The four arrays in host memory (the caller's, or a device-resident call's copied back) -> hp; one group per host-pool task.  A launch set
 // takes cells [off, off + cnt) of every group of npg, numbered gi * cnt + k on the device.  The whole group (off 0, cnt npg) is hashed here from
 // the same dedup; a block of it leaves hp.dig alone (the group's digest covers all its cells: cell_host_digests).
+// goff (groups + 1 entries, strictly increasing; npg, off and cnt are then unused): groups of different sizes, each whole -- group gi is entries
+// [goff[gi], goff[gi + 1]) of the caller's arrays and the same cell numbers on the device -- and the meta buffer ends with what the `_sets`
+// kernels find a group by: goff as ints, then the group of every cell.
 static void cell_host_prep(kzg355_settings *s, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t npg,
-                           size_t groups, CellHostPrep &hp, size_t off, size_t cnt) {
-    const bool whole = off == 0 && cnt == npg;
-    const int n = (int)cnt, G = (int)groups;
-    const size_t N = cnt * groups;
-    const int seg_cap = n < CELLS_PER_EXT_BLOB ? n : CELLS_PER_EXT_BLOB;
+                           size_t groups, CellHostPrep &hp, size_t off, size_t cnt_all, const size_t *goff = nullptr) {
+    const bool whole = goff || (off == 0 && cnt_all == npg);
+    const int G = (int)groups;
+    const size_t N = goff ? goff[groups] : cnt_all * groups;
+    // a group has at most min(its cells, 128) segments; until they are packed, group gi's start at seg_at(gi)
+    const size_t seg_cap = cnt_all < (size_t)CELLS_PER_EXT_BLOB ? cnt_all : (size_t)CELLS_PER_EXT_BLOB;
+    auto seg_at = [&](size_t gi) { return goff ? goff[gi] : gi * seg_cap; };
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> &h_uc = hp.uc, &h_dig = hp.dig;
     h_uc.resize(48 * N);
     if (whole) h_dig.resize(32 * groups);
     std::vector<int> h_cell(N), h_cidx(N), h_perm(N);
-    std::vector<int4> h_seg_local((size_t)G * seg_cap);
+    std::vector<int4> h_seg_local(goff ? N : groups * seg_cap);
     std::vector<CellHostGroup> &hg = hp.hg;
     hg.assign(groups, CellHostGroup());
     auto prep = [&](size_t gi) {
-        const size_t base = gi * cnt, src = gi * npg + off;       // the range on the device and in the caller's arrays
+        // the range on the device and in the caller's arrays, and its length
+        const size_t base = goff ? goff[gi] : gi * cnt_all, src = goff ? goff[gi] : gi * npg + off, cnt = goff ? goff[gi + 1] - goff[gi] : cnt_all;
         CellHostGroup &gr = hg[gi];
         for (size_t k = 0; k < cnt; k++) {
             const size_t c = cell_indices[src + k];
@@ -147,12 +153,12 @@ static void cell_host_prep(kzg355_settings *s, const uint8_t *commitments, const
         int acc = 0;
         for (int c = 0; c < CELLS_PER_EXT_BLOB; c++) {
             at[c] = acc;
-            if (ccnt[c]) h_seg_local[gi * seg_cap + gr.n_segs++] = make_int4((int)gi, c, (int)base + acc, ccnt[c]);
+            if (ccnt[c]) h_seg_local[seg_at(gi) + gr.n_segs++] = make_int4((int)gi, c, (int)base + acc, ccnt[c]);
             acc += ccnt[c];
         }
         for (size_t k = 0; k < cnt; k++) h_perm[base + at[h_cell[base + k]]++] = (int)(base + k);
         if (whole)
-            cell_transcript(s, uc, u, h_cidx.data() + base, cell_indices + src, cells + (size_t)CELL_BYTES * src, proofs + 48 * src, npg, h_dig.data() + 32 * gi);
+            cell_transcript(s, uc, u, h_cidx.data() + base, cell_indices + src, cells + (size_t)CELL_BYTES * src, proofs + 48 * src, cnt, h_dig.data() + 32 * gi);
     };
     if (s->host_pool && groups > 1) s->host_pool->parallel_for(groups, prep);
     else for (size_t gi = 0; gi < groups; gi++) prep(gi);
@@ -160,15 +166,20 @@ static void cell_host_prep(kzg355_settings *s, const uint8_t *commitments, const
     for (int gi = 0; gi < G; gi++) h_gseg[gi + 1] = h_gseg[gi] + hg[gi].n_segs;
     const int S = hp.S = h_gseg[G];
     std::vector<int> &meta = hp.meta;
-    meta.resize((size_t)4 * S + (G + 1) + 3 * N);
+    meta.resize((size_t)4 * S + (G + 1) + 3 * N + (goff ? (G + 1) + N : 0));
     {
         int4 *sg = reinterpret_cast<int4 *>(meta.data());
-        for (int gi = 0; gi < G; gi++) memcpy(sg + h_gseg[gi], h_seg_local.data() + (size_t)gi * seg_cap, sizeof(int4) * hg[gi].n_segs);
+        for (int gi = 0; gi < G; gi++) memcpy(sg + h_gseg[gi], h_seg_local.data() + seg_at(gi), sizeof(int4) * hg[gi].n_segs);
         int *q = meta.data() + 4 * (size_t)S;
         memcpy(q, h_gseg.data(), sizeof(int) * (G + 1)); q += G + 1;
         memcpy(q, h_cell.data(), sizeof(int) * N); q += N;
         memcpy(q, h_cidx.data(), sizeof(int) * N); q += N;
-        memcpy(q, h_perm.data(), sizeof(int) * N);
+        memcpy(q, h_perm.data(), sizeof(int) * N); q += N;
+        if (goff) {
+            for (int gi = 0; gi <= G; gi++) q[gi] = (int)goff[gi];
+            q += G + 1;
+            for (int gi = 0; gi < G; gi++) std::fill(q + goff[gi], q + goff[gi + 1], gi);
+        }
     }
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (s->timing) { std::lock_guard<std::mutex> lk(s->mu); auto &k = s->last_ms["cell_host"]; k.last = host_ms; k.total += host_ms; k.count++; }
@@ -197,13 +208,13 @@ bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, siz
 // The workspace's buffers by role: blobs = cells, commitments = unique commitments, q = meta, z = r powers, y = column coefficients, scal_a =
 // lincomb scalars, partials = lincomb terms, lc_partials = the three sums per group, out48 = r | debug output.  N = n * groups cells, S segments;
 // host_input: cells and proofs are uploaded (else read where the caller has them).
-int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints) {
-    const size_t N = (size_t)n * groups, T = (size_t)cell_terms(n);
+// N cells and `terms` lincomb terms in all groups together
+static int cell_reserve_sized(Workspace *w, bool host_input, size_t N, size_t terms, size_t groups, int S, size_t meta_ints) {
     int rc;
     if ((host_input && ((rc = w->blobs.ensure((size_t)CELL_BYTES * N)) || (rc = w->proofs.ensure(48 * N)))) || (rc = w->commitments.ensure(48 * N)) ||
         (rc = w->pts.ensure(sizeof(G1Affine) * 2 * N)) || (rc = w->digests.ensure(32 * groups)) || (rc = w->q.ensure(sizeof(int) * meta_ints)) ||
         (rc = w->z.ensure(sizeof(Fr) * N)) || (rc = w->y.ensure(sizeof(Fr) * CELL_FE * (size_t)(S > 0 ? S : 1))) ||
-        (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * T * groups)) || (rc = w->partials.ensure(sizeof(G1Jac) * T * groups)) ||
+        (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * terms)) || (rc = w->partials.ensure(sizeof(G1Jac) * terms)) ||
         (rc = w->lc_partials.ensure(sizeof(G1Jac) * 3 * groups)) || (rc = w->pair_pts.ensure(sizeof(PairPt) * 2 * groups)) ||
         (rc = w->ok.ensure(sizeof(int) * groups)) || (rc = w->err.ensure(sizeof(int) * groups)) || (rc = w->h_ok.ensure(sizeof(int) * groups)) ||
         (rc = w->h_err.ensure(sizeof(int) * groups)) || (rc = w->out48.ensure((size_t)(32 + CELL_DEBUG_BYTES) * groups)) ||
@@ -211,15 +222,21 @@ int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, siz
         return rc;
     return KZG355_OK;
 }
-// hp and the digests up; with host arrays (cells, proofs not null) also cells [off, off + cnt) of every group of npg and their proofs, group after group
+int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints) {
+    return cell_reserve_sized(w, host_input, (size_t)n * groups, (size_t)cell_terms(n) * groups, groups, S, meta_ints);
+}
+// hp and the digests up; with host arrays (cells, proofs not null) also cells [off, off + cnt) of every group of npg and their proofs, group after group.
+// sets_N: the launch set is sets_N cells in whole groups of different sizes (npg, off and cnt are unused)
 static int cell_upload(Workspace *w, const CellHostPrep &hp, const uint8_t *dig, const uint8_t *cells, const uint8_t *proofs, size_t npg, size_t off,
-                       size_t cnt, size_t groups) {
+                       size_t cnt, size_t groups, size_t sets_N = 0) {
     hipStream_t st = w->stream;
-    HIPCHK(hipMemcpyAsync(w->commitments.p, hp.uc.data(), 48 * cnt * groups, hipMemcpyHostToDevice, st));
+    const bool back_to_back = sets_N || cnt == npg;               // whole groups lie back to back
+    const size_t N = sets_N ? sets_N : cnt * groups;
+    HIPCHK(hipMemcpyAsync(w->commitments.p, hp.uc.data(), 48 * N, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(w->q.p, hp.meta.data(), sizeof(int) * hp.meta.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(w->digests.p, dig, 32 * groups, hipMemcpyHostToDevice, st));
     if (!cells) return KZG355_OK;
-    const size_t runs = cnt == npg ? 1 : groups, len = cnt == npg ? cnt * groups : cnt;       // whole groups lie back to back
+    const size_t runs = back_to_back ? 1 : groups, len = back_to_back ? N : cnt;
     for (size_t g = 0; g < runs; g++) {
         const size_t src = g * npg + off, dst = g * cnt;
         HIPCHK(hipMemcpyAsync(w->proofs.as<uint8_t>() + 48 * dst, proofs + 48 * src, 48 * len, hipMemcpyHostToDevice, st));
@@ -240,13 +257,35 @@ void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, 
     launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
     tm.end();
 }
+// sets_N (not with k0, bi or points_queued): the launch set is sets_N cells in G whole groups of different sizes, n is unused, and the meta buffer
+// ends with the group offsets and the group of every cell (cell_host_prep with goff): the `_sets` entries of the same kernel bodies run, then
+// k_cell_finish and the pairing as for any launch set.
 void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
-                uint8_t *d_dbg, bool points_queued, const BlobInterp *bi) {
-    const size_t N = (size_t)n * G;
+                uint8_t *d_dbg, bool points_queued, const BlobInterp *bi, size_t sets_N) {
+    const size_t N = sets_N ? sets_N : (size_t)n * G;
     hipStream_t st = w->stream;
     const int4 *d_segs = w->q.as<int4>();
     const int *d_gseg = w->q.as<int>() + 4 * (size_t)S, *d_cell = d_gseg + G + 1, *d_cidx = d_cell + N, *d_perm = d_cidx + N;
     uint8_t *d_r = w->out48.as<uint8_t>();
+    if (sets_N) {
+        const int *d_goff = d_perm + N, *d_cgrp = d_goff + G + 1;
+        tm.begin("cell_points");
+        launch_cell_points_sets(w->commitments.as<uint8_t>(), d_proofs, d_goff, d_cgrp, (int)N, w->pts.as<G1Affine>(), w->err.as<int>(), st);
+        tm.end();
+        tm.begin("cell_scalars");
+        launch_cell_scalars_sets(w->digests.as<uint8_t>(), d_cell, d_cidx, d_goff, d_cgrp, (int)N, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(),
+                                 w->scal_a.as<uint32_t>(), d_r, st);
+        tm.end();
+        tm.begin("cell_interp");
+        launch_cell_interp_sets(d_cells, d_perm, d_segs, S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), d_goff, G, w->y.as<Fr>(),
+                                w->scal_a.as<uint32_t>(), w->err.as<int>(), st);
+        tm.end();
+        tm.begin("cell_lincomb");
+        launch_cell_lincomb_sets(w->pts.as<G1Affine>(), s->cell_mono.as<G1Affine>(), w->scal_a.as<uint32_t>(), d_goff, (int)N, G, w->partials.as<G1Jac>(),
+                                 w->lc_partials.as<G1Jac>(), d_r, w->pair_pts.as<PairPt>(), d_dbg, st);
+        tm.end();
+        return;
+    }
     if (!points_queued) cell_chain_points(w, tm, d_proofs, n, G);
     tm.begin("cell_scalars");
     launch_cell_scalars(w->digests.as<uint8_t>(), d_cell, d_cidx, n, G, k0, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(), w->scal_a.as<uint32_t>(), d_r, st);
@@ -268,8 +307,10 @@ void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_ce
 // One set of launches for `groups` whole groups on the device of cs (a replica, for a handle over several devices); the arguments are checked.
 // device = false: the four arrays are host memory (the launch sequence of the host-buffer calls).  device = true: they are device memory on the
 // handle's device; prep_form 0 by size, 1 device preparation, 2 copy back and prepare on the host.
+// goff (host arrays only; groups + 1 entries, strictly increasing; npg is unused): the groups have their own sizes, group i being entries
+// [goff[i], goff[i + 1]) of the four arrays.
 static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
-                       size_t npg, size_t groups, const kzg355_settings *cs, bool device, int prep_form) {
+                       size_t npg, size_t groups, const kzg355_settings *cs, bool device, int prep_form, const size_t *goff = nullptr) {
     auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
     WsGuard g(cs);
     if (!g.w) return refuse(KZG355_NO_DEVICE);
@@ -278,7 +319,7 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     if ((rc = ensure_cell_setup(s, w))) return refuse(rc);
     s->n_cell_sets.fetch_add(1);
     const int n = (int)npg, G = (int)groups;
-    const size_t N = npg * groups;
+    const size_t N = goff ? goff[groups] : npg * groups;
     const int seg_cap = n < CELLS_PER_EXT_BLOB ? n : CELLS_PER_EXT_BLOB;
     hipStream_t st = w->stream;
 
@@ -286,7 +327,7 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     const bool dev_prep = device && !cell_device_call_prepares_on_host(s, npg, groups, prep_form);
     CellHostPrep hp;
     if (!device) {
-        cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, 0, npg);
+        cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, 0, npg, goff);
     } else if (!dev_prep) {
         // into the workspace's pinned staging buffer (kept from call to call): indices | commitments | proofs | cells
         if ((rc = w->h_stage.ensure((sizeof(size_t) + 48 + 48 + (size_t)CELL_BYTES) * N))) return refuse(rc);
@@ -307,7 +348,9 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     const size_t meta_ints = dev_prep ? (size_t)4 * S + (G + 1) + 3 * N + groups + gtab_ints : hp.meta.size();
 
     // ---- device
-    if ((rc = cell_reserve(w, !device, n, groups, S, meta_ints))) return refuse(rc);
+    if ((rc = goff ? cell_reserve_sized(w, true, N, (size_t)cell_terms_sets((int)N, G), groups, S, meta_ints)
+                   : cell_reserve(w, !device, n, groups, S, meta_ints)))
+        return refuse(rc);
     Fp *f12 = nullptr;
     if (w->pair_f.ensure(pairing_f12_bytes(G)) == KZG355_OK) f12 = w->pair_f.as<Fp>();
     if ((rc = launch_set_begin(w, groups, true))) return rc;       // (cell_reserve has sized the words)
@@ -326,10 +369,10 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
                           st);
         tm.end();
         s->n_cell_device_prep.fetch_add(1);
-    } else if ((rc = cell_upload(w, hp, hp.dig.data(), device ? nullptr : cells, proofs, npg, 0, npg, groups))) {
+    } else if ((rc = cell_upload(w, hp, hp.dig.data(), device ? nullptr : cells, proofs, npg, 0, npg, groups, goff ? N : 0))) {
         return rc;
     }
-    cell_chain(s, w, tm, d_cells, d_proofs, S, n, G, 0, true, d_dbg);
+    cell_chain(s, w, tm, d_cells, d_proofs, S, n, G, 0, true, d_dbg, false, nullptr, goff ? N : 0);
     tm.begin("cell_pairing");
     launch_pairing(w->pair_pts.as<PairPt>(), s->cell_t, G, w->ok.as<int>(), st, s->pairing_two_wave_upto, f12, s->pairing_hard12_from, s->miller_segments);
     tm.end();
@@ -485,6 +528,72 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
     return cell_single(ok, status, dbg, commitments, cell_indices, cells, proofs, npg, groups, cs, device, prep_form);
 }
 
+// Groups of different sizes (the `_sets` entry points): group g is entries [off_g, off_g + counts[g]) of the four host arrays, off_g the sum of the
+// counts before it.  Everything that refuses the whole call is decided from the counts alone, before an array is read or a device touched.  An
+// empty group is true / OK on the spot and takes no part in the launch set: the rest are numbered anew, so that the offsets the kernels search
+// are strictly increasing, and their results go back to their places.  The arrays need no packing for that -- an empty group has no entries.
+static const size_t CELL_SETS_MAX_GROUPS = (size_t)1 << 24;
+static int cell_sets_impl(bool *ok, int *status, uint8_t *dbg, const size_t *counts, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
+                          const uint8_t *proofs, size_t groups, const kzg355_settings *cs) {
+    auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
+    if (!cs || !ok || (groups > 0 && !counts)) return refuse(KZG355_BADARGS);
+    if (groups == 0) return KZG355_OK;
+    if (groups > CELL_SETS_MAX_GROUPS) return refuse(KZG355_BADARGS);
+    size_t total = 0, live = 0;
+    for (size_t g = 0; g < groups; g++) {
+        if (counts[g] > CELL_MAX_CELLS - total) return refuse(KZG355_BADARGS);       // (so the sum cannot overflow either)
+        total += counts[g];
+        live += counts[g] != 0;
+    }
+    if (total > 0 && (!commitments || !cell_indices || !cells || !proofs)) return refuse(KZG355_BADARGS);
+    if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
+    // the non-empty groups: where each came from, and the cells before each
+    std::vector<size_t> from(live), goff(live + 1, 0);
+    for (size_t g = 0, l = 0; g < groups; g++) {
+        if (counts[g] == 0) {                                     // verify_cell_kzg_proof_batch of no cells: true
+            ok[g] = true;
+            if (status) status[g] = KZG355_OK;
+            if (dbg) memset(dbg + (size_t)CELL_DEBUG_BYTES * g, 0, CELL_DEBUG_BYTES);
+            continue;
+        }
+        from[l] = g;
+        goff[l + 1] = goff[l] + counts[g];
+        l++;
+    }
+    if (live == 0) return KZG355_OK;
+    // results of the launch set(s) in the order of the non-empty groups (std::vector<bool> has no bool array to hand out)
+    std::unique_ptr<bool[]> l_ok(new bool[live]());
+    std::vector<int> l_st(live, KZG355_OK);
+    std::vector<uint8_t> l_dbg(dbg ? (size_t)CELL_DEBUG_BYTES * live : 0);
+    auto run = [&](const kzg355_settings *on, size_t l0, size_t k) -> int {
+        // groups l0 .. l0 + k - 1: their arrays start at goff[l0], their offsets count from there
+        const size_t c0 = goff[l0];
+        std::vector<size_t> sub(k + 1);
+        for (size_t i = 0; i <= k; i++) sub[i] = goff[l0 + i] - c0;
+        const int rc = cell_single(l_ok.get() + l0, l_st.data() + l0, dbg ? l_dbg.data() + (size_t)CELL_DEBUG_BYTES * l0 : nullptr, commitments + 48 * c0,
+                                   cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, 0, k, on, false, 0, sub.data());
+        return call_failed(rc) ? refuse_call(l_st.data() + l0, k, rc, l_ok.get() + l0) : rc;      // (a failure of the range is every group's of the range)
+    };
+    // A handle over several devices: contiguous ranges of the non-empty groups, one launch set per replica that gets any.  A group is never cut
+    // (and force_sharded does not apply); ranges equal in groups can be uneven in cells.
+    int rc;
+    if (cs->multi) {
+        const size_t D = cs->multi->rep.size();
+        rc = fan_out(cs, live < D ? live : D, live, run);
+    } else {
+        rc = run(cs, 0, live);
+    }
+    int first = KZG355_OK;
+    for (size_t l = 0; l < live; l++) {
+        const size_t g = from[l];
+        ok[g] = l_ok[l];
+        if (status) status[g] = l_st[l];
+        if (dbg) memcpy(dbg + (size_t)CELL_DEBUG_BYTES * g, l_dbg.data() + (size_t)CELL_DEBUG_BYTES * l, CELL_DEBUG_BYTES);
+        if (l_st[l] != KZG355_OK && first == KZG355_OK) first = l_st[l];
+    }
+    return call_failed(rc) ? rc : first;
+}
+
 }  // namespace kzg355_impl
 
 extern "C" {
@@ -508,6 +617,18 @@ int kzg355_debug_cell_batch_intermediates(uint8_t *out, bool *ok, int *status, c
                                           const uint8_t *proofs, size_t n_per_group, size_t groups, const kzg355_settings *s) {
     if (!out) return KZG355_BADARGS;
     return cell_impl(ok, status, out, commitments, cell_indices, cells, proofs, n_per_group, groups, s);
+}
+
+int kzg355_verify_cell_kzg_proof_batch_many_sets(bool *ok, int *status, const size_t *cell_counts, const uint8_t *commitments, const size_t *cell_indices,
+                                                 const uint8_t *cells, const uint8_t *proofs, size_t groups, const kzg355_settings *s) {
+    return cell_sets_impl(ok, status, nullptr, cell_counts, commitments, cell_indices, cells, proofs, groups, s);
+}
+
+int kzg355_debug_cell_batch_intermediates_sets(uint8_t *out, bool *ok, int *status, const size_t *cell_counts, const uint8_t *commitments,
+                                               const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs, size_t groups,
+                                               const kzg355_settings *s) {
+    if (!out) return refuse_call(status, groups, KZG355_BADARGS, ok);
+    return cell_sets_impl(ok, status, out, cell_counts, commitments, cell_indices, cells, proofs, groups, s);
 }
 
 int kzg355_verify_cell_kzg_proof_batch_many_device(bool *ok, int *status, const uint8_t *d_commitments, const size_t *d_cell_indices, const uint8_t *d_cells,

@@ -477,7 +477,8 @@ bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, siz
 int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints);
 void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, int G);
 void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
-                uint8_t *d_dbg, bool points_queued = false, const BlobInterp *bi = nullptr);
+                uint8_t *d_dbg, bool points_queued = false, const BlobInterp *bi = nullptr,
+                size_t sets_N = 0 /* groups of different sizes, sets_N cells in all: cells.hip */);
 
 }  // namespace kzg355_impl
 

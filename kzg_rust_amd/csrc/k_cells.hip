@@ -19,6 +19,7 @@
 #define KZG_MID_INLINE 1
 #include "kernels.h"
 #include "cell_domain.h"
+#include "group_geo.h"
 
 namespace kzg {
 
@@ -67,33 +68,51 @@ __global__ void __launch_bounds__(64) k_cell_lines(const uint8_t *g2_bytes, Line
 }
 
 // ---- per call
+// Every kernel that needs to know where a group lies has ONE body, written against the geometry of group_geo.h, and two entries: the uniform
+// one (every group npg cells; its name and arguments as they always were) and the `_sets` one (every group its own count).  k_cell_columns,
+// k_cell_finish and k_cell_merge work on global cell numbers and per-group slots and have one form.
 // thread (g, k): r of group g from its digest, r^(k0 + k), and the two proof scalars: r^(k0 + k) (LL) and r^(k0 + k) h_k^64 (RL).  k0: the
 // position in its group of the first cell handed to this launch (0 unless the group is cut into blocks)
-__global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, const int *cell_idx, int npg, int groups, int k0, const CellConsts *cc,
-                                                      Fr *rpow, uint32_t *scal, uint8_t *r_out) {
+template <class GEO>
+__device__ __forceinline__ void cell_rpowers_body(const GEO geo, const uint8_t *digests, const int *cell_idx, int n_cells, int k0, const CellConsts *cc,
+                                                  Fr *rpow, uint32_t *scal, uint8_t *r_out) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= npg * groups) return;
-    const int g = gid / npg, k = gid % npg;
-    const int T = cell_terms(npg);
+    if (gid >= n_cells) return;
+    const int g = geo.group_of_cell(gid), k = geo.cell_in_group(gid, g), n = geo.count(g);
+    const size_t t0 = geo.term0(g);
     uint32_t w[8]; be32_to_words(w, digests + 32 * (size_t)g);
     Fr r; fr_from_words(r, w);                                    // int(digest) mod r_BLS
     if (k == 0) fr_to_be32(r_out + 32 * (size_t)g, r);
     const Fr p = fr_pow_small(r, (uint32_t)k0 + (uint32_t)k);
     rpow[gid] = p;
     Fr q; fr_mul(q, p, cc->h64[cell_idx[gid]]);
-    fr_store_words(scal + 8 * ((size_t)g * T + npg + k), q);
-    fr_store_words(scal + 8 * ((size_t)g * T + 2 * npg + CELL_FE + k), p);
+    fr_store_words(scal + 8 * (t0 + n + k), q);
+    fr_store_words(scal + 8 * (t0 + 2 * n + CELL_FE + k), p);
+}
+__global__ void __launch_bounds__(256) k_cell_rpowers(const uint8_t *digests, const int *cell_idx, int npg, int groups, int k0, const CellConsts *cc,
+                                                      Fr *rpow, uint32_t *scal, uint8_t *r_out) {
+    cell_rpowers_body(GroupGeoUniform{npg}, digests, cell_idx, npg * groups, k0, cc, rpow, scal, r_out);
+}
+__global__ void __launch_bounds__(256) k_cell_rpowers_sets(const uint8_t *digests, const int *cell_idx, const int *goff, const int *cgrp, int n_cells,
+                                                           const CellConsts *cc, Fr *rpow, uint32_t *scal, uint8_t *r_out) {
+    cell_rpowers_body(GroupGeoSets{goff, cgrp}, digests, cell_idx, n_cells, 0, cc, rpow, scal, r_out);
 }
 // thread (g, i): weight of unique commitment i = sum of r^k over the cells that carry it (0 for the padding slots)
-__global__ void __launch_bounds__(256) k_cell_weights(const int *cidx, const Fr *rpow, int npg, int groups, uint32_t *scal) {
+template <class GEO> __device__ __forceinline__ void cell_weights_body(const GEO geo, const int *cidx, const Fr *rpow, int n_cells, uint32_t *scal) {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= npg * groups) return;
-    const int g = gid / npg, i = gid % npg;
-    const int *ci = cidx + (size_t)g * npg;
-    const Fr *rp = rpow + (size_t)g * npg;
+    if (gid >= n_cells) return;
+    const int g = geo.group_of_cell(gid), i = geo.cell_in_group(gid, g), n = geo.count(g);
+    const int *ci = cidx + (size_t)geo.first(g);
+    const Fr *rp = rpow + (size_t)geo.first(g);
     Fr acc = fr_zero();
-    for (int k = 0; k < npg; k++) if (ci[k] == i) fr_add(acc, acc, rp[k]);
-    fr_store_words(scal + 8 * ((size_t)g * cell_terms(npg) + i), acc);
+    for (int k = 0; k < n; k++) if (ci[k] == i) fr_add(acc, acc, rp[k]);
+    fr_store_words(scal + 8 * (geo.term0(g) + i), acc);
+}
+__global__ void __launch_bounds__(256) k_cell_weights(const int *cidx, const Fr *rpow, int npg, int groups, uint32_t *scal) {
+    cell_weights_body(GroupGeoUniform{npg}, cidx, rpow, npg * groups, scal);
+}
+__global__ void __launch_bounds__(256) k_cell_weights_sets(const int *cidx, const Fr *rpow, const int *goff, const int *cgrp, int n_cells, uint32_t *scal) {
+    cell_weights_body(GroupGeoSets{goff, cgrp}, cidx, rpow, n_cells, scal);
 }
 // One workgroup per (group, column) segment: lane j sums r^k cell_k[j] over the segment's cells (bytes_to_bls_field on every element read,
 // error into the group's word), the sum goes to LDS at rev6(j) (undoing the bit reversal), then lane t takes coefficient t of the inverse DFT
@@ -122,38 +141,53 @@ __global__ void __launch_bounds__(CELL_FE) k_cell_columns(const uint8_t *cells, 
     coef[(size_t)blockIdx.x * CELL_FE + j] = q;
 }
 // one workgroup per group: I_t = sum over the group's segments; the scalar of monomial point t is -I_t
-__global__ void __launch_bounds__(CELL_FE) k_cell_interp(const Fr *coef, const int *gseg, int npg, uint32_t *scal) {
+template <class GEO> __device__ __forceinline__ void cell_interp_body(const GEO geo, const Fr *coef, const int *gseg, uint32_t *scal) {
     const int g = blockIdx.x, t = threadIdx.x;
     Fr acc = fr_zero();
     for (int s = gseg[g]; s < gseg[g + 1]; s++) fr_add(acc, acc, coef[(size_t)s * CELL_FE + t]);
     Fr neg; fr_sub(neg, fr_zero(), acc);
-    fr_store_words(scal + 8 * ((size_t)g * cell_terms(npg) + 2 * npg + t), neg);
+    fr_store_words(scal + 8 * (geo.term0(g) + 2 * geo.count(g) + t), neg);
+}
+__global__ void __launch_bounds__(CELL_FE) k_cell_interp(const Fr *coef, const int *gseg, int npg, uint32_t *scal) {
+    cell_interp_body(GroupGeoUniform{npg}, coef, gseg, scal);
+}
+__global__ void __launch_bounds__(CELL_FE) k_cell_interp_sets(const Fr *coef, const int *gseg, const int *goff, uint32_t *scal) {
+    cell_interp_body(GroupGeoSets{goff, nullptr}, coef, gseg, scal);
 }
 // thread (g, term): [scalar] point.  Terms of a group: [0, n) unique commitments, [n, 2n) proofs (RL), [2n, 2n + 64) monomial points,
 // [2n + 64, 3n + 64) proofs (LL).  pts is [group][commitments | proofs] as launch_decompress_points writes it.
-__global__ void __launch_bounds__(64) k_cell_terms(const G1Affine *pts, const G1Affine *mono, const uint32_t *scal, int npg, int groups, G1Jac *partials) {
-    const int T = cell_terms(npg);
+template <class GEO>
+__device__ __forceinline__ void cell_terms_body(const GEO geo, const G1Affine *pts, const G1Affine *mono, const uint32_t *scal, size_t n_terms, int groups,
+                                                G1Jac *partials) {
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (size_t)T * groups) return;
-    const int g = (int)(gid / T), e = (int)(gid % T);
-    const G1Affine *gp = pts + (size_t)g * 2 * npg;
-    const G1Affine p = e < 2 * npg ? gp[e] : e < 2 * npg + CELL_FE ? mono[e - 2 * npg] : gp[npg + (e - 2 * npg - CELL_FE)];
+    if (gid >= n_terms) return;
+    const int g = geo.group_of_term(gid, groups), e = (int)(gid - geo.term0(g)), n = geo.count(g);
+    const G1Affine *gp = pts + geo.pts0(g);
+    const G1Affine p = e < 2 * n ? gp[e] : e < 2 * n + CELL_FE ? mono[e - 2 * n] : gp[n + (e - 2 * n - CELL_FE)];
     uint32_t k[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) k[i] = scal[8 * gid + i];
     G1Jac r; g1_mul_words(r, p, k, 8);
     partials[gid] = r;
 }
+__global__ void __launch_bounds__(64) k_cell_terms(const G1Affine *pts, const G1Affine *mono, const uint32_t *scal, int npg, int groups, G1Jac *partials) {
+    cell_terms_body(GroupGeoUniform{npg}, pts, mono, scal, (size_t)cell_terms(npg) * groups, groups, partials);
+}
+__global__ void __launch_bounds__(64) k_cell_terms_sets(const G1Affine *pts, const G1Affine *mono, const uint32_t *scal, const int *goff, int n_terms,
+                                                        int groups, G1Jac *partials) {
+    cell_terms_body(GroupGeoSets{goff, nullptr}, pts, mono, scal, (size_t)n_terms, groups, partials);
+}
 // workgroup (g, side): side 0 = terms [0, 2n) (commitments, RL proofs), 1 = [2n, 2n + 64) (= -[I(tau)]), 2 = [2n + 64, 3n + 64) (LL)
 constexpr int CELL_SUM_THREADS = 256;
-__global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum(const G1Jac *partials, int npg, G1Jac *sums) {
+template <class GEO> __device__ __forceinline__ void cell_sum_body(const GEO geo, const G1Jac *partials, G1Jac *sums) {
     __shared__ G1Jac red[CELL_SUM_THREADS];
     const int g = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
-    const int T = cell_terms(npg);
-    const int lo = side == 0 ? 0 : side == 1 ? 2 * npg : 2 * npg + CELL_FE;
-    const int hi = side == 0 ? 2 * npg : side == 1 ? 2 * npg + CELL_FE : T;
+    const int n = geo.count(g);
+    const G1Jac *gt = partials + geo.term0(g);
+    const int lo = side == 0 ? 0 : side == 1 ? 2 * n : 2 * n + CELL_FE;
+    const int hi = side == 0 ? 2 * n : side == 1 ? 2 * n + CELL_FE : cell_terms(n);
     G1Jac acc = g1_inf();
-    for (int e = lo + tid; e < hi; e += CELL_SUM_THREADS) g1_add(acc, acc, partials[(size_t)g * T + e]);
+    for (int e = lo + tid; e < hi; e += CELL_SUM_THREADS) g1_add(acc, acc, gt[e]);
     red[tid] = acc;
     __syncthreads();
     for (int s = CELL_SUM_THREADS / 2; s > 0; s >>= 1) {
@@ -161,6 +195,12 @@ __global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum(const G1Jac *part
         __syncthreads();
     }
     if (tid == 0) sums[3 * (size_t)g + side] = red[0];
+}
+__global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum(const G1Jac *partials, int npg, G1Jac *sums) {
+    cell_sum_body(GroupGeoUniform{npg}, partials, sums);
+}
+__global__ void __launch_bounds__(CELL_SUM_THREADS) k_cell_sum_sets(const G1Jac *partials, const int *goff, G1Jac *sums) {
+    cell_sum_body(GroupGeoSets{goff, nullptr}, partials, sums);
 }
 // The end of a group's check from its three sums a (commitments + RL proofs), b (= -[I(tau)]_1) and ll: the pairing arguments (-LL, RL) and, with
 // o, r | [I(tau)]_1 | LL | RL compressed (CELL_DEBUG_BYTES)
@@ -222,11 +262,24 @@ void launch_cell_scalars(const uint8_t *d_digests, const int *d_cell_idx, const 
     hipLaunchKernelGGL(k_cell_rpowers, dim3((n + 255) / 256), dim3(256), 0, st, d_digests, d_cell_idx, npg, groups, k0, d_cc, d_rpow, d_scal, d_r_be);
     hipLaunchKernelGGL(k_cell_weights, dim3((n + 255) / 256), dim3(256), 0, st, d_cidx, d_rpow, npg, groups, d_scal);
 }
+void launch_cell_scalars_sets(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, const int *d_goff, const int *d_cgrp, int n_cells,
+                              const CellConsts *d_cc, Fr *d_rpow, uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st) {
+    if (n_cells <= 0) return;
+    hipLaunchKernelGGL(k_cell_rpowers_sets, dim3((n_cells + 255) / 256), dim3(256), 0, st, d_digests, d_cell_idx, d_goff, d_cgrp, n_cells, d_cc, d_rpow, d_scal,
+                       d_r_be);
+    hipLaunchKernelGGL(k_cell_weights_sets, dim3((n_cells + 255) / 256), dim3(256), 0, st, d_cidx, d_rpow, d_goff, d_cgrp, n_cells, d_scal);
+}
 void launch_cell_interp(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg, const Fr *d_rpow, const CellConsts *d_cc,
                         int npg, int groups, Fr *d_coef, uint32_t *d_scal, int *d_err, hipStream_t st) {
     if (groups <= 0) return;
     if (n_segs > 0) hipLaunchKernelGGL(k_cell_columns, dim3(n_segs), dim3(CELL_FE), 0, st, d_cells, d_perm, d_segs, d_rpow, d_cc, d_coef, d_err);
     hipLaunchKernelGGL(k_cell_interp, dim3(groups), dim3(CELL_FE), 0, st, d_coef, d_gseg, npg, d_scal);
+}
+void launch_cell_interp_sets(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg, const Fr *d_rpow,
+                             const CellConsts *d_cc, const int *d_goff, int groups, Fr *d_coef, uint32_t *d_scal, int *d_err, hipStream_t st) {
+    if (groups <= 0) return;
+    if (n_segs > 0) hipLaunchKernelGGL(k_cell_columns, dim3(n_segs), dim3(CELL_FE), 0, st, d_cells, d_perm, d_segs, d_rpow, d_cc, d_coef, d_err);
+    hipLaunchKernelGGL(k_cell_interp_sets, dim3(groups), dim3(CELL_FE), 0, st, d_coef, d_gseg, d_goff, d_scal);
 }
 void launch_cell_sums(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, int npg, int groups, G1Jac *d_partials, G1Jac *d_sums,
                       hipStream_t st) {
@@ -239,6 +292,14 @@ void launch_cell_lincomb(const G1Affine *d_pts, const G1Affine *d_mono, const ui
                          const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st) {
     if (groups <= 0) return;
     launch_cell_sums(d_pts, d_mono, d_scal, npg, groups, d_partials, d_sums, st);
+    hipLaunchKernelGGL(k_cell_finish, dim3((groups + 63) / 64), dim3(64), 0, st, d_sums, groups, d_r_be, d_pair_pts, d_dbg);
+}
+void launch_cell_lincomb_sets(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, const int *d_goff, int n_cells, int groups,
+                              G1Jac *d_partials, G1Jac *d_sums, const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st) {
+    if (groups <= 0) return;
+    const int terms = cell_terms_sets(n_cells, groups);
+    hipLaunchKernelGGL(k_cell_terms_sets, dim3((unsigned)((terms + 63) / 64)), dim3(64), 0, st, d_pts, d_mono, d_scal, d_goff, terms, groups, d_partials);
+    hipLaunchKernelGGL(k_cell_sum_sets, dim3(groups, 3), dim3(CELL_SUM_THREADS), 0, st, d_partials, d_goff, d_sums);
     hipLaunchKernelGGL(k_cell_finish, dim3((groups + 63) / 64), dim3(64), 0, st, d_sums, groups, d_r_be, d_pair_pts, d_dbg);
 }
 bool launch_cell_merge(const G1Jac *d_parts, int blocks, int groups, const uint8_t *d_r_be, int r_first, int r_stride, PairPt *d_pair_pts, uint8_t *d_dbg,

@@ -215,6 +215,22 @@ void launch_cell_sums(const G1Affine *d_pts, const G1Affine *d_mono, const uint3
 constexpr int CELL_MERGE_MAX_BLOCKS = 64;
 bool launch_cell_merge(const G1Jac *d_parts, int blocks, int groups, const uint8_t *d_r_be, int r_first, int r_stride, PairPt *d_pair_pts, uint8_t *d_dbg,
                        hipStream_t st);
+// Groups of different sizes in one launch set (kzg355_verify_cell_kzg_proof_batch_many_sets): cells are numbered group after group, d_goff
+// (groups + 1 ints) holds the cells before each group and must be STRICTLY increasing (the host drops empty groups), d_cgrp (n_cells ints) the
+// group of each cell.  Group g's points start at 2 d_goff[g] and its cell_terms(count) lincomb terms at 3 d_goff[g] + 64 g, in the uniform
+// form's order; d_scal and d_partials hold cell_terms_sets(n_cells, groups) terms.  The bodies are those of the uniform kernels (group_geo.h).
+// (int: at most 2^18 cells in at most 2^18 groups are 67 * 2^18 terms)
+KZG_HD int cell_terms_sets(int n_cells, int groups) { return 3 * n_cells + CELL_FE * groups; }
+void launch_cell_scalars_sets(const uint8_t *d_digests, const int *d_cell_idx, const int *d_cidx, const int *d_goff, const int *d_cgrp, int n_cells,
+                              const CellConsts *d_cc, Fr *d_rpow, uint32_t *d_scal, uint8_t *d_r_be, hipStream_t st);
+void launch_cell_interp_sets(const uint8_t *d_cells, const int *d_perm, const int4 *d_segs, int n_segs, const int *d_gseg, const Fr *d_rpow,
+                             const CellConsts *d_cc, const int *d_goff, int groups, Fr *d_coef, uint32_t *d_scal, int *d_err, hipStream_t st);
+void launch_cell_lincomb_sets(const G1Affine *d_pts, const G1Affine *d_mono, const uint32_t *d_scal, const int *d_goff, int n_cells, int groups,
+                              G1Jac *d_partials, G1Jac *d_sums, const uint8_t *d_r_be, PairPt *d_pair_pts, uint8_t *d_dbg, hipStream_t st);
+// validate_kzg_g1 on such a launch set's points (k_cell_points.hip): launch_decompress_points and launch_subgroup_points with the slots and the error
+// words of the ragged layout; d_commitments holds n_cells unique-commitment slots, group after group
+void launch_cell_points_sets(const uint8_t *d_commitments, const uint8_t *d_proofs, const int *d_goff, const int *d_cgrp, int n_cells, G1Affine *d_pts,
+                             int *d_err, hipStream_t st);
 // ---- k_cell_prep.hip: what the host prepares per group of a cell batch, from inputs that are in HBM already (the *_device entry points)
 constexpr int CELL_PREP_LDS_SLOTS = 8192;      // slots of the dedup table k_cell_prep keeps in LDS; a larger table lives in d_gtab
 constexpr int CELL_PREP_MAX_CELLS = 16384;     // cells per group up to which the device prepares (128 blobs x 128 cells: a block as one batch)

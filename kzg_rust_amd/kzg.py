@@ -521,6 +521,40 @@ class Kzg:
         return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
 
     @staticmethod
+    def _cell_many_sets(groups, s, debug):
+        flat = [[], [], [], []]
+        counts = []
+        for grp in groups:
+            arrs = Kzg._cell_arrays(*grp)                          # a group whose four lists differ in length: BadArgs, before any FFI call
+            counts.append(len(arrs[0]))
+            for f, a in zip(flat, arrs):
+                f += a
+        G = len(counts)
+        ok = (C.c_bool * max(G, 1))()
+        st = (C.c_int * max(G, 1))()
+        cnt = (C.c_size_t * max(G, 1))(*counts)
+        idx = (C.c_size_t * max(len(flat[1]), 1))(*flat[1])
+        args = (ok, st, cnt, b"".join(flat[0]), idx, b"".join(flat[2]), b"".join(flat[3]), G, s.handle)
+        out = C.create_string_buffer(176 * max(G, 1)) if debug else None
+        rc = lib().kzg355_debug_cell_batch_intermediates_sets(out, *args) if debug else lib().kzg355_verify_cell_kzg_proof_batch_many_sets(*args)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_cell_kzg_proof_batch_many_sets")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_cell") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_cell_kzg_proof_batch_many_sets(groups, s):
+        """verify_cell_kzg_proof_batch_many for groups of any sizes (an empty group is True): list of (commitments, cell_indices, cells, proofs),
+        one independent verify_cell_kzg_proof_batch per group, all of them in one set of launches.  Returns a list of bool / Error."""
+        return Kzg._cell_many_sets(groups, s, False)[0]
+
+    @staticmethod
+    def debug_cell_batch_intermediates_sets(groups, s):
+        """(verdicts as verify_cell_kzg_proof_batch_many_sets, [r (32) | [I(tau)]_1 | LL | RL (48 each) per group; zero bytes for an empty group])."""
+        res, raw = Kzg._cell_many_sets(groups, s, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
     def debug_cell_setup_monomial(s):
         """The 64 monomial points [tau^t]_1 the handle derived for the cell check, compressed."""
         out = C.create_string_buffer(64 * 48)

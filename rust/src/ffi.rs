@@ -88,6 +88,13 @@ extern "C" {
                                               s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_cell_kzg_proof_batch_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, cell_indices: *const usize, cells: *const u8,
                                                    proofs: *const u8, n_per_group: usize, groups: usize, s: *const kzg355_settings) -> c_int;
+    // groups of different sizes: group g is cell_counts[g] entries of the four arrays, after those of group g - 1
+    pub fn kzg355_verify_cell_kzg_proof_batch_many_sets(ok: *mut bool, status: *mut c_int, cell_counts: *const usize, commitments: *const u8,
+                                                        cell_indices: *const usize, cells: *const u8, proofs: *const u8, groups: usize,
+                                                        s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_debug_cell_batch_intermediates_sets(out: *mut u8, ok: *mut bool, status: *mut c_int, cell_counts: *const usize, commitments: *const u8,
+                                                      cell_indices: *const usize, cells: *const u8, proofs: *const u8, groups: usize,
+                                                      s: *const kzg355_settings) -> c_int;
     // EIP-7594 cells and their proofs: cells_out 128*2048 (n*128*2048), proofs_out 128*48 (n*128*48), either may be null
     pub fn kzg355_compute_cells_and_kzg_proofs(cells_out: *mut u8, proofs_out: *mut u8, blob: *const u8, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_compute_cells_and_kzg_proofs_many(cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int, blobs: *const u8, n: usize,

@@ -445,6 +445,43 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
     }
 
+    /// `verify_cell_kzg_proof_batch_many` for groups of different sizes: group `g` is `cell_counts[g]` entries of the four slices, after those of
+    /// group `g - 1`; an empty group is `Ok(true)`.  All non-empty groups run in one set of launches.
+    pub fn verify_cell_kzg_proof_batch_many_sets(
+        cell_counts: &[usize],
+        commitments: &[KzgCommitment],
+        cell_indices: &[usize],
+        cells: &[Cell],
+        proofs: &[KzgProof],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let n = commitments.len();
+        let total = cell_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c));
+        if cell_indices.len() != n || cells.len() != n || proofs.len() != n || total != Some(n) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let groups = cell_counts.len();
+        // (one spare entry each: the pointer of an empty Vec is not one the library may be handed)
+        let mut counts = cell_counts.to_vec();
+        counts.push(0);
+        let mut idx = cell_indices.to_vec();
+        idx.push(0);
+        let mut c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        c.push(0);
+        let mut cl: Vec<u8> = cells.iter().flat_map(|x| x.iter().copied()).collect();
+        cl.push(0);
+        let mut p: Vec<u8> = proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        p.push(0);
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_verify_cell_kzg_proof_batch_many_sets(ok.as_mut_ptr(), st.as_mut_ptr(), counts.as_ptr(), c.as_ptr(), idx.as_ptr(), cl.as_ptr(),
+                                                              p.as_ptr(), groups, s.raw)
+        };
+        whole_call(rc, &st[..groups], "verify_cell_kzg_proof_batch_many_sets")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
+    }
+
     /// Blobs against their EIP-7594 cell proofs, the Fulu counterpart of `verify_blob_kzg_proof_batch`: `cell_proofs` holds the 128 proofs of
     /// every blob, blob after blob in cell order.  Exactly `verify_cell_kzg_proof_batch` over all 128 cells of every blob, the cells computed on
     /// the device.
