@@ -430,6 +430,39 @@ int kzg355_recover_cells_and_kzg_proofs_many_sets(uint8_t *cells_out /* m*128*20
                                                   int *status /* m or NULL */, const size_t *cell_counts /* m */,
                                                   const size_t *cell_indices /* sum of the counts */,
                                                   const uint8_t *cells /* (sum of the counts)*2048 */, size_t m, const kzg355_settings *s);
+/* ---- proofs of chosen cells ----------------------------------------------------------------------------------------------------------------
+ * The cells of a blob at k chosen indices and their proofs.  kzg355_compute_cells_and_kzg_proofs runs the whole FK20 chain whatever is wanted
+ * of its 128 proofs; here every (blob, index) pair is computed on its own -- the proof as the commitment to the quotient of the blob polynomial
+ * by X^64 - a_index, through the fixed-base MSM of the commitment calls -- so that a few proofs of a blob cost a few MSMs (a node that
+ * custodies a handful of columns, a server that answers one sample request).  All 128 proofs of many blobs remain the other call's work.
+ * Layout: slot j holds cell cell_indices[j] of the blob and its proof, byte for byte what kzg355_compute_cells_and_kzg_proofs returns at that
+ * index.  Each index is < 128; they may come in any order and may repeat.  k may be 0 (the blob is still read and checked) and may not exceed
+ * 128.  Either output may be NULL, not both (KZG355_BADARGS); without proofs_out no MSM runs and no MSM table is built.  A blob element >= r, an
+ * index >= 128 or k > 128 -> KZG355_BADARGS.  The first call that wants proofs builds the handle's fixed-base MSM table, exactly as the first
+ * commitment does (kzg355_options.msm_bits; kzg355_settings_build_msm_table builds it ahead of time); a handle loaded with msm_bits = 8 runs
+ * the bucket form and gives the same bytes.  Mainnet handles only. */
+int kzg355_compute_cell_kzg_proofs_at(uint8_t *cells_out /* k*2048 or NULL */, uint8_t *proofs_out /* k*48 or NULL */, const uint8_t *blob,
+                                      const size_t *cell_indices /* k */, size_t k, const kzg355_settings *s);
+/* n independent calls of the above in one set of launches: blob i asks for cell_counts[i] cells; with off_i = cell_counts[0] + .. +
+ * cell_counts[i-1], its indices are cell_indices[off_i .. off_i + cell_counts[i]) and output slot off_i + j holds cell cell_indices[off_i + j]
+ * of blob i and its proof.  A count may be 0: that blob is still read and checked, and it fills no slot.  What is wrong with one blob is that
+ * blob's KZG355_BADARGS: an element >= r, an index >= 128, a count > 128.  The other blobs are computed and are right: the layout always follows
+ * the counts as given.  The return value is the first non-OK status; the output slots of a refused blob are unspecified.  What is wrong with
+ * the call refuses it as a whole and marks every status: a NULL handle, both outputs NULL, NULL blobs, cell_counts or cell_indices with n > 0
+ * (cell_indices may be NULL when the sum of the counts is 0), a handle of another FIELD_ELEMENTS_PER_BLOB, n > 2^32, a sum of the counts that
+ * overflows size_t (or does so times 2048).  n == 0 -> OK, and nothing is touched.  A handle over several devices spreads contiguous ranges of
+ * blobs over them, each range's indices and slots starting at the sum of the counts before it (a blob is never cut), and every range counts in
+ * kzg355_settings_cell_calls_per_device.  Large calls run in chunks of whole blobs. */
+int kzg355_compute_cell_kzg_proofs_at_many(uint8_t *cells_out /* (sum of the counts)*2048 or NULL */, uint8_t *proofs_out /* (sum)*48 or NULL */,
+                                           int *status /* n or NULL */, const uint8_t *blobs /* n*131072 */, size_t n,
+                                           const size_t *cell_counts /* n */, const size_t *cell_indices /* sum of the counts */,
+                                           const kzg355_settings *s);
+/* The same with the blobs and both outputs in HBM: device pointers on the handle's device (its first device, for a handle over several: the
+ * call runs on that device alone), 16-byte aligned -- a misaligned pointer refuses the call as a whole; status, counts and indices stay HOST
+ * arguments.  The blobs are read and the slots written where they are; nothing but the pair list and the status words crosses PCIe. */
+int kzg355_compute_cell_kzg_proofs_at_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status /* host */, const uint8_t *d_blobs, size_t n,
+                                                  const size_t *cell_counts /* HOST */, const size_t *cell_indices /* HOST */,
+                                                  const kzg355_settings *s);
 /* Test form: the FK20 intermediates H_0 .. H_63 of each blob, compressed (H_e = sum_{m >= 64(e+1)} f_m [tau^(m - 64(e+1))]_1; H_63 = infinity). */
 int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
 /* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */

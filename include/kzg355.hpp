@@ -305,6 +305,59 @@ struct Kzg {
         return out;
     }
 
+    // The cells of a blob at chosen indices (each < 128, any order, repeats allowed) and their proofs, entry j what compute_cells_and_kzg_proofs
+    // returns at cell_indices[j]: every index through its own quotient and one MSM instead of the FK20 chain
+    static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cell_kzg_proofs_at(const Blob &blob, const std::vector<size_t> &cell_indices,
+                                                                                                  const KzgSettings &s) {
+        const size_t k = cell_indices.size();
+        std::vector<uint8_t> c((k + 1) * KZG355_BYTES_PER_CELL), p((k + 1) * 48);
+        std::vector<size_t> indices(cell_indices);
+        indices.push_back(0);                                      // (data() of an empty vector may be null)
+        int rc = kzg355_compute_cell_kzg_proofs_at(c.data(), p.data(), blob.data(), indices.data(), k, s.raw());
+        if (rc) return from_status(rc, "compute_cell_kzg_proofs_at");
+        std::pair<std::vector<Cell>, std::vector<KzgProof>> out;
+        for (size_t j = 0; j < k; j++) {
+            out.first.push_back(Cell::from_bytes(&c[j * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+            out.second.push_back(KzgProof::from_bytes(&p[j * 48], 48).value());
+        }
+        return out;
+    }
+
+    // One independent compute_cell_kzg_proofs_at per blob, each with its own index list (which may be empty), in one set of launches.  One Result
+    // per blob; blobs and index_lists of different lengths are BadArgs for the call.
+    static Result<std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>>> compute_cell_kzg_proofs_at_many(
+        const std::vector<Blob> &blobs, const std::vector<std::vector<size_t>> &index_lists, const KzgSettings &s) {
+        const size_t n = blobs.size();
+        if (index_lists.size() != n) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<size_t> counts, indices;
+        std::vector<uint8_t> in(n * BYTES_PER_BLOB + 1);
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(&in[i * BYTES_PER_BLOB], blobs[i].data(), BYTES_PER_BLOB);
+            counts.push_back(index_lists[i].size());
+            indices.insert(indices.end(), index_lists[i].begin(), index_lists[i].end());
+        }
+        const size_t total = indices.size();
+        std::vector<uint8_t> c((total + 1) * KZG355_BYTES_PER_CELL), p((total + 1) * 48);
+        std::vector<int> st(n + 1, 0);
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        indices.push_back(0);
+        int rc = kzg355_compute_cell_kzg_proofs_at_many(c.data(), p.data(), st.data(), in.data(), n, counts.data(), indices.data(), s.raw());
+        st.resize(n);
+        if (whole_call_failed(rc, st)) return from_status(rc, "compute_cell_kzg_proofs_at_many");
+        std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>> out;
+        size_t off = 0;
+        for (size_t i = 0; i < n; off += counts[i], i++) {
+            if (st[i]) { out.push_back(from_status(st[i], "compute_cell_kzg_proofs_at")); continue; }
+            std::pair<std::vector<Cell>, std::vector<KzgProof>> r;
+            for (size_t j = off; j < off + counts[i]; j++) {
+                r.first.push_back(Cell::from_bytes(&c[j * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+                r.second.push_back(KzgProof::from_bytes(&p[j * 48], 48).value());
+            }
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+
     // ---- the three cell calls on device-resident data (kzg355.h: pointer and alignment rules).  The d_* arguments are device pointers on the
     // handle's device; one Result per unit, an Err of the call itself only for whole-call failures (whole_call_failed, below).
     static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_device(const uint8_t *d_commitments, const size_t *d_cell_indices,

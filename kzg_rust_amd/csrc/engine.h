@@ -12,6 +12,7 @@
 //   cell_compute.hip   compute_cells_and_kzg_proofs: the setups, the chunk loop the recover call shares
 //   cell_recover.hip   recover_cells_and_kzg_proofs: index sets, the erasure decoding's field stage
 //   blob_cells.hip     verify_blob_cell_proofs_batch: blobs against all their cell proofs, the extension and the check in one launch set
+//   cell_proofs_at.hip compute_cell_kzg_proofs_at: the proofs of chosen cells, each the commitment to its own quotient (kernels: k_cell_quotient.hip)
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
 // entry point returns KZG355_NO_DEVICE (a HIP call that fails on a device that exists: KZG355_DEVICE_ERROR).
@@ -440,6 +441,9 @@ HostFront *resident_front(kzg355_settings *s, HostFront &hf, const uint8_t *d_co
 int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, size_t npg, size_t groups,
                             const kzg355_settings *cs);
 int ensure_wide_table(kzg355_settings *s);
+// n MSMs over the handle's Lagrange points, scalars from blobs or (d_scalars: n * 4096 Montgomery Fr, blob order) as given: the 48-byte results in
+// w->out48 (msm_to_device), and copied on to w->h_out (msm_to_host)
+int msm_to_device(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_t *d_blobs, const Fr *d_scalars);
 int msm_to_host(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_t *d_blobs, const Fr *d_scalars);
 int prove_common(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blobs, int n);
 // d_zs (device, n x 32 bytes, or null): proofs at these points instead of each blob's Fiat-Shamir challenge (compute_kzg_proof; d_c is then null), and
@@ -457,6 +461,7 @@ int host_many(const HostCall &hc, size_t units, const kzg355_settings *cs);
 // cell_compute.hip: the monomial points of the cell setups (also cells.hip), and what compute_cells_and_kzg_proofs and
 // recover_cells_and_kzg_proofs (cell_recover.hip: its own field stage) share
 static const size_t CC_CHUNK = 512;        // blobs per launch set (about 0.8 MB of device memory per blob)
+static const size_t CQ_CHUNK = 1152;       // (blob, cell) pairs per launch set of compute_cell_kzg_proofs_at: 128 KiB of MSM scalars per pair, 151 MB
 int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
 int ensure_cc_consts(kzg355_settings *s, Workspace *w);
 int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);

@@ -284,6 +284,15 @@ void launch_cc_columns(const Fr *d_coef, int n, const CellComputeConsts *d_cc, u
 void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *d_Z, hipStream_t st);
 void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
 
+// ---- k_cell_quotient.hip: compute_cell_kzg_proofs_at, the proofs of chosen cells (mainnet handles only)
+// a (blob, cell) pair of a chunk: the blob's place in the chunk, the cell index (< 128), and the slot its cell is gathered into
+struct CqPair { uint32_t blob, cell; uint64_t slot; };
+// d_coef and d_err (per blob of the chunk) as launch_cc_field leaves them; d_scal: pairs * 4096 Fr, Montgomery, in blob order -- the d_scalars of
+// launch_msm_wide / launch_digits_from_fr (zeros for a blob whose error word is set)
+void launch_cq_quotient(const Fr *d_coef, const CqPair *d_pairs, int pairs, const int *d_err, const CellComputeConsts *d_cc, Fr *d_scal, hipStream_t st);
+// d_cells as launch_cc_field leaves them (128 cells per blob of the chunk); pair p's cell goes to d_out + 2048 * d_pairs[p].slot
+void launch_cq_gather(const uint8_t *d_cells, const CqPair *d_pairs, int pairs, uint8_t *d_out, hipStream_t st);
+
 // ---- k_cell_recover.hip: the field stage of recover_cells_and_kzg_proofs (64..128 known cells -> coefficients and all 128 cells; mainnet handles only)
 struct RecoverTables {                                        // one per distinct index set of a chunk
     Fr sd[CELLS_PER_EXT_BLOB];                               // S(a_k) / (64 * 128), S the vanishing polynomial of the missing cells' a_m

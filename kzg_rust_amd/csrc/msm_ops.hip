@@ -91,14 +91,13 @@ int ensure_wide_table(kzg355_settings *s) {
     return s->msm_required ? s->wide_rc : KZG355_OK;
 }
 
-// MSM -> 48-byte outputs on the host.  Wide-window table form if the handle has the table (scalars straight from the blobs,
+// MSM -> 48-byte outputs in w->out48.  Wide-window table form if the handle has the table (scalars straight from the blobs,
 // or from Montgomery field elements for the quotient), else the 8-bit bucket form over a digit buffer.
-int msm_to_host(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_t *d_blobs, const Fr *d_scalars) {
+int msm_to_device(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_t *d_blobs, const Fr *d_scalars) {
     int rc;
     if ((rc = ensure_wide_table(s))) return rc;
     if ((rc = w->partials.ensure(sizeof(G1Jac) * (size_t)n * MSM_WINDOWS))) return rc;
     if ((rc = w->out48.ensure(48 * (size_t)n))) return rc;
-    if ((rc = w->h_out.ensure(48 * (size_t)n))) return rc;
     const kzg355_settings::WidePub *wp = tl_force_bucket ? nullptr : tl_wide_candidate ? tl_wide_candidate : s->wide_pub.load(std::memory_order_acquire);
     if (wp) {
         DeviceTables t = s->t;
@@ -114,6 +113,12 @@ int msm_to_host(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_
         tm.begin("msm_bucket"); launch_msm_bucket(w->digits.as<uint8_t>(), s->t, n, w->partials.as<G1Jac>(), w->stream); tm.end();
         tm.begin("msm_finalize"); launch_msm_finalize(w->partials.as<G1Jac>(), n, w->out48.as<uint8_t>(), w->stream); tm.end();
     }
+    return KZG355_OK;
+}
+// ... and on their way to the host, in w->h_out
+int msm_to_host(kzg355_settings *s, Workspace *w, Timed &tm, int n, const uint8_t *d_blobs, const Fr *d_scalars) {
+    int rc;
+    if ((rc = w->h_out.ensure(48 * (size_t)n)) || (rc = msm_to_device(s, w, tm, n, d_blobs, d_scalars))) return rc;
     HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 48 * (size_t)n, hipMemcpyDeviceToHost, w->stream));
     return KZG355_OK;
 }

@@ -703,6 +703,57 @@ class Kzg:
         """The cells alone, per unit a list of 128 cells or Error (no proof is computed and no proof setup built)."""
         return [r if isinstance(r, Error) else r[0] for r in Kzg._recover_sets(units, s, True, False)]
 
+    # ---- proofs of chosen EIP-7594 cells of a blob (compute_cell_kzg_proofs_at): every (blob, cell) pair through its own quotient and one MSM ----
+    @staticmethod
+    def _cells_at(blobs, index_lists, s, cells, proofs):
+        bl = [_b(x, Blob) for x in blobs]
+        lists = [[int(i) for i in ix] for ix in index_lists]
+        n = len(bl)
+        if len(lists) != n:
+            raise BadArgs("length mismatch")
+        if any(i < 0 or i >= 1 << 64 for ix in lists for i in ix):
+            raise BadArgs("cell index out of range")
+        flat = [i for ix in lists for i in ix]
+        total = len(flat)
+        c_out = C.create_string_buffer(BYTES_PER_CELL * max(total, 1)) if cells else None
+        p_out = C.create_string_buffer(48 * max(total, 1)) if proofs else None
+        st = (C.c_int * max(n, 1))()
+        counts = (C.c_size_t * max(n, 1))(*[len(ix) for ix in lists])
+        idx = (C.c_size_t * max(total, 1))(*flat)
+        rc = lib().kzg355_compute_cell_kzg_proofs_at_many(c_out, p_out, st, b"".join(bl), n, counts, idx, s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "compute_cell_kzg_proofs_at_many")
+        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
+        praw = p_out.raw if proofs else b""
+        res, off = [], 0
+        for i in range(n):
+            k = len(lists[i])
+            if st[i] != 0:
+                res.append(_ERRORS.get(st[i], InternalError)("compute_cell_kzg_proofs_at"))
+            else:
+                res.append(([Cell(craw[BYTES_PER_CELL * j:BYTES_PER_CELL * (j + 1)]) for j in range(off, off + k)] if cells else None,
+                            [KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if proofs else None))
+            off += k
+        return res
+
+    @staticmethod
+    def compute_cell_kzg_proofs_at(blob, cell_indices, s):
+        """([Cell], [KzgProof]) of the blob at cell_indices (each < 128, any order, repeats allowed): entry j is what compute_cells_and_kzg_proofs
+        returns at index cell_indices[j], at the price of one MSM per index instead of the FK20 chain.  BadArgs on a field element >= r, an
+        index >= 128 or more than 128 indices."""
+        return Kzg._one(Kzg._cells_at([blob], [cell_indices], s, True, True))
+
+    @staticmethod
+    def compute_kzg_cell_proofs_at(blob, cell_indices, s):
+        """The proofs alone (the cells are not copied out)."""
+        return Kzg._one(Kzg._cells_at([blob], [cell_indices], s, False, True))[1]
+
+    @staticmethod
+    def compute_cell_kzg_proofs_at_many(blobs, index_lists, s):
+        """One independent compute_cell_kzg_proofs_at per blob, each with its own index list (which may be empty), in one call.  Returns a list
+        of (cells, proofs) tuples or Error; blobs and index_lists of different lengths raise BadArgs."""
+        return Kzg._cells_at(blobs, index_lists, s, True, True)
+
     @staticmethod
     def debug_cell_compute_h(blobs, s):
         """FK20 intermediates per blob: H_0 .. H_63 compressed (H_63 is the point at infinity), or Error."""
@@ -839,6 +890,29 @@ class Kzg:
         if _whole_call_failed(rc, st, m):
             _check(rc, "recover_cells_and_kzg_proofs_many_sets_device")
         return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]
+
+    @staticmethod
+    def compute_cell_kzg_proofs_at_many_device(blobs, n, cell_counts, cell_indices, s, cells_out=None, proofs_out=None):
+        """compute_cell_kzg_proofs_at_many of n resident blobs (n * 131072 bytes): blob i asks for cell_counts[i] cells, its indices following
+        those of blob i - 1 in cell_indices (both host sequences).  Slot j of the device tensors cells_out (sum of the counts * 2048 bytes) and
+        proofs_out (* 48) receives the cell and proof of entry j of cell_indices; either may be None, not both.  Returns one entry per blob:
+        None, or the Error of that blob (its output slots are then unspecified)."""
+        n = int(n)
+        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
+        if n < 0 or len(cn) != n or any(c < 0 or c >= 1 << 64 for c in cn) or any(i < 0 or i >= 1 << 64 for i in ix) or sum(cn) != len(ix):
+            raise BadArgs("n, a count or a cell index out of range, or the counts do not add up to the indices")
+        if cells_out is None and proofs_out is None:
+            raise BadArgs("cells_out and proofs_out are both missing")
+        c_out = Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * len(ix), optional=True)
+        p_out = Kzg._dev(proofs_out, "proofs_out", 48 * len(ix), optional=True)
+        d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
+        st = (C.c_int * max(n, 1))()
+        counts = (C.c_size_t * max(n, 1))(*cn)
+        idx = (C.c_size_t * max(len(ix), 1))(*ix)
+        rc = lib().kzg355_compute_cell_kzg_proofs_at_many_device(c_out, p_out, st, d_blobs, n, counts, idx, s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "compute_cell_kzg_proofs_at_many_device")
+        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("compute_cell_kzg_proofs_at") for i in range(n)]
 
     # ---- blobs against their EIP-7594 cell proofs (what a Fulu blob transaction or blobs bundle carries): verify_cell_kzg_proof_batch over all
     # 128 cells of every blob, the cells computed on the device ----

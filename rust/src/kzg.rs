@@ -643,6 +643,49 @@ impl Kzg {
             .collect())
     }
 
+    /// The cells of the blob at `cell_indices` (each < 128, any order, repeats allowed) and their proofs: entry `j` is what
+    /// `compute_cells_and_kzg_proofs` returns at index `cell_indices[j]`, at the price of one MSM per index instead of the FK20 chain.
+    pub fn compute_cell_kzg_proofs_at(blob: &Blob, cell_indices: &[usize], s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
+        let mut res = Self::compute_cell_kzg_proofs_at_many(std::slice::from_ref(blob), &[cell_indices], s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// One independent `compute_cell_kzg_proofs_at` per blob, each with its own index list (which may be empty), in one set of launches.  One
+    /// `Result` per blob; `blobs` and `index_lists` of different lengths are `BadArgs` for the call.
+    pub fn compute_cell_kzg_proofs_at_many(
+        blobs: &[Blob],
+        index_lists: &[&[usize]],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let n = blobs.len();
+        if index_lists.len() != n {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let staged = stage_blobs(blobs);
+        let counts: Vec<usize> = index_lists.iter().map(|ix| ix.len()).collect();
+        let indices: Vec<usize> = index_lists.iter().flat_map(|ix| ix.iter().copied()).collect();
+        let total = indices.len();
+        let mut cells = vec![0u8; BYTES_PER_CELL * total.max(1)];
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * total.max(1)];
+        let mut st = vec![0i32; n.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_compute_cell_kzg_proofs_at_many(cells.as_mut_ptr(), proofs.as_mut_ptr(), st.as_mut_ptr(), staged.as_ptr(), n, counts.as_ptr(),
+                                                        indices.as_ptr(), s.raw)
+        };
+        whole_call(rc, &st[..n], "compute_cell_kzg_proofs_at_many")?;
+        let mut off = 0usize;
+        Ok((0..n)
+            .map(|i| {
+                let (lo, hi) = (off, off + counts[i]);
+                off = hi;
+                check(st[i], "compute_cell_kzg_proofs_at")?;
+                let cs = (lo..hi).map(|j| Cell::from_bytes(&cells[BYTES_PER_CELL * j..BYTES_PER_CELL * (j + 1)])).collect::<Result<Vec<_>, _>>()?;
+                let ps = (lo..hi).map(|j| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[48 * j..48 * (j + 1)]).unwrap())).collect();
+                Ok((cs, ps))
+            })
+            .collect())
+    }
+
     /// `verify_cell_kzg_proof_batch_many` on device-resident data: the four pointers are DEVICE pointers on the handle's device (byte buffers
     /// 16-byte aligned, the indices 8-byte aligned), group-major, `n_per_group` cells per group; only the verdicts cross PCIe.
     ///
