@@ -376,9 +376,9 @@ int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *o
  * A handle over several devices: the non-empty groups go to the devices in contiguous ranges, equal in GROUPS -- so the ranges can be uneven in
  * cells (not measured on several cards).  A group of this call is never cut into blocks, and kzg355_options.force_sharded does not apply to it.
  * kzg355_settings_cell_calls_per_device counts one launch set per device that received a non-empty group.
- * Not offered: a device-resident form (the device preparation, k_cell_prep, is built on one n per call), per-transaction blob counts for
- * kzg355_verify_blob_cell_proofs_batch_many (it needs this call's chain plus ragged forms of its own kernels), cutting a group of this call
- * over several devices. */
+ * Not offered: a device-resident form (the device preparation, k_cell_prep, is built on one n per call), cutting a group of this call over
+ * several devices.  (Per-transaction blob counts for kzg355_verify_blob_cell_proofs_batch_many are offered: its _many_sets form below runs
+ * this call's chain with ragged forms of its own kernels.) */
 int kzg355_verify_cell_kzg_proof_batch_many_sets(bool *ok /* groups */, int *status /* groups or NULL */, const size_t *cell_counts /* groups */,
                                                  const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
                                                  const uint8_t *proofs /* each: sum of the counts entries, group after group */, size_t groups,
@@ -547,6 +547,43 @@ int kzg355_debug_blob_cell_batch_intermediates(uint8_t *out /* groups*176 */, bo
 int kzg355_debug_blob_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,
                                                       const uint8_t *d_blobs, const uint8_t *d_commitments, const uint8_t *d_cell_proofs, size_t n_per_group,
                                                       size_t groups, int interp_form, int prep_form, const kzg355_settings *s);
+/* Groups of DIFFERENT blob counts in one call (the blob transactions of a mempool or a builder: 1, 2, 3 ... blobs side by side), one set of
+ * launches for all non-empty groups.  Layout: with boff_g = blob_counts[0] + ... + blob_counts[g-1], group g is blobs [boff_g, boff_g +
+ * blob_counts[g]) of `blobs`, the same entries of `commitments` and proofs [128 boff_g, 128 (boff_g + blob_counts[g])) of `cell_proofs`; the
+ * arrays hold the groups one after the other, with no padding.
+ * Result per group: EXACTLY that of kzg355_verify_blob_cell_proofs_batch on that slice -- the same verdict, status and challenge r; commitments
+ * deduplicated inside the group only, in order of first appearance; the transcript carries the group's own 128 * count.  A count of 0: that group
+ * is true / KZG355_OK.  A blob element >= r, a commitment or proof that fails validate_kzg_g1: that group's KZG355_BADARGS, the others are left
+ * alone; the return value is the first non-OK status in group order.
+ * Refused as a whole (every status marked, every verdict false), decided from the counts alone, before any array is read and before any device
+ * is touched: a NULL handle, NULL ok, or NULL blob_counts with groups > 0; a NULL array while the sum of the counts is > 0; a handle of another
+ * FIELD_ELEMENTS_PER_BLOB; groups above 2^24; one count above 2048 blobs (the most one set of launches takes, as for n_per_group above); a sum of
+ * the counts that overflows size_t, alone or times 131072.  groups == 0: KZG355_OK, nothing is touched.
+ * The sum of the counts is not limited: the non-empty groups run in launch sets of whole groups, taken in order while the set's blobs stay
+ * within 2048.  Work and device memory are proportional to the sum of the counts, not to groups times the largest count.
+ * A handle over several devices: the non-empty groups go to the devices in contiguous ranges, equal in GROUPS -- so the ranges can be uneven in
+ * blobs (not measured on several cards).  A group is never cut.  kzg355_settings_cell_calls_per_device counts the launch sets of every device
+ * that received a non-empty group. */
+int kzg355_verify_blob_cell_proofs_batch_many_sets(bool *ok /* groups */, int *status /* groups or NULL */, const size_t *blob_counts /* groups */,
+                                                   const uint8_t *blobs, const uint8_t *commitments,
+                                                   const uint8_t *cell_proofs /* sum of the counts blobs / commitments / x128 proofs */, size_t groups,
+                                                   const kzg355_settings *s);
+/* The same with the three bulk arrays in HBM, as kzg355_verify_blob_cell_proofs_batch_many_device takes them: device pointers on the handle's
+ * first device, 16-byte aligned (a misaligned pointer refuses the call: KZG355_BADARGS); ok, status and blob_counts are HOST pointers.  The 48
+ * bytes of every commitment come back for the deduplication; whether the transcripts are hashed on the device follows the rule of
+ * kzg355_verify_cell_kzg_proof_batch_many_device applied to a launch set's largest group and its number of groups (always on the host with a
+ * group above 128 blobs) -- a rule measured on uniform shapes only. */
+int kzg355_verify_blob_cell_proofs_batch_many_sets_device(bool *ok /* host, groups */, int *status /* host, groups or NULL */,
+                                                          const size_t *blob_counts /* HOST, groups */, const uint8_t *d_blobs, const uint8_t *d_commitments,
+                                                          const uint8_t *d_cell_proofs, size_t groups, const kzg355_settings *s);
+/* Test forms of the two _many_sets calls: out[176 g ..] as kzg355_debug_blob_cell_batch_intermediates lays it out, zero bytes for a group of
+ * count 0; interp_form and prep_form as there (interp_form 0: per set of launches from its blob total; any value out of range refuses the call). */
+int kzg355_debug_blob_cell_batch_intermediates_sets(uint8_t *out /* groups*176 */, bool *ok, int *status, const size_t *blob_counts, const uint8_t *blobs,
+                                                    const uint8_t *commitments, const uint8_t *cell_proofs, size_t groups, int interp_form,
+                                                    const kzg355_settings *s);
+int kzg355_debug_blob_cell_batch_intermediates_sets_device(uint8_t *out, bool *ok, int *status, const size_t *blob_counts, const uint8_t *d_blobs,
+                                                           const uint8_t *d_commitments, const uint8_t *d_cell_proofs, size_t groups, int interp_form,
+                                                           int prep_form, const kzg355_settings *s);
 int kzg355_host_sha256(uint8_t out[32], const uint8_t *msg, size_t len, int impl);
 int kzg355_host_challenge_digests(uint8_t *out /* n*32 */, const uint8_t *blobs, size_t blob_bytes, const uint8_t *commitments /* n*48 */, size_t n, int impl);
 

@@ -239,6 +239,41 @@ struct Kzg {
         return ok;
     }
 
+    // blob transactions of different blob counts in one call: one independent verify_blob_cell_proofs_batch per group, all non-empty groups in
+    // one set of launches (an empty group is true); a group whose three lengths do not fit is BadArgs before the library is called
+    struct BlobGroup {
+        std::vector<Blob> blobs;
+        std::vector<KzgCommitment> commitments;
+        std::vector<KzgProof> cell_proofs;
+    };
+    static Result<std::vector<Result<bool>>> verify_blob_cell_proofs_batch_many_sets(const std::vector<BlobGroup> &groups, const KzgSettings &s) {
+        const size_t G = groups.size();
+        std::vector<size_t> counts;
+        std::vector<uint8_t> b, c, p;
+        for (const BlobGroup &g : groups) {
+            const size_t n = g.blobs.size();
+            if (g.commitments.size() != n || g.cell_proofs.size() != (size_t)KZG355_CELLS_PER_EXT_BLOB * n) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(n);
+            for (size_t i = 0; i < n; i++) {
+                b.insert(b.end(), g.blobs[i].data(), g.blobs[i].data() + BYTES_PER_BLOB);
+                c.insert(c.end(), g.commitments[i].data(), g.commitments[i].data() + 48);
+            }
+            for (const KzgProof &x : g.cell_proofs) p.insert(p.end(), x.data(), x.data() + 48);
+        }
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        b.push_back(0); c.push_back(0); p.push_back(0);
+        std::unique_ptr<bool[]> ok(new bool[G + 1]());
+        std::vector<int> st(G + 1, 0);
+        int rc = kzg355_verify_blob_cell_proofs_batch_many_sets(ok.get(), st.data(), counts.data(), b.data(), c.data(), p.data(), G, s.raw());
+        st.resize(G);
+        if (whole_call_failed(rc, st)) return from_status(rc, "verify_blob_cell_proofs_batch_many_sets");
+        std::vector<Result<bool>> out;
+        for (size_t g = 0; g < G; g++) {
+            if (st[g]) out.push_back(from_status(st[g], "verify_blob_cells")); else out.push_back(bool(ok[g]));
+        }
+        return out;
+    }
+
     // EIP-7594 compute_cells_and_kzg_proofs: the 128 cells of the blob's 2x extension and their 128 proofs, in cell order
     static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cells_and_kzg_proofs(const Blob &blob, const KzgSettings &s) {
         std::vector<uint8_t> c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48);

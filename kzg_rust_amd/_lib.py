@@ -118,6 +118,10 @@ def load():
         "kzg355_verify_blob_cell_proofs_batch_many_device": [bp, ip, vp, vp, vp, sz, sz, vp],
         "kzg355_debug_blob_cell_batch_intermediates": [u8p, bp, ip, u8p, u8p, u8p, sz, sz, C.c_int, vp],
         "kzg355_debug_blob_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, sz, sz, C.c_int, C.c_int, vp],
+        "kzg355_verify_blob_cell_proofs_batch_many_sets": [bp, ip, szp, u8p, u8p, u8p, sz, vp],
+        "kzg355_verify_blob_cell_proofs_batch_many_sets_device": [bp, ip, szp, vp, vp, vp, sz, vp],
+        "kzg355_debug_blob_cell_batch_intermediates_sets": [u8p, bp, ip, szp, u8p, u8p, u8p, sz, C.c_int, vp],
+        "kzg355_debug_blob_cell_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, sz, C.c_int, C.c_int, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -170,5 +174,7 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_blob_cell_proofs_batch", "kzg355_verify_blob_cell_proofs_batch_many", "kzg355_verify_blob_cell_proofs_batch_many_device",
     "kzg355_debug_blob_cell_batch_intermediates", "kzg355_debug_blob_cell_batch_intermediates_device",
     "kzg355_verify_cell_kzg_proof_batch_many_sets", "kzg355_debug_cell_batch_intermediates_sets",
+    "kzg355_verify_blob_cell_proofs_batch_many_sets", "kzg355_verify_blob_cell_proofs_batch_many_sets_device",
+    "kzg355_debug_blob_cell_batch_intermediates_sets", "kzg355_debug_blob_cell_batch_intermediates_sets_device",
     "kzg355_compute_cell_kzg_proofs_at", "kzg355_compute_cell_kzg_proofs_at_many", "kzg355_compute_cell_kzg_proofs_at_many_device",
 ]

@@ -209,7 +209,7 @@ bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, siz
 // lincomb scalars, partials = lincomb terms, lc_partials = the three sums per group, out48 = r | debug output.  N = n * groups cells, S segments;
 // host_input: cells and proofs are uploaded (else read where the caller has them).
 // N cells and `terms` lincomb terms in all groups together
-static int cell_reserve_sized(Workspace *w, bool host_input, size_t N, size_t terms, size_t groups, int S, size_t meta_ints) {
+int cell_reserve_sized(Workspace *w, bool host_input, size_t N, size_t terms, size_t groups, int S, size_t meta_ints) {
     int rc;
     if ((host_input && ((rc = w->blobs.ensure((size_t)CELL_BYTES * N)) || (rc = w->proofs.ensure(48 * N)))) || (rc = w->commitments.ensure(48 * N)) ||
         (rc = w->pts.ensure(sizeof(G1Affine) * 2 * N)) || (rc = w->digests.ensure(32 * groups)) || (rc = w->q.ensure(sizeof(int) * meta_ints)) ||
@@ -257,9 +257,16 @@ void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, 
     launch_subgroup_points(w->pts.as<G1Affine>(), (int)N, n, w->err.as<int>(), st);
     tm.end();
 }
-// sets_N (not with k0, bi or points_queued): the launch set is sets_N cells in G whole groups of different sizes, n is unused, and the meta buffer
-// ends with the group offsets and the group of every cell (cell_host_prep with goff): the `_sets` entries of the same kernel bodies run, then
-// k_cell_finish and the pairing as for any launch set.
+void cell_chain_points_sets(Workspace *w, Timed &tm, const uint8_t *d_proofs, int S, size_t N, int G) {
+    const int *d_goff = w->q.as<int>() + 4 * (size_t)S + (G + 1) + 3 * N, *d_cgrp = d_goff + G + 1;
+    tm.begin("cell_points");
+    launch_cell_points_sets(w->commitments.as<uint8_t>(), d_proofs, d_goff, d_cgrp, (int)N, w->pts.as<G1Affine>(), w->err.as<int>(), w->stream);
+    tm.end();
+}
+// sets_N (not with k0): the launch set is sets_N cells in G whole groups of different sizes, n is unused, and the meta buffer ends with the group
+// offsets and the group of every cell (cell_host_prep with goff; blob_cells.hip writes the same): the `_sets` entries of the same kernel bodies
+// run, then k_cell_finish and the pairing as for any launch set.  points_queued: the caller has queued cell_chain_points_sets; bi: the groups are
+// whole blobs of different counts, bi->f their coefficients blob after blob (bi->n_blobs is unused: the offsets give every group's count).
 void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
                 uint8_t *d_dbg, bool points_queued, const BlobInterp *bi, size_t sets_N) {
     const size_t N = sets_N ? sets_N : (size_t)n * G;
@@ -269,15 +276,14 @@ void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_ce
     uint8_t *d_r = w->out48.as<uint8_t>();
     if (sets_N) {
         const int *d_goff = d_perm + N, *d_cgrp = d_goff + G + 1;
-        tm.begin("cell_points");
-        launch_cell_points_sets(w->commitments.as<uint8_t>(), d_proofs, d_goff, d_cgrp, (int)N, w->pts.as<G1Affine>(), w->err.as<int>(), st);
-        tm.end();
+        if (!points_queued) cell_chain_points_sets(w, tm, d_proofs, S, N, G);
         tm.begin("cell_scalars");
         launch_cell_scalars_sets(w->digests.as<uint8_t>(), d_cell, d_cidx, d_goff, d_cgrp, (int)N, s->cell_consts.as<CellConsts>(), w->z.as<Fr>(),
                                  w->scal_a.as<uint32_t>(), d_r, st);
         tm.end();
         tm.begin("cell_interp");
-        launch_cell_interp_sets(d_cells, d_perm, d_segs, S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), d_goff, G, w->y.as<Fr>(),
+        if (bi) launch_blob_cell_coefs_sets(bi->f, w->z.as<Fr>(), s->cc_consts.as<CellComputeConsts>(), d_goff, G, bi->W, w->y.as<Fr>(), st);
+        launch_cell_interp_sets(d_cells, d_perm, d_segs, bi ? 0 : S, d_gseg, w->z.as<Fr>(), s->cell_consts.as<CellConsts>(), d_goff, G, w->y.as<Fr>(),
                                 w->scal_a.as<uint32_t>(), w->err.as<int>(), st);
         tm.end();
         tm.begin("cell_lincomb");

@@ -474,13 +474,18 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
 static const char *const CELL_DOMAIN = "RCKZGCBATCH__V1_";
 static const size_t CELL_MAX_CELLS = (size_t)1 << 18;   // cells per call of the cell batch check, per launch set of the blob form (512 MiB of cells)
 inline void put_u64be(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (56 - 8 * i)); }
-// groups of whole blobs: their coefficients (groups * n_blobs * 4096 Fr) and the 64 weights per group the interpolation takes from them
+// groups of whole blobs: their coefficients (groups * n_blobs * 4096 Fr; with sets_N the blobs of all groups one after the other, every group
+// its own count, n_blobs unused) and the 64 weights per group the interpolation takes from them
 struct BlobInterp { const Fr *f; int n_blobs; Fr *W; };
 int ensure_cell_setup(kzg355_settings *s, Workspace *w);
 int cell_dedup(const uint8_t *commitments, size_t count, uint8_t *uc, int *cidx);
 bool cell_device_call_prepares_on_host(const kzg355_settings *s, size_t npg, size_t groups, int prep_form);
 int cell_reserve(Workspace *w, bool host_input, int n, size_t groups, int S, size_t meta_ints);
+// N cells and `terms` lincomb terms in all groups together (groups of different sizes: terms = cell_terms_sets(N, groups))
+int cell_reserve_sized(Workspace *w, bool host_input, size_t N, size_t terms, size_t groups, int S, size_t meta_ints);
 void cell_chain_points(Workspace *w, Timed &tm, const uint8_t *d_proofs, int n, int G);
+// the same for N cells in G groups of different sizes, once the meta buffer holds the offsets and the group of every cell (cell_chain, sets_N)
+void cell_chain_points_sets(Workspace *w, Timed &tm, const uint8_t *d_proofs, int S, size_t N, int G);
 void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_cells, const uint8_t *d_proofs, int S, int n, int G, int k0, bool finish,
                 uint8_t *d_dbg, bool points_queued = false, const BlobInterp *bi = nullptr,
                 size_t sets_N = 0 /* groups of different sizes, sets_N cells in all: cells.hip */);

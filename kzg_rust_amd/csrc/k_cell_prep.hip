@@ -143,16 +143,16 @@ struct CellMsg {
     uint32_t u, n, nq, nblocks;             // unique commitments, cells, 16-byte pieces of the message, SHA-256 blocks
     uint64_t bits;
 };
+// the message of group g: its n cells are cells base .. base + n - 1 of the launch set (uniform groups: base = g npg, n = npg)
 __device__ __forceinline__ CellMsg cp_msg(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs, const int *cidx,
-                                          const int *ucount, int npg, int g) {
-    const size_t base = (size_t)g * npg;
+                                          const int *ucount, size_t base, int n, int g) {
     CellMsg m;
     m.uc = reinterpret_cast<const uint4 *>(uc + 48 * base);
     m.cells = reinterpret_cast<const uint4 *>(cells + (size_t)CELL_BYTES * base);
     m.proofs = reinterpret_cast<const uint4 *>(proofs + 48 * base);
     m.indices = indices + base;
     m.cidx = cidx + base;
-    m.u = (uint32_t)ucount[g]; m.n = (uint32_t)npg;
+    m.u = (uint32_t)ucount[g]; m.n = (uint32_t)n;
     m.nq = 3u + 3u * m.u + CP_CELL_QUADS * m.n;
     m.nblocks = (m.nq * 16u + 9u + 63u) / 64u;
     m.bits = (uint64_t)m.nq * 128u;
@@ -190,12 +190,11 @@ __device__ __forceinline__ void cp_store_digest(uint8_t *digests, int g, const u
     dst[1] = make_uint4(bswap32(hs[4]), bswap32(hs[5]), bswap32(hs[6]), bswap32(hs[7]));
 }
 
+// Each hash kernel has one body and two entries: the uniform one (every group npg cells) and the `_sets` one (group g is cells goff[g] ..
+// goff[g + 1] - 1: whole blobs of different counts, kzg355_verify_blob_cell_proofs_batch_many_sets).  Message assembly, schedule and rounds are
+// the body's and do not know which entry called.
 // many groups: one lane per group, schedule and rounds in the lane's registers
-__global__ void __launch_bounds__(64) k_cell_rhash_lanes(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs,
-                                                         const int *cidx, const int *ucount, int npg, int groups, uint8_t *digests) {
-    const int g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= groups) return;
-    const CellMsg m = cp_msg(uc, indices, cells, proofs, cidx, ucount, npg, g);
+__device__ __forceinline__ void cp_rhash_lanes_body(const CellMsg &m, int g, uint8_t *digests) {
     uint32_t hs[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
 #pragma unroll 1
     for (uint32_t b = 0; b < m.nblocks; b++) {
@@ -214,19 +213,30 @@ __global__ void __launch_bounds__(64) k_cell_rhash_lanes(const uint8_t *uc, cons
     }
     cp_store_digest(digests, g, hs);
 }
+__global__ void __launch_bounds__(64) k_cell_rhash_lanes(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs,
+                                                         const int *cidx, const int *ucount, int npg, int groups, uint8_t *digests) {
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= groups) return;
+    cp_rhash_lanes_body(cp_msg(uc, indices, cells, proofs, cidx, ucount, (size_t)g * npg, npg, g), g, digests);
+}
+// The lanes of a wave hash transcripts of DIFFERENT lengths here: each lane's loop runs over its own nblocks, a lane that is done is masked off,
+// and the wave runs as long as its longest transcript.  That is correct (no lane reads past its own message, nothing is shared between lanes);
+// it only means that a wave of mixed sizes is as slow as its largest group.
+__global__ void __launch_bounds__(64) k_cell_rhash_lanes_sets(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs,
+                                                              const int *cidx, const int *ucount, const int *goff, int groups, uint8_t *digests) {
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= groups) return;
+    cp_rhash_lanes_body(cp_msg(uc, indices, cells, proofs, cidx, ucount, (size_t)goff[g], goff[g + 1] - goff[g], g), g, digests);
+}
 
 // few groups: one wave per group (four per workgroup, one per SIMD of its CU; the waves share nothing and synchronise with themselves only).
 // The message schedule of a block does not depend on the chaining state: the 64 lanes expand 64 blocks at once (W[t] + K[t] to LDS), then lane 0
 // runs the rounds of those blocks.
 constexpr int CP_WAVES = 4;
-__global__ void __launch_bounds__(64 * CP_WAVES) k_cell_rhash_wave(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs,
-                                                                   const int *cidx, const int *ucount, int npg, int groups, uint8_t *digests) {
+// (the message m of the calling wave's group g; wave wid of its workgroup, lane of the wave)
+__device__ __forceinline__ void cp_rhash_wave_body(const CellMsg &m, int g, int wid, int lane, uint8_t *digests) {
     __shared__ uint32_t wk_all[CP_WAVES][64][64];                 // per wave: [t][block of the chunk]
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g = blockIdx.x * CP_WAVES + wid;
-    if (g >= groups) return;
     uint32_t (*wk)[64] = wk_all[wid];
-    const CellMsg m = cp_msg(uc, indices, cells, proofs, cidx, ucount, npg, g);
     uint32_t hs[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
 #pragma unroll 1
     for (uint32_t b0 = 0; b0 < m.nblocks; b0 += 64) {
@@ -258,6 +268,22 @@ __global__ void __launch_bounds__(64 * CP_WAVES) k_cell_rhash_wave(const uint8_t
     }
     if (lane == 0) cp_store_digest(digests, g, hs);
 }
+__global__ void __launch_bounds__(64 * CP_WAVES) k_cell_rhash_wave(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells, const uint8_t *proofs,
+                                                                   const int *cidx, const int *ucount, int npg, int groups, uint8_t *digests) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * CP_WAVES + wid;
+    if (g >= groups) return;
+    cp_rhash_wave_body(cp_msg(uc, indices, cells, proofs, cidx, ucount, (size_t)g * npg, npg, g), g, wid, lane, digests);
+}
+// (a wave hashes one group, so the waves of a workgroup differ in length and share nothing but the LDS array's address)
+__global__ void __launch_bounds__(64 * CP_WAVES) k_cell_rhash_wave_sets(const uint8_t *uc, const uint64_t *indices, const uint8_t *cells,
+                                                                        const uint8_t *proofs, const int *cidx, const int *ucount, const int *goff,
+                                                                        int groups, uint8_t *digests) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * CP_WAVES + wid;
+    if (g >= groups) return;
+    cp_rhash_wave_body(cp_msg(uc, indices, cells, proofs, cidx, ucount, (size_t)goff[g], goff[g + 1] - goff[g], g), g, wid, lane, digests);
+}
 
 // ------------------------------------------------------------------------------------------------ launchers
 void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int npg, int groups, int tab_size, int *d_gtab, uint8_t *d_uc, int4 *d_segs,
@@ -276,6 +302,15 @@ void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8
                                   d_digests);
     else hipLaunchKernelGGL(k_cell_rhash_wave, dim3((groups + CP_WAVES - 1) / CP_WAVES), dim3(64 * CP_WAVES), 0, st, d_uc, idx, d_cells, d_proofs, d_cidx,
                             d_ucount, npg, groups, d_digests);
+}
+void launch_cell_rhash_sets(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx,
+                            const int *d_ucount, const int *d_goff, int groups, bool lanes, uint8_t *d_digests, hipStream_t st) {
+    if (groups <= 0) return;
+    const uint64_t *idx = reinterpret_cast<const uint64_t *>(d_indices);
+    if (lanes) hipLaunchKernelGGL(k_cell_rhash_lanes_sets, dim3((groups + 63) / 64), dim3(64), 0, st, d_uc, idx, d_cells, d_proofs, d_cidx, d_ucount, d_goff,
+                                  groups, d_digests);
+    else hipLaunchKernelGGL(k_cell_rhash_wave_sets, dim3((groups + CP_WAVES - 1) / CP_WAVES), dim3(64 * CP_WAVES), 0, st, d_uc, idx, d_cells, d_proofs,
+                            d_cidx, d_ucount, d_goff, groups, d_digests);
 }
 
 }  // namespace kzg

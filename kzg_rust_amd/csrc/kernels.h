@@ -246,6 +246,10 @@ void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int
 // (many groups), else one wave per group
 void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx, const int *d_ucount,
                        int npg, int groups, bool lanes, uint8_t *d_digests, hipStream_t st);
+// the same for groups of different sizes: group g is cells d_goff[g] .. d_goff[g + 1] - 1 of the launch set (d_goff: groups + 1 ints, strictly
+// increasing), every array cell-major as above; each group at most CELL_PREP_MAX_CELLS cells
+void launch_cell_rhash_sets(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx,
+                            const int *d_ucount, const int *d_goff, int groups, bool lanes, uint8_t *d_digests, hipStream_t st);
 // ---- k_blob_cells.hip: verify_blob_cell_proofs_batch -- groups of n blobs, each with all its 128 cells in cell order (npg = 128 n)
 // What the preparation leaves, from d_pos (groups * n: the position of each blob's commitment among its group's unique ones), d_ucount (how many
 // those are) and d_uc_in (groups * n * 48: the unique commitments of a group first): d_cell, d_cidx, d_uc (padded to npg per group with the
@@ -257,6 +261,14 @@ struct CellComputeConsts;
 // the interpolation from the blobs' coefficients (d_f: groups * n * 4096 Fr as launch_cc_field leaves them; d_rpow as launch_cell_scalars does):
 // d_W: groups * 64 Fr, d_coef: groups * 64 * 64 Fr in launch_cell_interp's segment layout (which finishes with n_segs = 0)
 void launch_blob_cell_coefs(const Fr *d_f, const Fr *d_rpow, const CellComputeConsts *d_cc, int n, int groups, Fr *d_W, Fr *d_coef, hipStream_t st);
+// Groups of different blob counts (kzg355_verify_blob_cell_proofs_batch_many_sets), in the `_sets` layout above: every group has 128 cells per
+// blob, so d_goff / d_cgrp (cells) give the blobs too -- d_goff[g] / 128 blobs lie before group g, and d_pos, d_uc_in, d_blob_err and d_f are
+// indexed by them, blob after blob with no padding.  Everything else as in the two launchers above.
+void launch_blob_cell_meta_sets(const int *d_pos, const int *d_ucount, const uint8_t *d_uc_in, const int *d_blob_err, const int *d_goff, const int *d_cgrp,
+                                int n_cells, int groups, bool columns, int4 *d_segs, int *d_gseg, int *d_cell, int *d_cidx, int *d_perm, size_t *d_indices,
+                                uint8_t *d_uc, int *d_err, hipStream_t st);
+void launch_blob_cell_coefs_sets(const Fr *d_f, const Fr *d_rpow, const CellComputeConsts *d_cc, const int *d_goff, int groups, Fr *d_W, Fr *d_coef,
+                                 hipStream_t st);
 
 
 // ---- k_cell_compute.hip: compute_cells_and_kzg_proofs (the cells of the 2x extension and their proofs by FK20; mainnet handles only)

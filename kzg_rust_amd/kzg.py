@@ -1003,3 +1003,79 @@ class Kzg:
         2 on the host."""
         res, raw = Kzg._blob_cells_many_device(blobs, commitments, cell_proofs, n_per_group, groups, s, interp_form, prep_form, True)
         return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
+    def _blob_cells_many_sets(groups, s, debug, interp_form=0):
+        if interp_form not in (0, 1, 2):
+            raise BadArgs("interp_form out of range")
+        flat = [[], [], []]
+        counts = []
+        for blobs, commitments, cell_proofs in groups:
+            arrs = ([_b(x, Blob) for x in blobs], [_b(x, KzgCommitment) for x in commitments], [_b(x, KzgProof) for x in cell_proofs])
+            n = len(arrs[0])
+            if len(arrs[1]) != n or len(arrs[2]) != CELLS_PER_EXT_BLOB * n:        # a group that does not fit: BadArgs, before any FFI call
+                raise BadArgs("length mismatch")
+            counts.append(n)
+            for f, a in zip(flat, arrs):
+                f += a
+        G = len(counts)
+        ok = (C.c_bool * max(G, 1))()
+        st = (C.c_int * max(G, 1))()
+        cnt = (C.c_size_t * max(G, 1))(*counts)
+        args = (ok, st, cnt, b"".join(flat[0]), b"".join(flat[1]), b"".join(flat[2]), G)
+        out = C.create_string_buffer(176 * max(G, 1)) if debug else None
+        rc = (lib().kzg355_debug_blob_cell_batch_intermediates_sets(out, *args, interp_form, s.handle) if debug
+              else lib().kzg355_verify_blob_cell_proofs_batch_many_sets(*args, s.handle))
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_cell_proofs_batch_many_sets")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_blob_cells") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_cell_proofs_batch_many_sets(groups, s):
+        """verify_blob_cell_proofs_batch_many for groups of any blob counts (an empty group is True): list of (blobs, commitments, cell_proofs),
+        one independent verify_blob_cell_proofs_batch per group, all of them in one set of launches.  Returns a list of bool / Error."""
+        return Kzg._blob_cells_many_sets(groups, s, False)[0]
+
+    @staticmethod
+    def debug_blob_cell_batch_intermediates_sets(groups, s, interp_form=0):
+        """(verdicts as verify_blob_cell_proofs_batch_many_sets, [r (32) | [I(tau)]_1 | LL | RL (48 each) per group; zero bytes for an empty
+        group]); interp_form as in debug_blob_cell_batch_intermediates, 0 chosen per set of launches."""
+        res, raw = Kzg._blob_cells_many_sets(groups, s, True, interp_form)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
+    def _blob_cells_many_sets_device(blobs, commitments, cell_proofs, blob_counts, s, interp_form, prep_form, debug):
+        counts = [int(c) for c in blob_counts]
+        if any(c < 0 for c in counts) or interp_form not in (0, 1, 2) or prep_form not in (0, 1, 2):
+            raise BadArgs("blob_counts, interp_form or prep_form out of range")
+        nb, G = sum(counts), len(counts)
+        ptrs = (Kzg._dev(blobs, "blobs", BYTES_PER_BLOB * nb, optional=nb == 0), Kzg._dev(commitments, "commitments", 48 * nb, optional=nb == 0),
+                Kzg._dev(cell_proofs, "cell_proofs", 48 * CELLS_PER_EXT_BLOB * nb, optional=nb == 0))
+        if G == 0:
+            return [], b""
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        cnt = (C.c_size_t * G)(*counts)
+        if debug:
+            out = C.create_string_buffer(176 * G)
+            rc = lib().kzg355_debug_blob_cell_batch_intermediates_sets_device(out, ok, st, cnt, *ptrs, G, interp_form, prep_form, s.handle)
+        else:
+            rc = lib().kzg355_verify_blob_cell_proofs_batch_many_sets_device(ok, st, cnt, *ptrs, G, s.handle)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_cell_proofs_batch_many_sets_device")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_blob_cells") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_cell_proofs_batch_many_sets_device(blobs, commitments, cell_proofs, blob_counts, s):
+        """verify_blob_cell_proofs_batch_many_sets on device memory: blobs (sum(blob_counts) * 131072 bytes, uint8), commitments (* 48) and
+        cell_proofs (* 128 * 48), group after group with no padding; blob_counts is a host list.  Returns a list of bool / Error per group."""
+        return Kzg._blob_cells_many_sets_device(blobs, commitments, cell_proofs, blob_counts, s, 0, 0, False)[0]
+
+    @staticmethod
+    def debug_blob_cell_batch_intermediates_sets_device(blobs, commitments, cell_proofs, blob_counts, s, interp_form=0, prep_form=0):
+        """(verdicts, [176 bytes per group]) as debug_blob_cell_batch_intermediates_sets; prep_form 0 by shape, 1 transcripts hashed on the
+        device, 2 on the host."""
+        res, raw = Kzg._blob_cells_many_sets_device(blobs, commitments, cell_proofs, blob_counts, s, interp_form, prep_form, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]

@@ -525,6 +525,43 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_blob_cells").map(|_| ok[g])).collect())
     }
 
+    /// Blob transactions of different blob counts in one call: group `g` is the next `blob_counts[g]` blobs and commitments and the next
+    /// `128 * blob_counts[g]` proofs of the three slices, which hold the groups one after the other with no padding.  One independent
+    /// `verify_blob_cell_proofs_batch` per group, all non-empty groups in one set of launches; an empty group is `Ok(true)`.
+    pub fn verify_blob_cell_proofs_batch_many_sets(
+        blobs: &[Blob],
+        commitments: &[KzgCommitment],
+        cell_proofs: &[KzgProof],
+        blob_counts: &[usize],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let n = blobs.len();
+        let total = blob_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c));
+        if total != Some(n) || commitments.len() != n || cell_proofs.len() != CELLS_PER_EXT_BLOB * n {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let groups = blob_counts.len();
+        let staged = stage_blobs(blobs);
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let p: Vec<u8> = cell_proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_verify_blob_cell_proofs_batch_many_sets(
+                ok.as_mut_ptr(),
+                st.as_mut_ptr(),
+                blob_counts.as_ptr(),
+                staged.as_ptr(),
+                c.as_ptr(),
+                p.as_ptr(),
+                groups,
+                s.raw,
+            )
+        };
+        whole_call(rc, &st[..groups], "verify_blob_cell_proofs_batch_many_sets")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_blob_cells").map(|_| ok[g])).collect())
+    }
+
     /// EIP-7594 `compute_cells_and_kzg_proofs`: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their 128 proofs,
     /// in cell order (FK20 on the device).
     pub fn compute_cells_and_kzg_proofs(blob: &Blob, s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
