@@ -463,6 +463,53 @@ int kzg355_compute_cell_kzg_proofs_at_many(uint8_t *cells_out /* (sum of the cou
 int kzg355_compute_cell_kzg_proofs_at_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status /* host */, const uint8_t *d_blobs, size_t n,
                                                   const size_t *cell_counts /* HOST */, const size_t *cell_indices /* HOST */,
                                                   const kzg355_settings *s);
+/* ---- chosen cells of recovered blobs -----------------------------------------------------------------------------------------------------
+ * kzg355_recover_cells_and_kzg_proofs runs the whole FK20 chain whatever is wanted of its 128 proofs.  A node that holds most columns of a
+ * block and lacks a few wants the cells and proofs of the missing ones, or of the few it custodies: here the blob is recovered as there, and
+ * then every wanted (blob, index) pair is computed on its own, as kzg355_compute_cell_kzg_proofs_at does for a blob.
+ * Input: that of kzg355_recover_cells_and_kzg_proofs (n known cells at strictly ascending cell_indices, 64 <= n <= 128).  Output: that of
+ * kzg355_compute_cell_kzg_proofs_at -- slot j holds cell want_indices[j] of the recovered extension and its proof, byte for byte what
+ * kzg355_recover_cells_and_kzg_proofs returns at that index for the same input (for a known index too, and also when more than 64 cells lie
+ * on no polynomial of degree < 4096: the result is that of the 4096 coefficients the specs' algorithm keeps, as there).  Each wanted index is
+ * < 128; they may come in any order and may repeat.  k may be 0 (the blob is still recovered and checked; want_indices may then be NULL) and
+ * may not exceed 128.  Either output may be NULL, not both; without proofs_out no MSM runs and no MSM table is built.  The first call that
+ * wants proofs builds the handle's fixed-base MSM table, exactly as the first commitment does; a handle loaded with msm_bits = 8 runs the
+ * bucket form and gives the same bytes.  n outside 64..128, a known index >= 128, known indices not strictly ascending, a cell element >= r,
+ * a wanted index >= 128 or k > 128 -> KZG355_BADARGS.  Mainnet handles only. */
+int kzg355_recover_cells_and_kzg_proofs_at(uint8_t *cells_out /* k*2048 or NULL */, uint8_t *proofs_out /* k*48 or NULL */,
+                                           const size_t *cell_indices /* n */, const uint8_t *cells /* n*2048 */, size_t n,
+                                           const size_t *want_indices /* k */, size_t k, const kzg355_settings *s);
+/* m independent calls of the above in one set of launches.  Input layout of kzg355_recover_cells_and_kzg_proofs_many_sets: blob i is known
+ * at cell_counts[i] cells; with koff_i the sum of the cell_counts before it, its indices are cell_indices[koff_i ..] and its cells are at
+ * cells + 2048 * koff_i.  Output layout of kzg355_compute_cell_kzg_proofs_at_many: with woff_i the sum of the want_counts before blob i, slot
+ * woff_i + j holds cell want_indices[woff_i + j] of blob i's recovered extension and its proof.  A want count may be 0: that blob is still
+ * recovered and checked, and it fills no slot; want_indices may be NULL when the want counts sum to 0.  What is wrong with one blob is that
+ * blob's KZG355_BADARGS: a known count outside 64..128, a known index >= 128, known indices not strictly ascending, a cell element >= r, a
+ * wanted index >= 128, a want count > 128.  The other blobs are computed and are right: both layouts always follow the counts as given.  The
+ * return value is the first non-OK status; the output slots of a refused blob are unspecified.  What is wrong with the call refuses it as a
+ * whole and marks every status, before any array is read or any device is touched: a NULL handle, both outputs NULL, NULL cell_counts,
+ * want_counts, cell_indices or cells with m > 0, NULL want_indices while the want counts sum to more than 0, a handle of another
+ * FIELD_ELEMENTS_PER_BLOB, m > 2^32, either sum of counts overflowing size_t (alone or times 2048).  m == 0 -> OK, and nothing is touched.  A
+ * handle over several devices spreads contiguous ranges of blobs over them, each range starting at its own two prefix sums (a blob is never
+ * cut), and every range counts in kzg355_settings_cell_calls_per_device.  Blobs known at the same index set share its tables wherever they sit
+ * in a chunk; large calls run in chunks of whole blobs.
+ * Not offered: a form with one index set shared by all blobs (the sets form already shares tables between blobs of equal sets), and a switch
+ * to the FK20 chain when many blobs want many cells -- that remains kzg355_recover_cells_and_kzg_proofs_many_sets.  Measured on one MI355X
+ * ("Recovery of chosen cells"): with 1, 6 and 21 blobs this call is the quicker one up to all the cells measured (6 blobs x 64
+ * wanted: 5.8 against 67.2 ms); at 128 blobs the two cross at about 50 wanted cells per blob on the wide MSM table and at about 17 on the
+ * bucket form (msm_bits = 8). */
+int kzg355_recover_cells_and_kzg_proofs_at_many_sets(uint8_t *cells_out /* (sum of the want counts)*2048 or NULL */,
+                                                     uint8_t *proofs_out /* (sum of the want counts)*48 or NULL */, int *status /* m or NULL */,
+                                                     const size_t *cell_counts /* m */, const size_t *cell_indices /* sum of the cell counts */,
+                                                     const uint8_t *cells /* (sum of the cell counts)*2048 */, const size_t *want_counts /* m */,
+                                                     const size_t *want_indices /* sum of the want counts */, size_t m, const kzg355_settings *s);
+/* The same with the known cells and both outputs in HBM: device pointers on the handle's device (its first device, for a handle over several:
+ * the call runs on that device alone), 16-byte aligned -- a misaligned pointer refuses the call as a whole; status, the counts and both index
+ * lists stay HOST arguments.  The cells are read and the slots written where they are. */
+int kzg355_recover_cells_and_kzg_proofs_at_many_sets_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status /* host */,
+                                                            const size_t *cell_counts /* HOST */, const size_t *cell_indices /* HOST */,
+                                                            const uint8_t *d_cells, const size_t *want_counts /* HOST */,
+                                                            const size_t *want_indices /* HOST */, size_t m, const kzg355_settings *s);
 /* Test form: the FK20 intermediates H_0 .. H_63 of each blob, compressed (H_e = sum_{m >= 64(e+1)} f_m [tau^(m - 64(e+1))]_1; H_63 = infinity). */
 int kzg355_debug_cell_compute_h(uint8_t *out /* n*64*48 */, int *status /* n or NULL */, const uint8_t *blobs, size_t n, const kzg355_settings *s);
 /* The 4096 monomial points [tau^t]_1 the handle derived for compute_cells_and_kzg_proofs, compressed (building the proof setup first if needed). */

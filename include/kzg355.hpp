@@ -393,6 +393,71 @@ struct Kzg {
         return out;
     }
 
+    // The cells of the recovered blob at want_indices (each < 128, any order, repeats allowed) and their proofs, entry j what
+    // recover_cells_and_kzg_proofs returns at want_indices[j] for the same input: every wanted index through its own quotient and one MSM
+    static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> recover_cells_and_kzg_proofs_at(const std::vector<size_t> &cell_indices,
+                                                                                                       const std::vector<Cell> &cells,
+                                                                                                       const std::vector<size_t> &want_indices,
+                                                                                                       const KzgSettings &s) {
+        const size_t n = cell_indices.size(), k = want_indices.size();
+        if (cells.size() != n) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<uint8_t> in(n * KZG355_BYTES_PER_CELL + 1), c((k + 1) * KZG355_BYTES_PER_CELL), p((k + 1) * 48);
+        for (size_t i = 0; i < n; i++) std::memcpy(&in[i * KZG355_BYTES_PER_CELL], cells[i].data(), KZG355_BYTES_PER_CELL);
+        std::vector<size_t> known(cell_indices), want(want_indices);
+        known.push_back(0);                                        // (data() of an empty vector may be null)
+        want.push_back(0);
+        int rc = kzg355_recover_cells_and_kzg_proofs_at(c.data(), p.data(), known.data(), in.data(), n, want.data(), k, s.raw());
+        if (rc) return from_status(rc, "recover_cells_and_kzg_proofs_at");
+        std::pair<std::vector<Cell>, std::vector<KzgProof>> out;
+        for (size_t j = 0; j < k; j++) {
+            out.first.push_back(Cell::from_bytes(&c[j * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+            out.second.push_back(KzgProof::from_bytes(&p[j * 48], 48).value());
+        }
+        return out;
+    }
+
+    // One independent recover_cells_and_kzg_proofs_at per unit (cell_indices, cells, want_indices) in one set of launches (want_indices may be
+    // empty: the blob is still recovered and checked).  One Result per unit; a unit whose first two lengths differ is BadArgs for the call.
+    struct RecoverAtUnit { std::vector<size_t> cell_indices; std::vector<Cell> cells; std::vector<size_t> want_indices; };
+    static Result<std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>>> recover_cells_and_kzg_proofs_at_many_sets(
+        const std::vector<RecoverAtUnit> &units, const KzgSettings &s) {
+        const size_t m = units.size();
+        std::vector<size_t> counts, indices, want_counts, want;
+        std::vector<uint8_t> in;
+        for (const RecoverAtUnit &u : units) {
+            if (u.cell_indices.size() != u.cells.size()) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(u.cell_indices.size());
+            indices.insert(indices.end(), u.cell_indices.begin(), u.cell_indices.end());
+            for (const Cell &x : u.cells) in.insert(in.end(), x.data(), x.data() + KZG355_BYTES_PER_CELL);
+            want_counts.push_back(u.want_indices.size());
+            want.insert(want.end(), u.want_indices.begin(), u.want_indices.end());
+        }
+        const size_t total = want.size();
+        std::vector<uint8_t> c((total + 1) * KZG355_BYTES_PER_CELL), p((total + 1) * 48);
+        std::vector<int> st(m + 1, 0);
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        indices.push_back(0);
+        in.push_back(0);
+        want_counts.push_back(0);
+        want.push_back(0);
+        int rc = kzg355_recover_cells_and_kzg_proofs_at_many_sets(c.data(), p.data(), st.data(), counts.data(), indices.data(), in.data(),
+                                                                  want_counts.data(), want.data(), m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_at_many_sets");
+        std::vector<Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>>> out;
+        size_t off = 0;
+        for (size_t i = 0; i < m; off += want_counts[i], i++) {
+            if (st[i]) { out.push_back(from_status(st[i], "recover_cells_and_kzg_proofs_at")); continue; }
+            std::pair<std::vector<Cell>, std::vector<KzgProof>> r;
+            for (size_t j = off; j < off + want_counts[i]; j++) {
+                r.first.push_back(Cell::from_bytes(&c[j * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+                r.second.push_back(KzgProof::from_bytes(&p[j * 48], 48).value());
+            }
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+
     // ---- the three cell calls on device-resident data (kzg355.h: pointer and alignment rules).  The d_* arguments are device pointers on the
     // handle's device; one Result per unit, an Err of the call itself only for whole-call failures (whole_call_failed, below).
     static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_device(const uint8_t *d_commitments, const size_t *d_cell_indices,

@@ -105,6 +105,9 @@ def load():
         "kzg355_compute_cell_kzg_proofs_at": [u8p, u8p, u8p, szp, sz, vp],
         "kzg355_compute_cell_kzg_proofs_at_many": [u8p, u8p, ip, u8p, sz, szp, szp, vp],
         "kzg355_compute_cell_kzg_proofs_at_many_device": [vp, vp, ip, vp, sz, szp, szp, vp],
+        "kzg355_recover_cells_and_kzg_proofs_at": [u8p, u8p, szp, u8p, sz, szp, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_at_many_sets": [u8p, u8p, ip, szp, szp, u8p, szp, szp, sz, vp],
+        "kzg355_recover_cells_and_kzg_proofs_at_many_sets_device": [vp, vp, ip, szp, szp, vp, szp, szp, sz, vp],
         "kzg355_debug_cell_compute_h": [u8p, ip, u8p, sz, vp],
         "kzg355_debug_cell_setup_monomial_all": [u8p, vp],
         "kzg355_verify_cell_kzg_proof_batch_many_device": [bp, ip, vp, vp, vp, vp, sz, sz, vp],
@@ -177,4 +180,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_blob_cell_proofs_batch_many_sets", "kzg355_verify_blob_cell_proofs_batch_many_sets_device",
     "kzg355_debug_blob_cell_batch_intermediates_sets", "kzg355_debug_blob_cell_batch_intermediates_sets_device",
     "kzg355_compute_cell_kzg_proofs_at", "kzg355_compute_cell_kzg_proofs_at_many", "kzg355_compute_cell_kzg_proofs_at_many_device",
+    "kzg355_recover_cells_and_kzg_proofs_at", "kzg355_recover_cells_and_kzg_proofs_at_many_sets",
+    "kzg355_recover_cells_and_kzg_proofs_at_many_sets_device",
 ]

@@ -9,7 +9,7 @@ namespace kzg355_impl {
 static const size_t RC_CELLS_OUT = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES, RC_PROOFS_OUT = (size_t)48 * CC_FFT;   // bytes of output per blob
 
 // The 128-bit mask of an index list (mask[0] bits 0..63, mask[1] bits 64..127); false unless it has 64..128 strictly ascending indices < 128.
-static bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n) {
+bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n) {
     mask[0] = mask[1] = 0;
     if (n < (size_t)CELLS_PER_EXT_BLOB / 2 || n > (size_t)CELLS_PER_EXT_BLOB) return false;
     for (size_t i = 0; i < n; i++) {

@@ -468,6 +468,8 @@ int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
            const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells)> &stage, bool dev_out = false);
+// cell_recover.hip: the 128-bit mask of a known-cell index list (also cell_recover_at.hip); false for a list recovery refuses
+bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n);
 
 // cells.hip: what verify_cell_kzg_proof_batch shares with verify_blob_cell_proofs_batch (blob_cells.hip) -- the setup, the dedup, the buffers of
 // a launch set and the chain on prepared buffers

@@ -329,5 +329,10 @@ void launch_rc_columns(Fr *d_u, const RecoverBlob *d_blobs, int m, const CellCom
 // a refused blob's 128 output cells are left as they are
 void launch_rc_cells(const Fr *d_u, const RecoverBlob *d_blobs, int m, const CellComputeConsts *d_cc, uint8_t *d_cells /* m * 128 * 2048 */,
                      hipStream_t st);
+// ---- k_cell_recover_at.hip: recover_cells_and_kzg_proofs_at, the chosen cells of recovered blobs
+// d_u as launch_rc_columns leaves it with want_cells; pair p's cell (d_pairs[p].cell of the chunk's blob d_pairs[p].blob) goes to
+// d_out + 2048 * d_pairs[p].slot; a pair of a refused blob writes nothing
+void launch_rc_cells_at(const Fr *d_u, const RecoverBlob *d_blobs, const CqPair *d_pairs, int pairs, const CellComputeConsts *d_cc, uint8_t *d_out,
+                        hipStream_t st);
 
 }  // namespace kzg

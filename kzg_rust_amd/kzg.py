@@ -754,6 +754,67 @@ class Kzg:
         of (cells, proofs) tuples or Error; blobs and index_lists of different lengths raise BadArgs."""
         return Kzg._cells_at(blobs, index_lists, s, True, True)
 
+    # ---- chosen cells of recovered blobs (recover_cells_and_kzg_proofs_at): the recovery of recover_cells_and_kzg_proofs, then every wanted
+    # (blob, cell) pair through its own quotient and one MSM ----
+    @staticmethod
+    def _recover_at(units, s, cells, proofs):
+        us = [([int(i) for i in ix], [_b(x, Cell) for x in row], [int(i) for i in want]) for ix, row, want in units]
+        m = len(us)
+        if any(len(ix) != len(row) for ix, row, _ in us):
+            raise BadArgs("length mismatch")
+        if any(i < 0 or i >= 1 << 64 for ix, _, want in us for i in ix + want):
+            raise BadArgs("cell index out of range")
+        kflat = [i for ix, _, _ in us for i in ix]
+        wflat = [i for _, _, want in us for i in want]
+        total = len(wflat)
+        c_out = C.create_string_buffer(BYTES_PER_CELL * max(total, 1)) if cells else None
+        p_out = C.create_string_buffer(48 * max(total, 1)) if proofs else None
+        st = (C.c_int * max(m, 1))()
+        kcounts = (C.c_size_t * max(m, 1))(*[len(ix) for ix, _, _ in us])
+        wcounts = (C.c_size_t * max(m, 1))(*[len(want) for _, _, want in us])
+        kidx = (C.c_size_t * max(len(kflat), 1))(*kflat)
+        widx = (C.c_size_t * max(total, 1))(*wflat)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_at_many_sets(c_out, p_out, st, kcounts, kidx, b"".join(b"".join(row) for _, row, _ in us),
+                                                                    wcounts, widx, m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs_at_many_sets")
+        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
+        praw = p_out.raw if proofs else b""
+        res, off = [], 0
+        for i in range(m):
+            k = len(us[i][2])
+            if st[i] != 0:
+                res.append(_ERRORS.get(st[i], InternalError)("recover_cells_and_kzg_proofs_at"))
+            else:
+                res.append(([Cell(craw[BYTES_PER_CELL * j:BYTES_PER_CELL * (j + 1)]) for j in range(off, off + k)] if cells else None,
+                            [KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if proofs else None))
+            off += k
+        return res
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_at(cell_indices, cells, want_indices, s):
+        """([Cell], [KzgProof]) at want_indices (each < 128, any order, repeats allowed) of the blob known at cell_indices (64..128 strictly
+        ascending indices, cells in the same order): entry j is what recover_cells_and_kzg_proofs returns at index want_indices[j] for the
+        same input, at the price of one MSM per wanted index instead of the FK20 chain.  BadArgs on what that call refuses, on a wanted
+        index >= 128 and on more than 128 of them."""
+        return Kzg._one(Kzg._recover_at([(cell_indices, cells, want_indices)], s, True, True))
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_at_many_sets(units, s):
+        """units: a sequence of (cell_indices, cells, want_indices), every blob with its own two lists (want_indices may be empty: the blob
+        is still recovered and checked); one independent recover_cells_and_kzg_proofs_at per unit in one call.  Returns a list of
+        (cells, proofs) tuples or Error; a unit whose first two lengths differ raises BadArgs."""
+        return Kzg._recover_at(units, s, True, True)
+
+    @staticmethod
+    def recover_missing_cells_and_kzg_proofs(cell_indices, cells, s):
+        """(missing_indices, [Cell], [KzgProof]): the cells and proofs of the blob at the indices below 128 that are not among cell_indices,
+        ascending -- what a node that lacks a few columns needs; the proofs of the known cells arrived with them."""
+        known = {int(i) for i in cell_indices}
+        missing = [i for i in range(CELLS_PER_EXT_BLOB) if i not in known]
+        c, p = Kzg.recover_cells_and_kzg_proofs_at(cell_indices, cells, missing, s)
+        return missing, c, p
+
     @staticmethod
     def debug_cell_compute_h(blobs, s):
         """FK20 intermediates per blob: H_0 .. H_63 compressed (H_63 is the point at infinity), or Error."""
@@ -913,6 +974,32 @@ class Kzg:
         if _whole_call_failed(rc, st, n):
             _check(rc, "compute_cell_kzg_proofs_at_many_device")
         return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("compute_cell_kzg_proofs_at") for i in range(n)]
+
+    @staticmethod
+    def recover_cells_and_kzg_proofs_at_many_sets_device(cell_counts, cell_indices, cells, want_counts, want_indices, s, cells_out=None, proofs_out=None):
+        """recover_cells_and_kzg_proofs_at_many_sets of resident blobs: blob i is known at cell_counts[i] cells, its indices following those of
+        blob i - 1 in cell_indices and its cells those of blob i - 1 in cells (sum of the cell counts * 2048 bytes on the device), and asks for
+        want_counts[i] cells, its wanted indices following those of blob i - 1 in want_indices (the four lists are host sequences).  Slot j of
+        the device tensors cells_out (sum of the want counts * 2048 bytes) and proofs_out (* 48) receives the cell and proof of entry j of
+        want_indices; either may be None, not both.  Returns one entry per blob: None, or the Error of that blob (its output slots are then
+        unspecified)."""
+        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
+        wn, wx = [int(c) for c in want_counts], [int(i) for i in want_indices]
+        m = len(cn)
+        if len(wn) != m or any(v < 0 or v >= 1 << 64 for v in cn + ix + wn + wx) or sum(cn) != len(ix) or sum(wn) != len(wx):
+            raise BadArgs("a count or a cell index out of range, or the counts do not add up to the indices")
+        if cells_out is None and proofs_out is None:
+            raise BadArgs("cells_out and proofs_out are both missing")
+        c_out = Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * len(wx), optional=True)
+        p_out = Kzg._dev(proofs_out, "proofs_out", 48 * len(wx), optional=True)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(ix), optional=m == 0)
+        st = (C.c_int * max(m, 1))()
+        kcounts, wcounts = (C.c_size_t * max(m, 1))(*cn), (C.c_size_t * max(m, 1))(*wn)
+        kidx, widx = (C.c_size_t * max(len(ix), 1))(*ix), (C.c_size_t * max(len(wx), 1))(*wx)
+        rc = lib().kzg355_recover_cells_and_kzg_proofs_at_many_sets_device(c_out, p_out, st, kcounts, kidx, d_cells, wcounts, widx, m, s.handle)
+        if _whole_call_failed(rc, st, m):
+            _check(rc, "recover_cells_and_kzg_proofs_at_many_sets_device")
+        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells_and_kzg_proofs_at") for i in range(m)]
 
     # ---- blobs against their EIP-7594 cell proofs (what a Fulu blob transaction or blobs bundle carries): verify_cell_kzg_proof_batch over all
     # 128 cells of every blob, the cells computed on the device ----

@@ -115,6 +115,17 @@ extern "C" {
                                                   cell_counts: *const usize, cell_indices: *const usize, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_compute_cell_kzg_proofs_at_many_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int, d_blobs: *const u8, n: usize,
                                                          cell_counts: *const usize, cell_indices: *const usize, s: *const kzg355_settings) -> c_int;
+    // chosen cells of recovered blobs and their proofs: the input of recover_cells_and_kzg_proofs_many_sets (blob i known at cell_counts[i] cells),
+    // the output of compute_cell_kzg_proofs_at_many (blob i asks for want_counts[i] cells; output slot j belongs to entry j of want_indices)
+    pub fn kzg355_recover_cells_and_kzg_proofs_at(cells_out: *mut u8, proofs_out: *mut u8, cell_indices: *const usize, cells: *const u8, n: usize,
+                                                  want_indices: *const usize, k: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_cells_and_kzg_proofs_at_many_sets(cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int, cell_counts: *const usize,
+                                                            cell_indices: *const usize, cells: *const u8, want_counts: *const usize,
+                                                            want_indices: *const usize, m: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_cells_and_kzg_proofs_at_many_sets_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int,
+                                                                   cell_counts: *const usize, cell_indices: *const usize, d_cells: *const u8,
+                                                                   want_counts: *const usize, want_indices: *const usize, m: usize,
+                                                                   s: *const kzg355_settings) -> c_int;
     // the three cell calls on device-resident data: d_* are device pointers (byte buffers 16-byte aligned, indices 8-byte aligned); the index set
     // of the recovery stays in host memory; prep_form: 0 by shape, 1 device preparation, 2 host preparation
     pub fn kzg355_verify_cell_kzg_proof_batch_many_device(ok: *mut bool, status: *mut c_int, d_commitments: *const u8, d_cell_indices: *const usize,

@@ -723,6 +723,87 @@ impl Kzg {
             .collect())
     }
 
+    /// The cells of the recovered blob at `want_indices` (each < 128, any order, repeats allowed) and their proofs: entry `j` is what
+    /// `recover_cells_and_kzg_proofs` returns at index `want_indices[j]` for the same input, at the price of one MSM per wanted index instead
+    /// of the FK20 chain.
+    pub fn recover_cells_and_kzg_proofs_at(
+        cell_indices: &[usize],
+        cells: &[Cell],
+        want_indices: &[usize],
+        s: &KzgSettings,
+    ) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
+        let mut res = Self::recover_cells_and_kzg_proofs_at_many_sets(&[(cell_indices, cells, want_indices)], s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// One independent `recover_cells_and_kzg_proofs_at` per unit `(cell_indices, cells, want_indices)` in one set of launches (`want_indices`
+    /// may be empty: the blob is still recovered and checked).  One `Result` per unit; a unit whose first two lengths differ is `BadArgs` for
+    /// the call.
+    pub fn recover_cells_and_kzg_proofs_at_many_sets(
+        units: &[(&[usize], &[Cell], &[usize])],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let m = units.len();
+        if units.iter().any(|(ix, cells, _)| ix.len() != cells.len()) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let counts: Vec<usize> = units.iter().map(|(ix, _, _)| ix.len()).collect();
+        let indices: Vec<usize> = units.iter().flat_map(|(ix, _, _)| ix.iter().copied()).collect();
+        let input: Vec<u8> = units.iter().flat_map(|(_, cells, _)| cells.iter().flat_map(|x| x.iter().copied())).collect();
+        let want_counts: Vec<usize> = units.iter().map(|(_, _, want)| want.len()).collect();
+        let want: Vec<usize> = units.iter().flat_map(|(_, _, want)| want.iter().copied()).collect();
+        let total = want.len();
+        let mut out_cells = vec![0u8; BYTES_PER_CELL * total.max(1)];
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * total.max(1)];
+        let mut st = vec![0i32; m.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_recover_cells_and_kzg_proofs_at_many_sets(out_cells.as_mut_ptr(), proofs.as_mut_ptr(), st.as_mut_ptr(), counts.as_ptr(),
+                                                                  indices.as_ptr(), input.as_ptr(), want_counts.as_ptr(), want.as_ptr(), m, s.raw)
+        };
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_at_many_sets")?;
+        let mut off = 0usize;
+        Ok((0..m)
+            .map(|i| {
+                let (lo, hi) = (off, off + want_counts[i]);
+                off = hi;
+                check(st[i], "recover_cells_and_kzg_proofs_at")?;
+                let cs = (lo..hi).map(|j| Cell::from_bytes(&out_cells[BYTES_PER_CELL * j..BYTES_PER_CELL * (j + 1)])).collect::<Result<Vec<_>, _>>()?;
+                let ps = (lo..hi).map(|j| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[48 * j..48 * (j + 1)]).unwrap())).collect();
+                Ok((cs, ps))
+            })
+            .collect())
+    }
+
+    /// `recover_cells_and_kzg_proofs_at_many_sets` of resident blobs: the known cells (device memory) follow `cell_counts`, and slot `j` of the
+    /// device outputs receives the cell and proof of entry `j` of `want_indices`; the counts and both index lists are host memory.
+    ///
+    /// # Safety
+    /// `d_cells` holds `cell_indices.len()` cells on the handle's device; the outputs `want_indices.len()` cells / proofs; all 16-byte aligned.
+    pub unsafe fn recover_cells_and_kzg_proofs_at_many_sets_device(
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        cell_counts: &[usize],
+        cell_indices: &[usize],
+        d_cells: *const u8,
+        want_counts: &[usize],
+        want_indices: &[usize],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let m = cell_counts.len();
+        if want_counts.len() != m
+            || cell_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c)) != Some(cell_indices.len())
+            || want_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c)) != Some(want_indices.len())
+        {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let mut st = vec![0i32; m.max(1)];
+        let rc = ffi::kzg355_recover_cells_and_kzg_proofs_at_many_sets_device(d_cells_out, d_proofs_out, st.as_mut_ptr(), cell_counts.as_ptr(),
+                                                                              cell_indices.as_ptr(), d_cells, want_counts.as_ptr(),
+                                                                              want_indices.as_ptr(), m, s.raw);
+        whole_call(rc, &st[..m], "recover_cells_and_kzg_proofs_at_many_sets_device")?;
+        Ok((0..m).map(|i| check(st[i], "recover_cells_and_kzg_proofs_at")).collect())
+    }
+
     /// `verify_cell_kzg_proof_batch_many` on device-resident data: the four pointers are DEVICE pointers on the handle's device (byte buffers
     /// 16-byte aligned, the indices 8-byte aligned), group-major, `n_per_group` cells per group; only the verdicts cross PCIe.
     ///
