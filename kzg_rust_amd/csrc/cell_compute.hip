@@ -119,6 +119,16 @@ static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t
     return KZG355_OK;
 }
 
+int cell_call_begin(const kzg355_settings *cs, size_t units, std::unique_ptr<WsGuard> &g, int (*second_setup)(kzg355_settings *, Workspace *)) {
+    if (units > ((size_t)1 << 32) || is_small(cs)) return KZG355_BADARGS;     // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
+    g.reset(new WsGuard(cs));
+    if (!g->w) return KZG355_NO_DEVICE;
+    int rc;
+    if ((rc = ensure_cc_consts(g->s, g->w)) || (second_setup && (rc = second_setup(g->s, g->w)))) return rc;
+    g->s->n_cell_sets.fetch_add(1);
+    return KZG355_OK;
+}
+
 // What the two calls share once the caller has checked its own arguments (`units` > 0 blobs, some output wanted): the remaining refusals, the
 // setups, and the chunk loop.  `reserve` sizes the caller's own workspace buffers for CH blobs; `stage` copies the input of blobs c0 .. c0 + m - 1
 // in (or reads it where it is, for device-resident input) and queues the kernels that leave their coefficients in w->y (when proofs or H are
@@ -129,16 +139,11 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
            const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int, uint8_t *)> &stage,
            bool dev_out) {
     auto refuse = [&](int code) { return refuse_call(status, units, code); };
-    if (units > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
-    if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
-    WsGuard g(cs);
-    if (!g.w) return refuse(KZG355_NO_DEVICE);
-    kzg355_settings *s = g.s; Workspace *w = g.w;
     const bool want_proofs = proofs_out || h_dbg;
+    std::unique_ptr<WsGuard> g;
     int rc;
-    if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
-    if (want_proofs && (rc = ensure_cc_proof_setup(s, w))) return refuse(rc);
-    s->n_cell_sets.fetch_add(1);
+    if ((rc = cell_call_begin(cs, units, g, want_proofs ? ensure_cc_proof_setup : nullptr))) return refuse(rc);
+    kzg355_settings *s = g->s; Workspace *w = g->w;
     const size_t CH = units < CC_CHUNK ? units : CC_CHUNK;
     if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg, dev_out, dev_out && proofs_out))) return refuse(rc);
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
@@ -193,7 +198,7 @@ static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int 
     if (!cs || (!cells_out && !proofs_out && !h_dbg)) return refuse_call(status, n, KZG355_BADARGS);
     if (n == 0) return KZG355_OK;
     if (!blobs) return refuse_call(status, n, KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return refuse_call(status, n, KZG355_BADARGS);
+    if (device && misaligned(cells_out, proofs_out, blobs)) return refuse_call(status, n, KZG355_BADARGS);
     if (cs->multi && !device)
         return cc_fan_out(cs, n, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
             return cc_single(cells_out ? cells_out + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * u0 : nullptr, proofs_out ? proofs_out + (size_t)48 * CC_FFT * u0 : nullptr,

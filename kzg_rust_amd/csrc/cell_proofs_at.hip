@@ -7,9 +7,43 @@
 
 namespace kzg355_impl {
 
-// a chunk's output runs: `len` pairs from the chunk's pair `pair` on land in the call's slots `slot` onwards (a blob the host refused fills no
-// pair and may still take slots, so that the pairs of a chunk are not always one run)
-struct CqRun { size_t pair, slot, len; };
+// coefficients of the chunk's blobs in w->y -> the proofs of its pairs (engine.h)
+int cq_proofs(kzg355_settings *s, Workspace *w, Timed &tm, const CellComputeConsts *cc, const CellChunk &ch, const CqPair *d_pairs, uint8_t *proofs_out,
+              bool device) {
+    const size_t P = ch.pairs.size();
+    hipStream_t st = w->stream;
+    tm.begin("cq_quotient");
+    launch_cq_quotient(w->y.as<Fr>(), d_pairs, (int)P, w->err.as<int>(), cc, w->scal_a.as<Fr>(), st);
+    tm.end();
+    int rc;
+    if ((rc = msm_to_device(s, w, tm, (int)P, nullptr, w->scal_a.as<Fr>()))) return rc;
+    if (!device) HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 48 * P, hipMemcpyDeviceToHost, st));
+    else for (const PlanRun &r : ch.runs)
+        HIPCHK(hipMemcpyAsync(proofs_out + 48 * r.slot, w->out48.as<uint8_t>() + 48 * r.pair, 48 * r.len, hipMemcpyDeviceToDevice, st));
+    return KZG355_OK;
+}
+
+int cq_cells_to_host(Workspace *w, const CellChunk &ch, uint8_t *cells_out) {
+    for (const PlanRun &r : ch.runs)
+        HIPCHK(hipMemcpyAsync(cells_out + (size_t)CELL_BYTES * r.slot, w->records.as<uint8_t>() + (size_t)CELL_BYTES * r.pair, (size_t)CELL_BYTES * r.len,
+                              hipMemcpyDeviceToHost, w->stream));
+    return KZG355_OK;
+}
+
+int cq_finish(Workspace *w, Timed &tm, const CellChunk &ch, const size_t *counts, uint8_t *host_proofs_out, int *status, int &first) {
+    HIPCHK(hipGetLastError());
+    int rc;
+    if ((rc = launch_set_results(w, ch.m)) || (rc = launch_set_wait(w, tm))) return rc;
+    // a refused blob's proofs are not copied into host outputs
+    size_t slot = 0;
+    rc = launch_set_read(w, ch.m, status, 0, [&](size_t i, int &bst) {
+        if (bst == KZG355_OK && host_proofs_out && counts[i])
+            memcpy(host_proofs_out + 48 * slot, w->h_out.as<uint8_t>() + 48 * ch.first_pair[i], 48 * counts[i]);
+        slot += counts[i];
+    });
+    if (first == KZG355_OK) first = rc;
+    return KZG355_OK;
+}
 
 // n > 0 blobs on the device of cs (a replica, for a handle over several devices); the arguments are checked, and the sum of the counts fits.
 // Blob i asks for counts[i] cells, the indices idx[off_i ..]; slot off_i + j of cells_out / proofs_out receives cell idx[off_i + j] and its proof.
@@ -19,46 +53,21 @@ struct CqRun { size_t pair, slot, len; };
 static int cq_run(uint8_t *cells_out, uint8_t *proofs_out, int *status, const uint8_t *blobs, size_t n, const size_t *counts, const size_t *idx,
                   const kzg355_settings *cs, bool device) {
     auto refuse = [&](int code) { return refuse_call(status, n, code); };
-    if (n > ((size_t)1 << 32) || is_small(cs)) return refuse(KZG355_BADARGS);    // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
-    WsGuard g(cs);
-    if (!g.w) return refuse(KZG355_NO_DEVICE);
-    kzg355_settings *s = g.s; Workspace *w = g.w;
+    std::unique_ptr<WsGuard> g;
     int rc;
-    if ((rc = ensure_cc_consts(s, w))) return refuse(rc);
-    if (proofs_out && (rc = ensure_wide_table(s))) return refuse(rc);             // the first call that wants proofs builds the table, as a commitment does
-    s->n_cell_sets.fetch_add(1);
+    if ((rc = cell_call_begin(cs, n, g, proofs_out ? wide_table_setup : nullptr))) return refuse(rc);
+    kzg355_settings *s = g->s; Workspace *w = g->w;
     const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
-    std::vector<CqPair> pairs;
-    std::vector<CqRun> runs;
-    std::vector<int> refused;                                     // the chunk's err words, when the host refuses one of its blobs
-    std::vector<size_t> first_pair;                               // of each blob of the chunk (refused: none)
+    CellChunk ch(CC_CHUNK, CQ_CHUNK);
     Timed tm(s, w);
     int first = KZG355_OK;
     size_t off = 0;                                               // the call's slots before the chunk
     auto run = [&]() -> int {                                     // (HIPCHK returns from here: a failed chunk refuses the whole call)
-    for (size_t c0 = 0; c0 < n;) {
-        // the chunk: whole blobs while their pairs fit CQ_CHUNK (a blob has at most 128) and there are at most CC_CHUNK of them
-        pairs.clear(); runs.clear(); refused.clear(); first_pair.clear();
-        bool any_refused = false;
-        size_t m = 0, slots = 0;
-        for (; c0 + m < n && m < CC_CHUNK; m++) {
-            const size_t cnt = counts[c0 + m], *ix = cnt ? idx + off + slots : nullptr;
-            bool good = cnt <= (size_t)CELLS_PER_EXT_BLOB;
-            for (size_t j = 0; good && j < cnt; j++) good = ix[j] < (size_t)CELLS_PER_EXT_BLOB;
-            if (good && pairs.size() + cnt > CQ_CHUNK) break;
-            first_pair.push_back(pairs.size());
-            refused.push_back(good ? 0 : ERR_NONCANONICAL_FR);   // any err word is this blob's KZG355_BADARGS (status_from_err)
-            any_refused |= !good;
-            if (good && cnt) {
-                if (runs.empty() || runs.back().slot + runs.back().len != slots) runs.push_back(CqRun{pairs.size(), slots, 0});
-                runs.back().len += cnt;
-                // (the host form gathers pair after pair and copies run by run; the device form gathers into the caller's slots)
-                for (size_t j = 0; j < cnt; j++) pairs.push_back(CqPair{(uint32_t)m, (uint32_t)ix[j], device ? slots + j : (uint64_t)pairs.size()});
-            }
-            slots += cnt;
-        }
-        const size_t P = pairs.size();
+    for (size_t c0 = 0; c0 < n; c0 += ch.m, off += ch.slots) {
+        plan_compute_chunk(ch, counts + c0, idx ? idx + off : nullptr, n - c0, device);
+        const size_t m = ch.m, P = ch.pairs.size();
+        uint8_t *cells_at = cells_out ? cells_out + (size_t)CELL_BYTES * off : nullptr, *proofs_at = proofs_out ? proofs_out + 48 * off : nullptr;
         int crc;
         if ((!device && (crc = w->blobs.ensure((size_t)BLOB_BYTES * m))) || (crc = w->z.ensure(sizeof(CqPair) * P)) ||
             (proofs_out && ((crc = w->y.ensure(sizeof(Fr) * N_FE * m)) || (crc = w->scal_a.ensure(sizeof(Fr) * N_FE * P)) ||
@@ -69,40 +78,19 @@ static int cq_run(uint8_t *cells_out, uint8_t *proofs_out, int *status, const ui
         hipStream_t st = w->stream;
         const uint8_t *d_blobs = device ? blobs + (size_t)BLOB_BYTES * c0 : w->blobs.as<uint8_t>();
         if (!device) HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, st));
-        if (any_refused) HIPCHK(hipMemcpyAsync(w->err.p, refused.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-        if (P) HIPCHK(hipMemcpyAsync(w->z.p, pairs.data(), sizeof(CqPair) * P, hipMemcpyHostToDevice, st));
+        if (ch.any_refused) HIPCHK(hipMemcpyAsync(w->err.p, ch.refused.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+        if (P) HIPCHK(hipMemcpyAsync(w->z.p, ch.pairs.data(), sizeof(CqPair) * P, hipMemcpyHostToDevice, st));
         tm.begin("cc_field");
         launch_cc_field(d_blobs, (int)m, cc, proofs_out ? w->y.as<Fr>() : nullptr, cells_out ? w->q.as<uint8_t>() : nullptr, w->err.as<int>(), st);
         tm.end();
-        if (proofs_out && P) {
-            tm.begin("cq_quotient");
-            launch_cq_quotient(w->y.as<Fr>(), w->z.as<CqPair>(), (int)P, w->err.as<int>(), cc, w->scal_a.as<Fr>(), st);
-            tm.end();
-            if ((crc = msm_to_device(s, w, tm, (int)P, nullptr, w->scal_a.as<Fr>()))) return crc;
-            if (!device) HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 48 * P, hipMemcpyDeviceToHost, st));
-            else for (const CqRun &r : runs)
-                HIPCHK(hipMemcpyAsync(proofs_out + 48 * (off + r.slot), w->out48.as<uint8_t>() + 48 * r.pair, 48 * r.len, hipMemcpyDeviceToDevice, st));
-        }
+        if (proofs_out && P && (crc = cq_proofs(s, w, tm, cc, ch, w->z.as<CqPair>(), proofs_at, device))) return crc;
         if (cells_out && P) {
             tm.begin("cq_gather");
-            launch_cq_gather(w->q.as<uint8_t>(), w->z.as<CqPair>(), (int)P, device ? cells_out + (size_t)CELL_BYTES * off : w->records.as<uint8_t>(), st);
+            launch_cq_gather(w->q.as<uint8_t>(), w->z.as<CqPair>(), (int)P, device ? cells_at : w->records.as<uint8_t>(), st);
             tm.end();
-            if (!device) for (const CqRun &r : runs)
-                HIPCHK(hipMemcpyAsync(cells_out + (size_t)CELL_BYTES * (off + r.slot), w->records.as<uint8_t>() + (size_t)CELL_BYTES * r.pair,
-                                      (size_t)CELL_BYTES * r.len, hipMemcpyDeviceToHost, st));
+            if (!device && (crc = cq_cells_to_host(w, ch, cells_at))) return crc;
         }
-        HIPCHK(hipGetLastError());
-        if ((crc = launch_set_results(w, m)) || (crc = launch_set_wait(w, tm))) return crc;
-        // a refused blob's proofs are not copied into host outputs
-        size_t slot = off;
-        crc = launch_set_read(w, m, status ? status + c0 : nullptr, 0, [&](size_t i, int &bst) {
-            const size_t cnt = counts[c0 + i];
-            if (bst == KZG355_OK && proofs_out && !device && cnt) memcpy(proofs_out + 48 * slot, w->h_out.as<uint8_t>() + 48 * first_pair[i], 48 * cnt);
-            slot += cnt;
-        });
-        if (first == KZG355_OK) first = crc;
-        off += slots;
-        c0 += m;
+        if ((crc = cq_finish(w, tm, ch, counts + c0, device ? nullptr : proofs_at, status ? status + c0 : nullptr, first))) return crc;
     }
     return KZG355_OK;
     };
@@ -116,16 +104,11 @@ static int cq_impl(uint8_t *cells_out, uint8_t *proofs_out, int *status, const u
     if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
     if (n == 0) return KZG355_OK;
     if (!blobs || !counts || n > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)blobs & 15))) return refuse(KZG355_BADARGS);
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (counts[i] > SIZE_MAX / CELL_BYTES - total) return refuse(KZG355_BADARGS);    // the sum, in bytes of cells, stays a size_t
-        total += counts[i];
-    }
-    if (total && !idx) return refuse(KZG355_BADARGS);
+    if (device && misaligned(cells_out, proofs_out, blobs)) return refuse(KZG355_BADARGS);
+    size_t total;
+    if (!sum_counts(total, counts, n) || (total && !idx)) return refuse(KZG355_BADARGS);
     if (cs->multi && !device) {                                   // ranges of blobs over the replicas: a range's indices and slots start at the sum before it
-        std::vector<size_t> first(n + 1, 0);
-        for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + counts[i];
+        const std::vector<size_t> first = prefix_sums(counts, n);
         return cc_fan_out(cs, n, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
             return cq_run(cells_out ? cells_out + (size_t)CELL_BYTES * first[u0] : nullptr, proofs_out ? proofs_out + 48 * first[u0] : nullptr,
                           status ? status + u0 : nullptr, blobs + (size_t)BLOB_BYTES * u0, k, counts + u0, idx ? idx + first[u0] : nullptr, rep, false);

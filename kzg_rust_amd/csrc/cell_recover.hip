@@ -8,101 +8,75 @@ namespace kzg355_impl {
 
 static const size_t RC_CELLS_OUT = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES, RC_PROOFS_OUT = (size_t)48 * CC_FFT;   // bytes of output per blob
 
-// The 128-bit mask of an index list (mask[0] bits 0..63, mask[1] bits 64..127); false unless it has 64..128 strictly ascending indices < 128.
-bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n) {
-    mask[0] = mask[1] = 0;
-    if (n < (size_t)CELLS_PER_EXT_BLOB / 2 || n > (size_t)CELLS_PER_EXT_BLOB) return false;
-    for (size_t i = 0; i < n; i++) {
-        if (idx[i] >= (size_t)CELLS_PER_EXT_BLOB || (i && idx[i] <= idx[i - 1])) return false;
-        mask[idx[i] >> 6] |= (uint64_t)1 << (idx[i] & 63);
+// The field stage of a recover chunk as rs laid it out (engine.h).  Also the first half of recover_cells_and_kzg_proofs_at (cell_recover_at.hip).
+int rc_field_stage(Workspace *w, Timed &tm, const CellComputeConsts *cc, const RecoverStage &rs, int mc, const int *refused, const uint8_t *cells,
+                   bool device, bool want_coef, bool want_cells, const RecoverBlob **d_desc) {
+    hipStream_t st = w->stream;
+    RecoverTables *rt = w->z.as<RecoverTables>();
+    uint64_t *d_up = reinterpret_cast<uint64_t *>(w->z.as<uint8_t>() + rs.masks_off<RecoverTables>());
+    *d_desc = reinterpret_cast<const RecoverBlob *>(w->z.as<uint8_t>() + rs.desc_off<RecoverTables>());
+    size_t dst = 0;
+    for (const auto &c : rs.copies) {
+        HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + dst * CELL_BYTES, cells + c.first * CELL_BYTES, c.second * CELL_BYTES, hipMemcpyHostToDevice, st));
+        dst += c.second;
     }
-    return true;
+    HIPCHK(hipMemcpyAsync(d_up, rs.up.data(), rs.up_bytes(), hipMemcpyHostToDevice, st));
+    if (refused) HIPCHK(hipMemcpyAsync(w->err.p, refused, sizeof(int) * mc, hipMemcpyHostToDevice, st));
+    const uint8_t *d_known = device ? cells + rs.base * CELL_BYTES : w->blobs.as<uint8_t>();
+    tm.begin("rc_vanish");
+    launch_rc_vanish(cc, d_up, (int)rs.sets.size(), rt, st);
+    tm.end();
+    tm.begin("rc_interp");
+    launch_rc_interp(d_known, *d_desc, mc, cc, rt, w->scal_b.as<Fr>(), w->err.as<int>(), st);
+    tm.end();
+    tm.begin("rc_columns");
+    launch_rc_columns(w->scal_b.as<Fr>(), *d_desc, mc, cc, rt, want_coef ? w->y.as<Fr>() : nullptr, want_cells, st);
+    tm.end();
+    return KZG355_OK;
 }
 
 // What every recover call runs, once its arguments are checked (m > 0).  counts null: the shared-set calls, every blob known at the n indices
 // idx (a valid list).  Otherwise blob i is known at counts[i] cells and its index list and cells start counts[0] + .. + counts[i-1] entries
 // into idx and cells (the sum does not overflow); a blob whose list is refused gets KZG355_BADARGS and the others do not notice.
-// Per chunk the distinct masks are numbered (blobs with the same set share one RecoverTables wherever they sit), and w->z holds, one after
-// the other: the chunk's tables, the masks of its sets and the descriptors of its blobs.
+// Per chunk w->z holds, one after the other: the chunk's tables, the masks of its sets and the descriptors of its blobs (cell_plan.h).
 // device: cells, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are
-static_assert(sizeof(RecoverTables) % alignof(RecoverBlob) == 0, "the masks and descriptors behind the tables in w->z are 8-byte aligned");
 static int rc_run(uint8_t *cells_out, uint8_t *proofs_out, int *status, const size_t *counts, const size_t *idx, size_t n, const uint8_t *cells,
                   size_t m, const kzg355_settings *cs, bool device) {
     uint64_t shared_mask[2] = {0, 0};
     if (!counts) rc_mask(shared_mask, idx, n);
-    size_t max_sets = 0, next = 0;                               // tables per chunk; the call's cells before the chunk about to be staged
-    std::vector<uint64_t> up;                                    // what a chunk uploads: 2 * max_sets mask words, then RecoverBlob per blob
+    std::unique_ptr<RecoverStage> rs;                            // made for the call's chunk size
+    size_t next = 0;                                             // the call's cells before the chunk about to be staged
     std::vector<int> refused;                                    // the chunk's err words, when the host refuses one of its blobs
     return cc_run(cs, m, cells_out, proofs_out, nullptr, status,
         // the workspace's buffers by role: blobs = known cells, z = tables, masks and descriptors, scal_b = u (cell interpolants, then P_r(a_k))
         [&](Workspace *w, size_t CH) {
-            max_sets = counts ? CH : 1;
-            up.resize(2 * max_sets + sizeof(RecoverBlob) / sizeof(uint64_t) * CH);
+            rs.reset(new RecoverStage(CH, counts ? CH : 1));
             int rc;
             if ((!device && (rc = w->blobs.ensure((size_t)CELL_BYTES * (counts ? (size_t)CELLS_PER_EXT_BLOB : n) * CH))) ||
-                (rc = w->z.ensure(sizeof(RecoverTables) * max_sets + sizeof(uint64_t) * up.size())))
+                (rc = w->z.ensure(rs->end_off<RecoverTables>())))
                 return rc;
             return w->scal_b.ensure(sizeof(Fr) * CELLS_PER_EXT_BLOB * CELL_FE * CH);
         },
         [&](Workspace *w, Timed &tm, size_t c0, int mc, uint8_t *d_cells) -> int {
             const CellComputeConsts *cc = cs->cc_consts.as<CellComputeConsts>();
-            RecoverTables *rt = w->z.as<RecoverTables>();
-            uint64_t *d_up = reinterpret_cast<uint64_t *>(rt + max_sets);
-            const RecoverBlob *d_desc = reinterpret_cast<const RecoverBlob *>(d_up + 2 * max_sets);
-            RecoverBlob *desc = reinterpret_cast<RecoverBlob *>(up.data() + 2 * max_sets);
-            hipStream_t st = w->stream;
-            // the chunk's sets and descriptors.  The host form packs the accepted blobs' cells into w->blobs (at most 128 each, whatever a refused
-            // blob's count says), run of neighbours by run; the device form reads them where they are, from the chunk's first cell on.
-            std::map<std::pair<uint64_t, uint64_t>, int> sets;
-            const size_t base = next;
-            size_t staged = 0, run_src = 0, run_dst = 0, run_len = 0;
             bool any_refused = false;
             refused.assign(mc, 0);
-            auto flush = [&]() -> int {
-                if (run_len) HIPCHK(hipMemcpyAsync(w->blobs.as<uint8_t>() + run_dst * CELL_BYTES, cells + run_src * CELL_BYTES, run_len * CELL_BYTES,
-                                                   hipMemcpyHostToDevice, st));
-                run_len = 0;
-                return KZG355_OK;
-            };
+            rs->reset(next);
             for (int b = 0; b < mc; b++) {
                 const size_t cnt = counts ? counts[c0 + b] : n;
                 uint64_t mask[2] = {shared_mask[0], shared_mask[1]};
-                int rc;
-                if (counts && !rc_mask(mask, idx + next, cnt)) {
-                    desc[b] = RecoverBlob{0, -1, 0};
-                    refused[b] = ERR_NONCANONICAL_FR;           // any err word is this blob's KZG355_BADARGS (status_from_err)
-                    any_refused = true;
-                    if ((rc = flush())) return rc;
-                } else {
-                    const int set = sets.emplace(std::make_pair(mask[0], mask[1]), (int)sets.size()).first->second;
-                    up[2 * set] = mask[0];
-                    up[2 * set + 1] = mask[1];
-                    desc[b] = RecoverBlob{device ? next - base : staged, set, 0};
-                    if (!device) {
-                        if (!run_len) { run_src = next; run_dst = staged; }
-                        run_len += cnt;
-                        staged += cnt;
-                    }
-                }
+                const bool good = !counts || rc_mask(mask, idx + next, cnt);
+                if (!good) refused[b] = ERR_NONCANONICAL_FR;     // any err word is this blob's KZG355_BADARGS (status_from_err)
+                any_refused |= !good;
+                rs->add(good, mask, cnt, device);
                 next += cnt;
             }
+            const RecoverBlob *d_desc;
             int rc;
-            if ((rc = flush())) return rc;
-            HIPCHK(hipMemcpyAsync(d_up, up.data(), sizeof(uint64_t) * up.size(), hipMemcpyHostToDevice, st));
-            if (any_refused) HIPCHK(hipMemcpyAsync(w->err.p, refused.data(), sizeof(int) * mc, hipMemcpyHostToDevice, st));
-            const uint8_t *d_known = device ? cells + base * CELL_BYTES : w->blobs.as<uint8_t>();
-            tm.begin("rc_vanish");
-            launch_rc_vanish(cc, d_up, (int)sets.size(), rt, st);
-            tm.end();
-            tm.begin("rc_interp");
-            launch_rc_interp(d_known, d_desc, mc, cc, rt, w->scal_b.as<Fr>(), w->err.as<int>(), st);
-            tm.end();
-            tm.begin("rc_columns");
-            launch_rc_columns(w->scal_b.as<Fr>(), d_desc, mc, cc, rt, proofs_out ? w->y.as<Fr>() : nullptr, cells_out != nullptr, st);
-            tm.end();
+            if ((rc = rc_field_stage(w, tm, cc, *rs, mc, any_refused ? refused.data() : nullptr, cells, device, proofs_out, cells_out, &d_desc))) return rc;
             if (cells_out) {
                 tm.begin("rc_cells");
-                launch_rc_cells(w->scal_b.as<Fr>(), d_desc, mc, cc, d_cells, st);
+                launch_rc_cells(w->scal_b.as<Fr>(), d_desc, mc, cc, d_cells, w->stream);
                 tm.end();
             }
             return KZG355_OK;
@@ -118,7 +92,7 @@ static int rc_shared(uint8_t *cells_out, uint8_t *proofs_out, int *status, const
     if (!idx || !rc_mask(mask, idx, n)) return refuse(KZG355_BADARGS);
     if (m == 0) return KZG355_OK;
     if (!cells) return refuse(KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
+    if (device && misaligned(cells_out, proofs_out, cells)) return refuse(KZG355_BADARGS);
     if (cs->multi && !device)                                     // ranges of blobs over the replicas (cc_fan_out)
         return cc_fan_out(cs, m, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
             return rc_run(cells_out ? cells_out + RC_CELLS_OUT * u0 : nullptr, proofs_out ? proofs_out + RC_PROOFS_OUT * u0 : nullptr,
@@ -134,15 +108,11 @@ static int rc_sets(uint8_t *cells_out, uint8_t *proofs_out, int *status, const s
     if (!cs || (!cells_out && !proofs_out)) return refuse(KZG355_BADARGS);
     if (m == 0) return KZG355_OK;
     if (!counts || !idx || !cells || m > ((size_t)1 << 32)) return refuse(KZG355_BADARGS);
-    if (device && (((uintptr_t)cells_out & 15) || ((uintptr_t)proofs_out & 15) || ((uintptr_t)cells & 15))) return refuse(KZG355_BADARGS);
-    size_t total = 0;
-    for (size_t i = 0; i < m; i++) {
-        if (counts[i] > SIZE_MAX / CELL_BYTES - total) return refuse(KZG355_BADARGS);    // the sum, in bytes of cells, stays a size_t
-        total += counts[i];
-    }
+    if (device && misaligned(cells_out, proofs_out, cells)) return refuse(KZG355_BADARGS);
+    size_t total;
+    if (!sum_counts(total, counts, m)) return refuse(KZG355_BADARGS);
     if (cs->multi && !device) {                                   // ranges of blobs over the replicas: a range's indices and cells start at the sum of the counts before it
-        std::vector<size_t> first(m + 1, 0);
-        for (size_t i = 0; i < m; i++) first[i + 1] = first[i] + counts[i];
+        const std::vector<size_t> first = prefix_sums(counts, m);
         return cc_fan_out(cs, m, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
             return rc_run(cells_out ? cells_out + RC_CELLS_OUT * u0 : nullptr, proofs_out ? proofs_out + RC_PROOFS_OUT * u0 : nullptr,
                           status ? status + u0 : nullptr, counts + u0, idx + first[u0], 0, cells + (size_t)CELL_BYTES * first[u0], k, rep, false);

@@ -13,6 +13,8 @@
 //   cell_recover.hip   recover_cells_and_kzg_proofs: index sets, the erasure decoding's field stage
 //   blob_cells.hip     verify_blob_cell_proofs_batch: blobs against all their cell proofs, the extension and the check in one launch set
 //   cell_proofs_at.hip compute_cell_kzg_proofs_at: the proofs of chosen cells, each the commitment to its own quotient (kernels: k_cell_quotient.hip)
+//   cell_recover_at.hip recover_cells_and_kzg_proofs_at: the field stage of the recovery, then the chain of chosen cells
+//   cell_plan.h        the chunk layout of the last three, plain host arithmetic without HIP (included through kernels.h)
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
 // entry point returns KZG355_NO_DEVICE (a HIP call that fails on a device that exists: KZG355_DEVICE_ERROR).
@@ -468,8 +470,29 @@ int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::
 int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
            const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells)> &stage, bool dev_out = false);
-// cell_recover.hip: the 128-bit mask of a known-cell index list (also cell_recover_at.hip); false for a list recovery refuses
-bool rc_mask(uint64_t mask[2], const size_t *idx, size_t n);
+// how every chunked cell call starts (cc_run and the chosen-cell calls): the refusal by size or preset, the workspace (g.w), the field-stage
+// constants, the caller's second setup (the FK20 proof setup or the MSM table; null: none is needed) and, when all that succeeded, the count of
+// the call among the handle's cell launch sets.  Not OK: the code the whole call is refused with.
+int cell_call_begin(const kzg355_settings *cs, size_t units, std::unique_ptr<WsGuard> &g, int (*second_setup)(kzg355_settings *, Workspace *));
+inline int wide_table_setup(kzg355_settings *s, Workspace *) { return ensure_wide_table(s); }   // (the first call that wants proofs builds the table)
+// the device forms take 16-byte aligned device pointers (null is aligned)
+inline bool misaligned(const void *a, const void *b, const void *c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0; }
+// cell_plan.h lays out the chunks of the recover and chosen-cell calls without HIP; its constants are the kernels'
+static_assert(PLAN_CELLS == (size_t)CELLS_PER_EXT_BLOB && PLAN_CELL_BYTES == (size_t)CELL_BYTES && PLAN_REFUSED == ERR_NONCANONICAL_FR, "cell_plan.h");
+// cell_recover.hip: the field stage of a recover chunk that rs has laid out (mc blobs; `cells` is the call's known cells, host or device memory;
+// refused: the chunk's err words, or null when the host refused none).  Queues the host form's copy runs into w->blobs, the upload of the masks
+// and descriptors into w->z behind the tables (RecoverStage::masks_off) and rc_vanish, rc_interp and rc_columns: u in w->scal_b, and with
+// want_coef the coefficients in w->y.  Returns through d_desc where the chunk's descriptors lie on the device.
+int rc_field_stage(Workspace *w, Timed &tm, const CellComputeConsts *cc, const RecoverStage &rs, int mc, const int *refused, const uint8_t *cells,
+                   bool device, bool want_coef, bool want_cells, const RecoverBlob **d_desc);
+// cell_proofs_at.hip: what the chosen-cell calls do with a chunk ch once their field stage is queued; cells_out / proofs_out / status start at the
+// chunk's first slot / blob.  cq_proofs: the coefficients of the chunk's blobs in w->y -> the pairs' proofs (cq_quotient, the MSM), left in
+// w->h_out (host form) or copied run by run into the caller's device slots.  cq_cells_to_host: the gathered cells of w->records, run by run.
+// cq_finish: the statuses' way back, the wait, and per blob its status and (host form; never for a refused blob) its proofs out of w->h_out.
+int cq_proofs(kzg355_settings *s, Workspace *w, Timed &tm, const CellComputeConsts *cc, const CellChunk &ch, const CqPair *d_pairs, uint8_t *proofs_out,
+              bool device);
+int cq_cells_to_host(Workspace *w, const CellChunk &ch, uint8_t *cells_out);
+int cq_finish(Workspace *w, Timed &tm, const CellChunk &ch, const size_t *counts, uint8_t *host_proofs_out, int *status, int &first);
 
 // cells.hip: what verify_cell_kzg_proof_batch shares with verify_blob_cell_proofs_batch (blob_cells.hip) -- the setup, the dedup, the buffers of
 // a launch set and the chain on prepared buffers

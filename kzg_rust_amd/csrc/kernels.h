@@ -11,6 +11,7 @@
 #include "sha256.h"
 #include "pairing_coop.h"
 #include "eval_core.h"
+#include "cell_plan.h"
 
 namespace kzg {
 
@@ -297,8 +298,6 @@ void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *
 void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
 
 // ---- k_cell_quotient.hip: compute_cell_kzg_proofs_at, the proofs of chosen cells (mainnet handles only)
-// a (blob, cell) pair of a chunk: the blob's place in the chunk, the cell index (< 128), and the slot its cell is gathered into
-struct CqPair { uint32_t blob, cell; uint64_t slot; };
 // d_coef and d_err (per blob of the chunk) as launch_cc_field leaves them; d_scal: pairs * 4096 Fr, Montgomery, in blob order -- the d_scalars of
 // launch_msm_wide / launch_digits_from_fr (zeros for a blob whose error word is set)
 void launch_cq_quotient(const Fr *d_coef, const CqPair *d_pairs, int pairs, const int *d_err, const CellComputeConsts *d_cc, Fr *d_scal, hipStream_t st);
@@ -310,12 +309,6 @@ struct RecoverTables {                                        // one per distinc
     Fr sd[CELLS_PER_EXT_BLOB];                               // S(a_k) / (64 * 128), S the vanishing polynomial of the missing cells' a_m
     Fr sci[CELLS_PER_EXT_BLOB];                              // 1 / (128 S(w a_k))
     int pos[CELLS_PER_EXT_BLOB];                             // cell k's place in the set's ascending index list, -1 if missing
-};
-// a blob of the chunk: its index set (the tables are d_rt[set]; set < 0: refused by the host, no transform runs for it) and where its known cells
-// start, in cells from d_cells
-struct RecoverBlob {
-    uint64_t first;
-    int set, pad;
 };
 // workgroup per set of the chunk: pos, sd and sci of d_rt[set] from the set's 128-bit mask (d_masks[2 set] bits 0..63, d_masks[2 set + 1] bits 64..127)
 void launch_rc_vanish(const CellComputeConsts *d_cc, const uint64_t *d_masks, int sets, RecoverTables *d_rt, hipStream_t st);

@@ -310,6 +310,46 @@ def _blob(x, s):
     return b
 
 
+# ---- what the wrappers of the EIP-7594 cell calls share
+def _size_t_arrays(counts, indices, message):
+    """Host sequences as c_size_t arrays, (counts, indices), or BadArgs(message): every value is within 0 <= v < 2^64 and the counts (None: the
+    call takes none) add up to the indices."""
+    cn, ix = None if counts is None else [int(c) for c in counts], [int(i) for i in indices]
+    if any(v < 0 or v >= 1 << 64 for v in (cn or []) + ix) or (cn is not None and sum(cn) != len(ix)):
+        raise BadArgs(message)
+    return None if cn is None else (C.c_size_t * max(len(cn), 1))(*cn), (C.c_size_t * max(len(ix), 1))(*ix)
+
+
+def _cell_buffers(cells, proofs, slots, units):
+    """(cells_out, proofs_out, statuses) of a host-form call with `slots` output slots in all; None for an output that is not asked for"""
+    return (C.create_string_buffer(BYTES_PER_CELL * max(slots, 1)) if cells else None, C.create_string_buffer(48 * max(slots, 1)) if proofs else None,
+            (C.c_int * max(units, 1))())
+
+
+def _cell_results(rc, st, slots, c_out, p_out, call, label):
+    """What a host-form call returns: per unit (cells, proofs) out of the call's output buffers, unit i owning the next slots[i] slots, or
+    Error(label); a failure of the whole call raises."""
+    if _whole_call_failed(rc, st, len(slots)):
+        _check(rc, call)
+    craw, praw = (None if b is None else b.raw for b in (c_out, p_out))      # (.raw copies the whole buffer: once)
+    res, off = [], 0
+    for i, k in enumerate(slots):
+        if st[i] != 0:
+            res.append(_ERRORS.get(st[i], InternalError)(label))
+        else:
+            res.append(([Cell(craw[BYTES_PER_CELL * j:BYTES_PER_CELL * (j + 1)]) for j in range(off, off + k)] if craw is not None else None,
+                        [KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if praw is not None else None))
+        off += k
+    return res
+
+
+def _device_results(rc, st, units, call, label):
+    """What a device form returns: per unit None or Error(label); a failure of the whole call raises."""
+    if _whole_call_failed(rc, st, units):
+        _check(rc, call)
+    return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)(label) for i in range(units)]
+
+
 class Kzg:
     """pub struct Kzg (kzg.rs:983-1079): the seven associated functions, forwarded to the HIP engine."""
 
@@ -566,24 +606,9 @@ class Kzg:
     def _compute_cells(blobs, s, cells, proofs):
         bl = [_b(x, Blob) for x in blobs]
         n = len(bl)
-        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(n, 1)) if cells else None
-        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1)) if proofs else None
-        st = (C.c_int * max(n, 1))()
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * n, n)
         rc = lib().kzg355_compute_cells_and_kzg_proofs_many(c_out, p_out, st, b"".join(bl), n, s.handle)
-        if _whole_call_failed(rc, st, n):
-            _check(rc, "compute_cells_and_kzg_proofs")
-        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
-        praw = p_out.raw if proofs else b""
-        res = []
-        for i in range(n):
-            if st[i] != 0:
-                res.append(_ERRORS.get(st[i], InternalError)("compute_cells"))
-                continue
-            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
-            pb = 48 * CELLS_PER_EXT_BLOB * i
-            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
-                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
-        return res
+        return _cell_results(rc, st, [CELLS_PER_EXT_BLOB] * n, c_out, p_out, "compute_cells_and_kzg_proofs", "compute_cells")
 
     @staticmethod
     def _one(res):
@@ -619,27 +644,10 @@ class Kzg:
         n, m = len(ix), len(rw)
         if any(len(row) != n for row in rw):
             raise BadArgs("length mismatch")
-        if any(i < 0 or i >= 1 << 64 for i in ix):
-            raise BadArgs("cell index out of range")
-        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(m, 1)) if cells else None
-        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1)) if proofs else None
-        st = (C.c_int * max(m, 1))()
-        idx = (C.c_size_t * max(n, 1))(*ix)
+        _, idx = _size_t_arrays(None, ix, "cell index out of range")
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * m, m)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many(c_out, p_out, st, idx, b"".join(b"".join(row) for row in rw), n, m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs")
-        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
-        praw = p_out.raw if proofs else b""
-        res = []
-        for i in range(m):
-            if st[i] != 0:
-                res.append(_ERRORS.get(st[i], InternalError)("recover_cells"))
-                continue
-            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
-            pb = 48 * CELLS_PER_EXT_BLOB * i
-            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
-                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
-        return res
+        return _cell_results(rc, st, [CELLS_PER_EXT_BLOB] * m, c_out, p_out, "recover_cells_and_kzg_proofs", "recover_cells")
 
     @staticmethod
     def recover_cells_and_kzg_proofs(cell_indices, cells, s):
@@ -667,29 +675,10 @@ class Kzg:
         m = len(us)
         if any(len(ix) != len(row) for ix, row in us):
             raise BadArgs("length mismatch")
-        if any(i < 0 or i >= 1 << 64 for ix, _ in us for i in ix):
-            raise BadArgs("cell index out of range")
-        c_out = C.create_string_buffer(BYTES_PER_CELL * CELLS_PER_EXT_BLOB * max(m, 1)) if cells else None
-        p_out = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1)) if proofs else None
-        st = (C.c_int * max(m, 1))()
-        flat = [i for ix, _ in us for i in ix]
-        counts = (C.c_size_t * max(m, 1))(*[len(ix) for ix, _ in us])
-        idx = (C.c_size_t * max(len(flat), 1))(*flat)
+        counts, idx = _size_t_arrays([len(ix) for ix, _ in us], [i for ix, _ in us for i in ix], "cell index out of range")
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * m, m)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many_sets(c_out, p_out, st, counts, idx, b"".join(b"".join(row) for _, row in us), m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs_many_sets")
-        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
-        praw = p_out.raw if proofs else b""
-        res = []
-        for i in range(m):
-            if st[i] != 0:
-                res.append(_ERRORS.get(st[i], InternalError)("recover_cells"))
-                continue
-            cb = BYTES_PER_CELL * CELLS_PER_EXT_BLOB * i
-            pb = 48 * CELLS_PER_EXT_BLOB * i
-            res.append(([Cell(craw[cb + BYTES_PER_CELL * k:cb + BYTES_PER_CELL * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if cells else None,
-                        [KzgProof(praw[pb + 48 * k:pb + 48 * (k + 1)]) for k in range(CELLS_PER_EXT_BLOB)] if proofs else None))
-        return res
+        return _cell_results(rc, st, [CELLS_PER_EXT_BLOB] * m, c_out, p_out, "recover_cells_and_kzg_proofs_many_sets", "recover_cells")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_many_sets(units, s):
@@ -711,30 +700,11 @@ class Kzg:
         n = len(bl)
         if len(lists) != n:
             raise BadArgs("length mismatch")
-        if any(i < 0 or i >= 1 << 64 for ix in lists for i in ix):
-            raise BadArgs("cell index out of range")
-        flat = [i for ix in lists for i in ix]
-        total = len(flat)
-        c_out = C.create_string_buffer(BYTES_PER_CELL * max(total, 1)) if cells else None
-        p_out = C.create_string_buffer(48 * max(total, 1)) if proofs else None
-        st = (C.c_int * max(n, 1))()
-        counts = (C.c_size_t * max(n, 1))(*[len(ix) for ix in lists])
-        idx = (C.c_size_t * max(total, 1))(*flat)
+        slots = [len(ix) for ix in lists]
+        counts, idx = _size_t_arrays(slots, [i for ix in lists for i in ix], "cell index out of range")
+        c_out, p_out, st = _cell_buffers(cells, proofs, sum(slots), n)
         rc = lib().kzg355_compute_cell_kzg_proofs_at_many(c_out, p_out, st, b"".join(bl), n, counts, idx, s.handle)
-        if _whole_call_failed(rc, st, n):
-            _check(rc, "compute_cell_kzg_proofs_at_many")
-        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
-        praw = p_out.raw if proofs else b""
-        res, off = [], 0
-        for i in range(n):
-            k = len(lists[i])
-            if st[i] != 0:
-                res.append(_ERRORS.get(st[i], InternalError)("compute_cell_kzg_proofs_at"))
-            else:
-                res.append(([Cell(craw[BYTES_PER_CELL * j:BYTES_PER_CELL * (j + 1)]) for j in range(off, off + k)] if cells else None,
-                            [KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if proofs else None))
-            off += k
-        return res
+        return _cell_results(rc, st, slots, c_out, p_out, "compute_cell_kzg_proofs_at_many", "compute_cell_kzg_proofs_at")
 
     @staticmethod
     def compute_cell_kzg_proofs_at(blob, cell_indices, s):
@@ -762,34 +732,13 @@ class Kzg:
         m = len(us)
         if any(len(ix) != len(row) for ix, row, _ in us):
             raise BadArgs("length mismatch")
-        if any(i < 0 or i >= 1 << 64 for ix, _, want in us for i in ix + want):
-            raise BadArgs("cell index out of range")
-        kflat = [i for ix, _, _ in us for i in ix]
-        wflat = [i for _, _, want in us for i in want]
-        total = len(wflat)
-        c_out = C.create_string_buffer(BYTES_PER_CELL * max(total, 1)) if cells else None
-        p_out = C.create_string_buffer(48 * max(total, 1)) if proofs else None
-        st = (C.c_int * max(m, 1))()
-        kcounts = (C.c_size_t * max(m, 1))(*[len(ix) for ix, _, _ in us])
-        wcounts = (C.c_size_t * max(m, 1))(*[len(want) for _, _, want in us])
-        kidx = (C.c_size_t * max(len(kflat), 1))(*kflat)
-        widx = (C.c_size_t * max(total, 1))(*wflat)
+        slots = [len(want) for _, _, want in us]
+        kcounts, kidx = _size_t_arrays([len(ix) for ix, _, _ in us], [i for ix, _, _ in us for i in ix], "cell index out of range")
+        wcounts, widx = _size_t_arrays(slots, [i for _, _, want in us for i in want], "cell index out of range")
+        c_out, p_out, st = _cell_buffers(cells, proofs, sum(slots), m)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_at_many_sets(c_out, p_out, st, kcounts, kidx, b"".join(b"".join(row) for _, row, _ in us),
                                                                     wcounts, widx, m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs_at_many_sets")
-        craw = c_out.raw if cells else b""                      # (.raw copies the whole buffer: once)
-        praw = p_out.raw if proofs else b""
-        res, off = [], 0
-        for i in range(m):
-            k = len(us[i][2])
-            if st[i] != 0:
-                res.append(_ERRORS.get(st[i], InternalError)("recover_cells_and_kzg_proofs_at"))
-            else:
-                res.append(([Cell(craw[BYTES_PER_CELL * j:BYTES_PER_CELL * (j + 1)]) for j in range(off, off + k)] if cells else None,
-                            [KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if proofs else None))
-            off += k
-        return res
+        return _cell_results(rc, st, slots, c_out, p_out, "recover_cells_and_kzg_proofs_at_many_sets", "recover_cells_and_kzg_proofs_at")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_at(cell_indices, cells, want_indices, s):
@@ -893,11 +842,10 @@ class Kzg:
         return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
 
     @staticmethod
-    def _cell_outputs(cells_out, proofs_out, units):
+    def _cell_outputs(cells_out, proofs_out, slots):
         if cells_out is None and proofs_out is None:
             raise BadArgs("cells_out and proofs_out are both missing")
-        return (Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * CELLS_PER_EXT_BLOB * units, optional=True),
-                Kzg._dev(proofs_out, "proofs_out", 48 * CELLS_PER_EXT_BLOB * units, optional=True))
+        return Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * slots, optional=True), Kzg._dev(proofs_out, "proofs_out", 48 * slots, optional=True)
 
     @staticmethod
     def compute_cells_and_kzg_proofs_many_device(blobs, n, s, cells_out=None, proofs_out=None):
@@ -907,50 +855,41 @@ class Kzg:
         n = int(n)
         if n < 0:
             raise BadArgs("n out of range")
-        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, n)
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, CELLS_PER_EXT_BLOB * n)
         d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
         st = (C.c_int * max(n, 1))()
         rc = lib().kzg355_compute_cells_and_kzg_proofs_many_device(c_out, p_out, st, d_blobs, n, s.handle)
-        if _whole_call_failed(rc, st, n):
-            _check(rc, "compute_cells_and_kzg_proofs_many_device")
-        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("compute_cells") for i in range(n)]
+        return _device_results(rc, st, n, "compute_cells_and_kzg_proofs_many_device", "compute_cells")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_many_device(cell_indices, cells, m, s, cells_out=None, proofs_out=None):
         """recover_cells_and_kzg_proofs of m resident blobs known at the same cell_indices (a host sequence of 64..128 strictly ascending
         indices): cells holds m * len(cell_indices) * 2048 bytes, blob after blob.  Outputs and return value as
         compute_cells_and_kzg_proofs_many_device."""
-        ix = [int(i) for i in cell_indices]
-        n, m = len(ix), int(m)
-        if m < 0 or any(i < 0 or i >= 1 << 64 for i in ix):
+        cell_indices = list(cell_indices)
+        n, m = len(cell_indices), int(m)
+        if m < 0:
             raise BadArgs("m or a cell index out of range")
-        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, m)
+        _, idx = _size_t_arrays(None, cell_indices, "m or a cell index out of range")
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, CELLS_PER_EXT_BLOB * m)
         d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * n * m, optional=m == 0)
         st = (C.c_int * max(m, 1))()
-        idx = (C.c_size_t * max(n, 1))(*ix)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many_device(c_out, p_out, st, idx, d_cells, n, m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs_many_device")
-        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]
+        return _device_results(rc, st, m, "recover_cells_and_kzg_proofs_many_device", "recover_cells")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_many_sets_device(cell_counts, cell_indices, cells, s, cells_out=None, proofs_out=None):
         """recover_cells_and_kzg_proofs_many_sets of resident blobs: blob i is known at cell_counts[i] cells, its indices following those of
         blob i - 1 in cell_indices (both host sequences) and its cells those of blob i - 1 in cells (sum of the counts * 2048 bytes on the
         device).  Outputs and return value as compute_cells_and_kzg_proofs_many_device."""
-        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
-        m = len(cn)
-        if any(c < 0 or c >= 1 << 64 for c in cn) or any(i < 0 or i >= 1 << 64 for i in ix) or sum(cn) != len(ix):
-            raise BadArgs("a count or a cell index out of range, or the counts do not add up to the indices")
-        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, m)
-        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(ix), optional=m == 0)
+        cell_counts, cell_indices = list(cell_counts), list(cell_indices)
+        counts, idx = _size_t_arrays(cell_counts, cell_indices, "a count or a cell index out of range, or the counts do not add up to the indices")
+        m = len(cell_counts)
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, CELLS_PER_EXT_BLOB * m)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(cell_indices), optional=m == 0)
         st = (C.c_int * max(m, 1))()
-        counts = (C.c_size_t * max(m, 1))(*cn)
-        idx = (C.c_size_t * max(len(ix), 1))(*ix)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many_sets_device(c_out, p_out, st, counts, idx, d_cells, m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs_many_sets_device")
-        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells") for i in range(m)]
+        return _device_results(rc, st, m, "recover_cells_and_kzg_proofs_many_sets_device", "recover_cells")
 
     @staticmethod
     def compute_cell_kzg_proofs_at_many_device(blobs, n, cell_counts, cell_indices, s, cells_out=None, proofs_out=None):
@@ -958,22 +897,16 @@ class Kzg:
         those of blob i - 1 in cell_indices (both host sequences).  Slot j of the device tensors cells_out (sum of the counts * 2048 bytes) and
         proofs_out (* 48) receives the cell and proof of entry j of cell_indices; either may be None, not both.  Returns one entry per blob:
         None, or the Error of that blob (its output slots are then unspecified)."""
-        n = int(n)
-        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
-        if n < 0 or len(cn) != n or any(c < 0 or c >= 1 << 64 for c in cn) or any(i < 0 or i >= 1 << 64 for i in ix) or sum(cn) != len(ix):
-            raise BadArgs("n, a count or a cell index out of range, or the counts do not add up to the indices")
-        if cells_out is None and proofs_out is None:
-            raise BadArgs("cells_out and proofs_out are both missing")
-        c_out = Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * len(ix), optional=True)
-        p_out = Kzg._dev(proofs_out, "proofs_out", 48 * len(ix), optional=True)
+        cell_counts, cell_indices = list(cell_counts), list(cell_indices)
+        n, message = int(n), "n, a count or a cell index out of range, or the counts do not add up to the indices"
+        if n < 0 or len(cell_counts) != n:
+            raise BadArgs(message)
+        counts, idx = _size_t_arrays(cell_counts, cell_indices, message)
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, len(cell_indices))
         d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
         st = (C.c_int * max(n, 1))()
-        counts = (C.c_size_t * max(n, 1))(*cn)
-        idx = (C.c_size_t * max(len(ix), 1))(*ix)
         rc = lib().kzg355_compute_cell_kzg_proofs_at_many_device(c_out, p_out, st, d_blobs, n, counts, idx, s.handle)
-        if _whole_call_failed(rc, st, n):
-            _check(rc, "compute_cell_kzg_proofs_at_many_device")
-        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("compute_cell_kzg_proofs_at") for i in range(n)]
+        return _device_results(rc, st, n, "compute_cell_kzg_proofs_at_many_device", "compute_cell_kzg_proofs_at")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_at_many_sets_device(cell_counts, cell_indices, cells, want_counts, want_indices, s, cells_out=None, proofs_out=None):
@@ -983,23 +916,17 @@ class Kzg:
         the device tensors cells_out (sum of the want counts * 2048 bytes) and proofs_out (* 48) receives the cell and proof of entry j of
         want_indices; either may be None, not both.  Returns one entry per blob: None, or the Error of that blob (its output slots are then
         unspecified)."""
-        cn, ix = [int(c) for c in cell_counts], [int(i) for i in cell_indices]
-        wn, wx = [int(c) for c in want_counts], [int(i) for i in want_indices]
-        m = len(cn)
-        if len(wn) != m or any(v < 0 or v >= 1 << 64 for v in cn + ix + wn + wx) or sum(cn) != len(ix) or sum(wn) != len(wx):
-            raise BadArgs("a count or a cell index out of range, or the counts do not add up to the indices")
-        if cells_out is None and proofs_out is None:
-            raise BadArgs("cells_out and proofs_out are both missing")
-        c_out = Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * len(wx), optional=True)
-        p_out = Kzg._dev(proofs_out, "proofs_out", 48 * len(wx), optional=True)
-        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(ix), optional=m == 0)
+        cell_counts, cell_indices, want_counts, want_indices = list(cell_counts), list(cell_indices), list(want_counts), list(want_indices)
+        m, message = len(cell_counts), "a count or a cell index out of range, or the counts do not add up to the indices"
+        if len(want_counts) != m:
+            raise BadArgs(message)
+        kcounts, kidx = _size_t_arrays(cell_counts, cell_indices, message)
+        wcounts, widx = _size_t_arrays(want_counts, want_indices, message)
+        c_out, p_out = Kzg._cell_outputs(cells_out, proofs_out, len(want_indices))
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(cell_indices), optional=m == 0)
         st = (C.c_int * max(m, 1))()
-        kcounts, wcounts = (C.c_size_t * max(m, 1))(*cn), (C.c_size_t * max(m, 1))(*wn)
-        kidx, widx = (C.c_size_t * max(len(ix), 1))(*ix), (C.c_size_t * max(len(wx), 1))(*wx)
         rc = lib().kzg355_recover_cells_and_kzg_proofs_at_many_sets_device(c_out, p_out, st, kcounts, kidx, d_cells, wcounts, widx, m, s.handle)
-        if _whole_call_failed(rc, st, m):
-            _check(rc, "recover_cells_and_kzg_proofs_at_many_sets_device")
-        return [None if st[i] == 0 else _ERRORS.get(st[i], InternalError)("recover_cells_and_kzg_proofs_at") for i in range(m)]
+        return _device_results(rc, st, m, "recover_cells_and_kzg_proofs_at_many_sets_device", "recover_cells_and_kzg_proofs_at")
 
     # ---- blobs against their EIP-7594 cell proofs (what a Fulu blob transaction or blobs bundle carries): verify_cell_kzg_proof_batch over all
     # 128 cells of every blob, the cells computed on the device ----
