@@ -376,9 +376,9 @@ int kzg355_debug_cell_batch_intermediates(uint8_t *out /* groups*176 */, bool *o
  * A handle over several devices: the non-empty groups go to the devices in contiguous ranges, equal in GROUPS -- so the ranges can be uneven in
  * cells (not measured on several cards).  A group of this call is never cut into blocks, and kzg355_options.force_sharded does not apply to it.
  * kzg355_settings_cell_calls_per_device counts one launch set per device that received a non-empty group.
- * Not offered: a device-resident form (the device preparation, k_cell_prep, is built on one n per call), cutting a group of this call over
- * several devices.  (Per-transaction blob counts for kzg355_verify_blob_cell_proofs_batch_many are offered: its _many_sets form below runs
- * this call's chain with ragged forms of its own kernels.) */
+ * The device-resident form of this call is kzg355_verify_cell_kzg_proof_batch_many_sets_device, below.  Not offered: cutting a group of this
+ * call over several devices.  (Per-transaction blob counts for kzg355_verify_blob_cell_proofs_batch_many are offered: its _many_sets form
+ * below runs this call's chain with ragged forms of its own kernels.) */
 int kzg355_verify_cell_kzg_proof_batch_many_sets(bool *ok /* groups */, int *status /* groups or NULL */, const size_t *cell_counts /* groups */,
                                                  const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
                                                  const uint8_t *proofs /* each: sum of the counts entries, group after group */, size_t groups,
@@ -549,6 +549,28 @@ int kzg355_recover_cells_and_kzg_proofs_many_sets_device(uint8_t *d_cells_out, u
 int kzg355_debug_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,
                                                  const uint8_t *d_commitments, const size_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs,
                                                  size_t n_per_group, size_t groups, int prep_form, const kzg355_settings *s);
+/* kzg355_verify_cell_kzg_proof_batch_many_sets with the four bulk arrays in HBM (sidecars received over RDMA, or the outputs of the compute and
+ * recover *_device calls): device pointers on the handle's first device, the byte buffers 16-byte and the indices 8-byte aligned -- a misaligned
+ * pointer refuses the call as a whole: KZG355_BADARGS -- read where they are; ok, status and cell_counts are HOST pointers.  Layout, results
+ * per group, empty groups, the limits and everything that refuses the call from the counts alone, before any device is touched, are those of
+ * the host form.  One set of launches on that device for all non-empty groups, counted once in kzg355_settings_cell_calls_per_device; a group is
+ * never cut over several devices.  The preparation runs on the device (one workgroup per group; nothing per cell crosses PCIe, only two
+ * offsets per group go up) or, the four arrays copied back, on the host: the rule of kzg355_verify_cell_kzg_proof_batch_many_device applied to
+ * the call's largest group and its number of non-empty groups, and always the host with a group above 16384 cells.  That rule was measured on
+ * uniform shapes only.  On the three ragged shapes timed so far ("Ragged device-resident cell verify": 128 groups of 1 .. 64 cells,
+ * 1024 groups of 1 .. 6, 8 groups of 1000 .. 16000) it chose the host preparation every time: the faster route at the first and the third, a
+ * tie at the second.  There the call was level with copying the arrays back and calling the host form at the two small shapes and took 45 ms
+ * against 70 ms at the large one; with the device preparation it was never the quicker of the two. */
+int kzg355_verify_cell_kzg_proof_batch_many_sets_device(bool *ok /* host, groups */, int *status /* host, groups or NULL */,
+                                                        const size_t *cell_counts /* HOST, groups */, const uint8_t *d_commitments,
+                                                        const size_t *d_cell_indices, const uint8_t *d_cells,
+                                                        const uint8_t *d_proofs /* each: sum of the counts entries */, size_t groups,
+                                                        const kzg355_settings *s);
+/* Test form of the call above: out[176 g ..] as kzg355_debug_cell_batch_intermediates_sets lays it out (zero bytes for a count of 0), prep_form as
+ * in kzg355_debug_cell_batch_intermediates_device (with prep_form 1 and a group above 16384 cells the host still prepares). */
+int kzg355_debug_cell_batch_intermediates_sets_device(uint8_t *out /* host, groups*176 */, bool *ok, int *status, const size_t *cell_counts,
+                                                      const uint8_t *d_commitments, const size_t *d_cell_indices, const uint8_t *d_cells,
+                                                      const uint8_t *d_proofs, size_t groups, int prep_form, const kzg355_settings *s);
 /* How many device-resident cell verify calls on this handle were prepared on the device so far (the others took the host preparation). */
 long kzg355_settings_cell_device_prep_calls(const kzg355_settings *s);
 /* How the cell calls of a handle were spread: returns the number of devices the handle spans (1 for a plain handle) and fills out[d], d < min(cap,

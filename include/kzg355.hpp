@@ -475,6 +475,23 @@ struct Kzg {
         }
         return out;
     }
+    // groups of different sizes: group g is cell_counts[g] entries of the four device arrays, group after group; the counts are host memory
+    static Result<std::vector<Result<bool>>> verify_cell_kzg_proof_batch_many_sets_device(const std::vector<size_t> &cell_counts, const uint8_t *d_commitments,
+                                                                                          const size_t *d_cell_indices, const uint8_t *d_cells,
+                                                                                          const uint8_t *d_proofs, const KzgSettings &s) {
+        const size_t groups = cell_counts.size();
+        std::unique_ptr<bool[]> ok(new bool[groups + 1]());
+        std::vector<int> st(groups + 1, 0);
+        int rc = kzg355_verify_cell_kzg_proof_batch_many_sets_device(ok.get(), st.data(), cell_counts.data(), d_commitments, d_cell_indices, d_cells, d_proofs,
+                                                                     groups, s.raw());
+        st.resize(groups);
+        if (whole_call_failed(rc, st)) return from_status(rc, "verify_cell_kzg_proof_batch_many_sets_device");
+        std::vector<Result<bool>> out;
+        for (size_t g = 0; g < groups; g++) {
+            if (st[g]) out.push_back(from_status(st[g], "verify_cell")); else out.push_back(bool(ok[g]));
+        }
+        return out;
+    }
     // statuses per blob (KZG355_OK or that blob's error); cells and proofs land in the caller's device buffers (either may be null, not both)
     static Result<std::vector<int>> compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, const uint8_t *d_blobs, size_t n,
                                                                              const KzgSettings &s) {

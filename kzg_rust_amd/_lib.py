@@ -115,6 +115,8 @@ def load():
         "kzg355_recover_cells_and_kzg_proofs_many_device": [vp, vp, ip, szp, vp, sz, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many_sets_device": [vp, vp, ip, szp, szp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
+        "kzg355_verify_cell_kzg_proof_batch_many_sets_device": [bp, ip, szp, vp, vp, vp, vp, sz, vp],
+        "kzg355_debug_cell_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, vp, sz, C.c_int, vp],
         "kzg355_settings_cell_calls_per_device": [vp, C.POINTER(C.c_long), sz],
         "kzg355_verify_blob_cell_proofs_batch": [bp, u8p, sz, u8p, sz, u8p, sz, vp],
         "kzg355_verify_blob_cell_proofs_batch_many": [bp, ip, u8p, u8p, u8p, sz, sz, vp],
@@ -177,6 +179,7 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_blob_cell_proofs_batch", "kzg355_verify_blob_cell_proofs_batch_many", "kzg355_verify_blob_cell_proofs_batch_many_device",
     "kzg355_debug_blob_cell_batch_intermediates", "kzg355_debug_blob_cell_batch_intermediates_device",
     "kzg355_verify_cell_kzg_proof_batch_many_sets", "kzg355_debug_cell_batch_intermediates_sets",
+    "kzg355_verify_cell_kzg_proof_batch_many_sets_device", "kzg355_debug_cell_batch_intermediates_sets_device",
     "kzg355_verify_blob_cell_proofs_batch_many_sets", "kzg355_verify_blob_cell_proofs_batch_many_sets_device",
     "kzg355_debug_blob_cell_batch_intermediates_sets", "kzg355_debug_blob_cell_batch_intermediates_sets_device",
     "kzg355_compute_cell_kzg_proofs_at", "kzg355_compute_cell_kzg_proofs_at_many", "kzg355_compute_cell_kzg_proofs_at_many_device",

@@ -313,8 +313,10 @@ void cell_chain(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_ce
 // One set of launches for `groups` whole groups on the device of cs (a replica, for a handle over several devices); the arguments are checked.
 // device = false: the four arrays are host memory (the launch sequence of the host-buffer calls).  device = true: they are device memory on the
 // handle's device; prep_form 0 by size, 1 device preparation, 2 copy back and prepare on the host.
-// goff (host arrays only; groups + 1 entries, strictly increasing; npg is unused): the groups have their own sizes, group i being entries
-// [goff[i], goff[i + 1]) of the four arrays.
+// goff (groups + 1 entries, strictly increasing; npg is unused): the groups have their own sizes, group i being entries [goff[i], goff[i + 1])
+// of the four arrays, host or device.  With device arrays the route is chosen from the largest group and the number of groups (the rule of
+// blob_cells.hip's launch sets; measured on uniform shapes only), and one group above CELL_PREP_MAX_CELLS sends the whole call to the host
+// preparation.  The device preparation gets goff and gseg from here (2 (groups + 1) ints); no per-cell array crosses PCIe.
 static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
                        size_t npg, size_t groups, const kzg355_settings *cs, bool device, int prep_form, const size_t *goff = nullptr) {
     auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
@@ -328,9 +330,11 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     const size_t N = goff ? goff[groups] : npg * groups;
     const int seg_cap = n < CELLS_PER_EXT_BLOB ? n : CELLS_PER_EXT_BLOB;
     hipStream_t st = w->stream;
+    size_t n_max = goff ? 0 : npg;                                // the largest group
+    if (goff) for (size_t i = 0; i < groups; i++) n_max = std::max(n_max, goff[i + 1] - goff[i]);
 
     // ---- prepare: dedup, column sort, transcripts -- by the host from the caller's arrays, by the host from a copy of them, or on the device
-    const bool dev_prep = device && !cell_device_call_prepares_on_host(s, npg, groups, prep_form);
+    const bool dev_prep = device && !cell_device_call_prepares_on_host(s, n_max, groups, prep_form);
     CellHostPrep hp;
     if (!device) {
         cell_host_prep(s, commitments, cell_indices, cells, proofs, npg, groups, hp, 0, npg, goff);
@@ -344,17 +348,27 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
         HIPCHK(hipMemcpyAsync(b_p, proofs, 48 * N, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(b_cells, cells, (size_t)CELL_BYTES * N, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        cell_host_prep(s, b_c, b_idx, b_cells, b_p, npg, groups, hp, 0, npg);
+        cell_host_prep(s, b_c, b_idx, b_cells, b_p, npg, groups, hp, 0, npg, goff);
     }
-    // meta buffer of the device preparation: the host's layout with a fixed seg_cap segments per group, then the unique-commitment counts and
-    // (tables too large for LDS) the dedup tables
-    const int tab_size = dev_prep ? cell_prep_table_slots(n) : 0;
-    const size_t gtab_ints = tab_size > CELL_PREP_LDS_SLOTS ? (size_t)tab_size * groups : 0;
-    const int S = dev_prep ? G * seg_cap : hp.S;
-    const size_t meta_ints = dev_prep ? (size_t)4 * S + (G + 1) + 3 * N + groups + gtab_ints : hp.meta.size();
+    // meta buffer of the device preparation: the host's layout with min(count, 128) segments per group (groups of different sizes: then the
+    // offsets and the group of every cell, as cell_chain reads them), then the unique-commitment counts and (tables too large for LDS) the
+    // dedup tables -- tab_size slots per group, or with goff 4 per cell (k_cell_prep_sets)
+    const int tab_size = dev_prep ? cell_prep_table_slots((int)n_max) : 0;
+    const size_t gtab_ints = tab_size > CELL_PREP_LDS_SLOTS ? (goff ? 4 * N : (size_t)tab_size * groups) : 0;
+    std::vector<int> h_geo;                                       // (device preparation with goff) gseg | goff
+    if (dev_prep && goff) {
+        h_geo.assign(2 * (groups + 1), 0);
+        for (size_t i = 0; i < groups; i++) {
+            h_geo[i + 1] = h_geo[i] + (int)std::min(goff[i + 1] - goff[i], (size_t)CELLS_PER_EXT_BLOB);
+            h_geo[groups + 1 + i + 1] = (int)goff[i + 1];
+        }
+    }
+    const int S = !dev_prep ? hp.S : goff ? h_geo[groups] : G * seg_cap;
+    const size_t sets_ints = goff ? (G + 1) + N : 0;
+    const size_t meta_ints = dev_prep ? (size_t)4 * S + (G + 1) + 3 * N + sets_ints + groups + gtab_ints : hp.meta.size();
 
     // ---- device
-    if ((rc = goff ? cell_reserve_sized(w, true, N, (size_t)cell_terms_sets((int)N, G), groups, S, meta_ints)
+    if ((rc = goff ? cell_reserve_sized(w, !device, N, (size_t)cell_terms_sets((int)N, G), groups, S, meta_ints)
                    : cell_reserve(w, !device, n, groups, S, meta_ints)))
         return refuse(rc);
     Fp *f12 = nullptr;
@@ -365,14 +379,26 @@ static int cell_single(bool *ok, int *status, uint8_t *dbg, const uint8_t *commi
     uint8_t *d_dbg = dbg ? w->out48.as<uint8_t>() + 32 * groups : nullptr;
     if (dev_prep) {
         int *m = w->q.as<int>() + 4 * (size_t)S;
-        int *d_cidx = m + (G + 1) + N, *d_ucount = m + (G + 1) + 3 * N, *d_gtab = gtab_ints ? d_ucount + groups : nullptr;
+        int *d_cidx = m + (G + 1) + N, *d_goff = m + (G + 1) + 3 * N, *d_ucount = d_goff + sets_ints, *d_gtab = gtab_ints ? d_ucount + groups : nullptr;
+        if (goff) {                                               // (pageable: staged before the copies return)
+            HIPCHK(hipMemcpyAsync(m, h_geo.data(), sizeof(int) * (G + 1), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_goff, h_geo.data() + (G + 1), sizeof(int) * (G + 1), hipMemcpyHostToDevice, st));
+        }
         tm.begin("cell_prep");
-        launch_cell_prep(commitments, cell_indices, n, G, tab_size, d_gtab, w->commitments.as<uint8_t>(), w->q.as<int4>(), m, m + (G + 1), d_cidx,
-                         m + (G + 1) + 2 * N, d_ucount, w->err.as<int>(), st);
+        if (goff)
+            launch_cell_prep_sets(commitments, cell_indices, d_goff, m, G, d_gtab, w->commitments.as<uint8_t>(), w->q.as<int4>(), m + (G + 1), d_cidx,
+                                  m + (G + 1) + 2 * N, d_goff + (G + 1), d_ucount, w->err.as<int>(), st);
+        else
+            launch_cell_prep(commitments, cell_indices, n, G, tab_size, d_gtab, w->commitments.as<uint8_t>(), w->q.as<int4>(), m, m + (G + 1), d_cidx,
+                             m + (G + 1) + 2 * N, d_ucount, w->err.as<int>(), st);
         tm.end();
         tm.begin("cell_rhash");
-        launch_cell_rhash(w->commitments.as<uint8_t>(), cell_indices, cells, proofs, d_cidx, d_ucount, n, G, G >= s->rhash_lanes_from, w->digests.as<uint8_t>(),
-                          st);
+        if (goff)
+            launch_cell_rhash_sets(w->commitments.as<uint8_t>(), cell_indices, cells, proofs, d_cidx, d_ucount, d_goff, G, G >= s->rhash_lanes_from,
+                                   w->digests.as<uint8_t>(), st);
+        else
+            launch_cell_rhash(w->commitments.as<uint8_t>(), cell_indices, cells, proofs, d_cidx, d_ucount, n, G, G >= s->rhash_lanes_from,
+                              w->digests.as<uint8_t>(), st);
         tm.end();
         s->n_cell_device_prep.fetch_add(1);
     } else if ((rc = cell_upload(w, hp, hp.dig.data(), device ? nullptr : cells, proofs, npg, 0, npg, groups, goff ? N : 0))) {
@@ -538,13 +564,16 @@ static int cell_impl(bool *ok, int *status, uint8_t *dbg, const uint8_t *commitm
 // counts before it.  Everything that refuses the whole call is decided from the counts alone, before an array is read or a device touched.  An
 // empty group is true / OK on the spot and takes no part in the launch set: the rest are numbered anew, so that the offsets the kernels search
 // are strictly increasing, and their results go back to their places.  The arrays need no packing for that -- an empty group has no entries.
+// device: the four arrays are device memory on the handle's first device (16- / 8-byte aligned, or the call is refused) and the counts stay host
+// memory: one launch set there for all non-empty groups, prep_form as cell_single takes it.
 static const size_t CELL_SETS_MAX_GROUPS = (size_t)1 << 24;
 static int cell_sets_impl(bool *ok, int *status, uint8_t *dbg, const size_t *counts, const uint8_t *commitments, const size_t *cell_indices, const uint8_t *cells,
-                          const uint8_t *proofs, size_t groups, const kzg355_settings *cs) {
+                          const uint8_t *proofs, size_t groups, const kzg355_settings *cs, bool device = false, int prep_form = 0) {
     auto refuse = [&](int code) { return refuse_call(status, groups, code, ok); };
     if (!cs || !ok || (groups > 0 && !counts)) return refuse(KZG355_BADARGS);
     if (groups == 0) return KZG355_OK;
     if (groups > CELL_SETS_MAX_GROUPS) return refuse(KZG355_BADARGS);
+    if (prep_form < 0 || prep_form > 2) return refuse(KZG355_BADARGS);
     size_t total = 0, live = 0;
     for (size_t g = 0; g < groups; g++) {
         if (counts[g] > CELL_MAX_CELLS - total) return refuse(KZG355_BADARGS);       // (so the sum cannot overflow either)
@@ -552,6 +581,8 @@ static int cell_sets_impl(bool *ok, int *status, uint8_t *dbg, const size_t *cou
         live += counts[g] != 0;
     }
     if (total > 0 && (!commitments || !cell_indices || !cells || !proofs)) return refuse(KZG355_BADARGS);
+    if (device && total > 0 && (((uintptr_t)commitments & 15) || ((uintptr_t)cells & 15) || ((uintptr_t)proofs & 15) || ((uintptr_t)cell_indices & 7)))
+        return refuse(KZG355_BADARGS);
     if (is_small(cs)) return refuse(KZG355_BADARGS);             // the cell layout is defined for FIELD_ELEMENTS_PER_BLOB = 4096 only
     // the non-empty groups: where each came from, and the cells before each
     std::vector<size_t> from(live), goff(live + 1, 0);
@@ -577,13 +608,14 @@ static int cell_sets_impl(bool *ok, int *status, uint8_t *dbg, const size_t *cou
         std::vector<size_t> sub(k + 1);
         for (size_t i = 0; i <= k; i++) sub[i] = goff[l0 + i] - c0;
         const int rc = cell_single(l_ok.get() + l0, l_st.data() + l0, dbg ? l_dbg.data() + (size_t)CELL_DEBUG_BYTES * l0 : nullptr, commitments + 48 * c0,
-                                   cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, 0, k, on, false, 0, sub.data());
+                                   cell_indices + c0, cells + (size_t)CELL_BYTES * c0, proofs + 48 * c0, 0, k, on, device, prep_form, sub.data());
         return call_failed(rc) ? refuse_call(l_st.data() + l0, k, rc, l_ok.get() + l0) : rc;      // (a failure of the range is every group's of the range)
     };
     // A handle over several devices: contiguous ranges of the non-empty groups, one launch set per replica that gets any.  A group is never cut
-    // (and force_sharded does not apply); ranges equal in groups can be uneven in cells.
+    // (and force_sharded does not apply); ranges equal in groups can be uneven in cells.  Device-resident arrays live on the handle's first
+    // device and stay there.
     int rc;
-    if (cs->multi) {
+    if (cs->multi && !device) {
         const size_t D = cs->multi->rep.size();
         rc = fan_out(cs, live < D ? live : D, live, run);
     } else {
@@ -635,6 +667,19 @@ int kzg355_debug_cell_batch_intermediates_sets(uint8_t *out, bool *ok, int *stat
                                                const kzg355_settings *s) {
     if (!out) return refuse_call(status, groups, KZG355_BADARGS, ok);
     return cell_sets_impl(ok, status, out, cell_counts, commitments, cell_indices, cells, proofs, groups, s);
+}
+
+int kzg355_verify_cell_kzg_proof_batch_many_sets_device(bool *ok, int *status, const size_t *cell_counts, const uint8_t *d_commitments,
+                                                        const size_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs, size_t groups,
+                                                        const kzg355_settings *s) {
+    return cell_sets_impl(ok, status, nullptr, cell_counts, d_commitments, d_cell_indices, d_cells, d_proofs, groups, s, true, 0);
+}
+
+int kzg355_debug_cell_batch_intermediates_sets_device(uint8_t *out, bool *ok, int *status, const size_t *cell_counts, const uint8_t *d_commitments,
+                                                      const size_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs, size_t groups,
+                                                      int prep_form, const kzg355_settings *s) {
+    if (!out) return refuse_call(status, groups, KZG355_BADARGS, ok);
+    return cell_sets_impl(ok, status, out, cell_counts, d_commitments, d_cell_indices, d_cells, d_proofs, groups, s, true, prep_form);
 }
 
 int kzg355_verify_cell_kzg_proof_batch_many_device(bool *ok, int *status, const uint8_t *d_commitments, const size_t *d_cell_indices, const uint8_t *d_cells,

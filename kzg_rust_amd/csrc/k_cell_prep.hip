@@ -10,6 +10,7 @@
 // The column sort counts with LDS atomics and places serially per column (one thread per column walks the group's cells in order: stable).
 // The segment list has a fixed stride of min(n, 128) slots per group, the columns present first and empty segments (count 0) behind them: the
 // host knows the number of segments, here it would be data, and an empty segment contributes zero to its group's interpolant.
+// k_cell_prep_sets is the same body on groups of different sizes (kzg355_verify_cell_kzg_proof_batch_many_sets_device).
 //
 // k_cell_rhash_lanes / k_cell_rhash_wave: the transcript "RCKZGCBATCH__V1_" | u64be(4096) | u64be(64) | u64be(u) | u64be(n) | unique commitments |
 // per cell: u64be(position) u64be(index) cell proof, gathered from the caller's buffers 16 bytes at a time (every piece of the message is a
@@ -45,21 +46,21 @@ __device__ __forceinline__ uint32_t cp_hash(const Key48 &k) {
 
 constexpr int CP_THREADS = 256;
 constexpr int CP_SORT_TILE = 2048;     // cells whose columns one placement step keeps in LDS
-__global__ void __launch_bounds__(CP_THREADS) k_cell_prep(const uint8_t *commitments, const uint64_t *indices, int npg, int groups, int seg_cap, int tab_size,
-                                                          int *gtab, uint8_t *uc, int4 *segs, int *gseg, int *cell, int *cidx, int *perm, int *ucount,
-                                                          int *err) {
+// k_cell_prep has one body and two entries, as the hash kernels below: the uniform one (every group npg cells, its arithmetic on npg) and the
+// `_sets` one (group g is cells goff[g] .. goff[g + 1] - 1).  The body prepares the npg cells from `base` on as group g: its segment slots are
+// seg0 .. seg0 + seg_cap - 1, its dedup table is `tab` (tab_size slots in HBM) or, with tab null, the LDS one.
+__device__ __forceinline__ void cp_prep_body(const uint8_t *commitments, const uint64_t *indices, size_t base, int npg, int g, size_t seg0, int seg_cap,
+                                             int *tab, int tab_size, uint8_t *uc, int4 *segs, int *cell, int *cidx, int *perm, int *ucount, int *err) {
     __shared__ int tab_l[CELL_PREP_LDS_SLOTS];
     __shared__ uint8_t col_l[CP_SORT_TILE];
     __shared__ int cnt[CELLS_PER_EXT_BLOB], at[CELLS_PER_EXT_BLOB];
     __shared__ int wsum[CP_THREADS / 64], n_segs_l;
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const size_t base = (size_t)g * npg;
-    int *tab = gtab ? gtab + (size_t)g * tab_size : tab_l;        // (gtab is set when tab_size > CELL_PREP_LDS_SLOTS)
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (!tab) tab = tab_l;
     const uint32_t mask = (uint32_t)tab_size - 1u;
 
     for (int t = tid; t < tab_size; t += CP_THREADS) tab[t] = -1;
     if (tid < CELLS_PER_EXT_BLOB) cnt[tid] = 0;
-    if (tid == 0) { gseg[g] = g * seg_cap; if (g == groups - 1) gseg[groups] = groups * seg_cap; }
     __syncthreads();
     // cell indices: an index >= 128 is the group's error; the clamped index goes on
     bool bad = false;
@@ -117,11 +118,11 @@ __global__ void __launch_bounds__(CP_THREADS) k_cell_prep(const uint8_t *commitm
         int acc = 0, ord = 0;
         for (int c = 0; c < tid; c++) { acc += cnt[c]; ord += cnt[c] != 0; }
         at[tid] = acc;
-        if (cnt[tid]) segs[(size_t)g * seg_cap + ord] = make_int4(g, tid, (int)base + acc, cnt[tid]);
+        if (cnt[tid]) segs[seg0 + ord] = make_int4(g, tid, (int)base + acc, cnt[tid]);
         if (tid == CELLS_PER_EXT_BLOB - 1) n_segs_l = ord + (cnt[tid] != 0);
     }
     __syncthreads();
-    for (int i = n_segs_l + tid; i < seg_cap; i += CP_THREADS) segs[(size_t)g * seg_cap + i] = make_int4(g, 0, (int)base, 0);
+    for (int i = n_segs_l + tid; i < seg_cap; i += CP_THREADS) segs[seg0 + i] = make_int4(g, 0, (int)base, 0);
     int put = tid < CELLS_PER_EXT_BLOB ? at[tid] : 0;
     for (int k0 = 0; k0 < npg; k0 += CP_SORT_TILE) {
         const int len = npg - k0 < CP_SORT_TILE ? npg - k0 : CP_SORT_TILE;
@@ -132,6 +133,26 @@ __global__ void __launch_bounds__(CP_THREADS) k_cell_prep(const uint8_t *commitm
                 if (col_l[i] == tid) perm[base + put++] = (int)base + k0 + i;
         __syncthreads();
     }
+}
+// (gtab is set when tab_size > CELL_PREP_LDS_SLOTS)
+__global__ void __launch_bounds__(CP_THREADS) k_cell_prep(const uint8_t *commitments, const uint64_t *indices, int npg, int groups, int seg_cap, int tab_size,
+                                                          int *gtab, uint8_t *uc, int4 *segs, int *gseg, int *cell, int *cidx, int *perm, int *ucount,
+                                                          int *err) {
+    const int g = blockIdx.x;
+    if (threadIdx.x == 0) { gseg[g] = g * seg_cap; if (g == groups - 1) gseg[groups] = groups * seg_cap; }
+    cp_prep_body(commitments, indices, (size_t)g * npg, npg, g, (size_t)g * seg_cap, seg_cap, gtab ? gtab + (size_t)g * tab_size : nullptr, tab_size, uc,
+                 segs, cell, cidx, perm, ucount, err);
+}
+// Groups of different sizes: the table of a group of n cells has cell_prep_table_slots(n) < 4 n slots, so an HBM one at gtab + 4 goff[g] ends
+// before its neighbour's begins (gtab: 4 ints per cell of the launch set, or null when no group's table exceeds LDS).  gseg (the prefix sums of
+// min(count, 128)) comes from the host, which knows the counts; the group of every cell is written here.
+__global__ void __launch_bounds__(CP_THREADS) k_cell_prep_sets(const uint8_t *commitments, const uint64_t *indices, const int *goff, const int *gseg,
+                                                               int *gtab, uint8_t *uc, int4 *segs, int *cell, int *cidx, int *perm, int *cgrp,
+                                                               int *ucount, int *err) {
+    const int g = blockIdx.x, base = goff[g], npg = goff[g + 1] - base, tab_size = cell_prep_table_slots(npg);
+    for (int k = threadIdx.x; k < npg; k += CP_THREADS) cgrp[base + k] = g;
+    cp_prep_body(commitments, indices, (size_t)base, npg, g, (size_t)gseg[g], npg < CELLS_PER_EXT_BLOB ? npg : CELLS_PER_EXT_BLOB,
+                 tab_size > CELL_PREP_LDS_SLOTS ? gtab + 4 * (size_t)base : nullptr, tab_size, uc, segs, cell, cidx, perm, ucount, err);
 }
 
 // ------------------------------------------------------------------------------------------------ transcript hash
@@ -191,7 +212,7 @@ __device__ __forceinline__ void cp_store_digest(uint8_t *digests, int g, const u
 }
 
 // Each hash kernel has one body and two entries: the uniform one (every group npg cells) and the `_sets` one (group g is cells goff[g] ..
-// goff[g + 1] - 1: whole blobs of different counts, kzg355_verify_blob_cell_proofs_batch_many_sets).  Message assembly, schedule and rounds are
+// goff[g + 1] - 1: the groups of kzg355_verify_cell_kzg_proof_batch_many_sets_device, or whole blobs of different counts).  Message assembly, schedule and rounds are
 // the body's and do not know which entry called.
 // many groups: one lane per group, schedule and rounds in the lane's registers
 __device__ __forceinline__ void cp_rhash_lanes_body(const CellMsg &m, int g, uint8_t *digests) {
@@ -293,6 +314,12 @@ void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int
     const int seg_cap = npg < CELLS_PER_EXT_BLOB ? npg : CELLS_PER_EXT_BLOB;
     hipLaunchKernelGGL(k_cell_prep, dim3(groups), dim3(CP_THREADS), 0, st, d_commitments, reinterpret_cast<const uint64_t *>(d_indices), npg, groups, seg_cap,
                        tab_size, tab_size > CELL_PREP_LDS_SLOTS ? d_gtab : nullptr, d_uc, d_segs, d_gseg, d_cell, d_cidx, d_perm, d_ucount, d_err);
+}
+void launch_cell_prep_sets(const uint8_t *d_commitments, const size_t *d_indices, const int *d_goff, const int *d_gseg, int groups, int *d_gtab,
+                           uint8_t *d_uc, int4 *d_segs, int *d_cell, int *d_cidx, int *d_perm, int *d_cgrp, int *d_ucount, int *d_err, hipStream_t st) {
+    if (groups <= 0) return;
+    hipLaunchKernelGGL(k_cell_prep_sets, dim3(groups), dim3(CP_THREADS), 0, st, d_commitments, reinterpret_cast<const uint64_t *>(d_indices), d_goff, d_gseg,
+                       d_gtab, d_uc, d_segs, d_cell, d_cidx, d_perm, d_cgrp, d_ucount, d_err);
 }
 void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx, const int *d_ucount,
                        int npg, int groups, bool lanes, uint8_t *d_digests, hipStream_t st) {

@@ -236,13 +236,20 @@ void launch_cell_points_sets(const uint8_t *d_commitments, const uint8_t *d_proo
 constexpr int CELL_PREP_LDS_SLOTS = 8192;      // slots of the dedup table k_cell_prep keeps in LDS; a larger table lives in d_gtab
 constexpr int CELL_PREP_MAX_CELLS = 16384;     // cells per group up to which the device prepares (128 blobs x 128 cells: a block as one batch)
 // slots of a group's dedup table: a power of two >= 2 npg
-inline int cell_prep_table_slots(int npg) { int t = 2; while (t < 2 * npg) t <<= 1; return t; }
+KZG_HD int cell_prep_table_slots(int npg) { int t = 2; while (t < 2 * npg) t <<= 1; return t; }
 // d_commitments / d_indices: the caller's (16- / 8-byte aligned).  Out: d_uc (unique commitments per group in first-appearance order, padded to npg
 // with the encoding of infinity), d_ucount[g], d_cell (clamped indices; an index >= 128 sets ERR_CELL_INDEX in d_err[g]), d_cidx, d_perm, and
 // the segment list with a fixed min(npg, 128) slots per group (d_gseg[g] = g * that; empty segments have count 0).  d_gtab: groups * tab_size
 // ints when tab_size > CELL_PREP_LDS_SLOTS, unused otherwise.
 void launch_cell_prep(const uint8_t *d_commitments, const size_t *d_indices, int npg, int groups, int tab_size, int *d_gtab, uint8_t *d_uc, int4 *d_segs,
                       int *d_gseg, int *d_cell, int *d_cidx, int *d_perm, int *d_ucount, int *d_err, hipStream_t st);
+// The same for groups of different sizes (kzg355_verify_cell_kzg_proof_batch_many_sets_device), one workgroup per group: group g is cells
+// d_goff[g] .. d_goff[g + 1] - 1 (d_goff: groups + 1 ints, strictly increasing, each group at most CELL_PREP_MAX_CELLS cells) and its segment
+// slots start at d_gseg[g], the sum of min(count, 128) over the groups before it -- both uploaded by the host, which has the counts.  Out: what
+// launch_cell_prep leaves, d_uc padded to every group's own count, d_perm in cell numbers of the launch set, and d_cgrp, the group of every
+// cell.  d_gtab: 4 ints per cell of the launch set when some group's table exceeds CELL_PREP_LDS_SLOTS (group g's at 4 d_goff[g]), else unused.
+void launch_cell_prep_sets(const uint8_t *d_commitments, const size_t *d_indices, const int *d_goff, const int *d_gseg, int groups, int *d_gtab,
+                           uint8_t *d_uc, int4 *d_segs, int *d_cell, int *d_cidx, int *d_perm, int *d_cgrp, int *d_ucount, int *d_err, hipStream_t st);
 // the transcript digests (32 bytes per group, as launch_cell_scalars takes them), gathered from the caller's buffers; lanes: one lane per group
 // (many groups), else one wave per group
 void launch_cell_rhash(const uint8_t *d_uc, const size_t *d_indices, const uint8_t *d_cells, const uint8_t *d_proofs, const int *d_cidx, const int *d_ucount,

@@ -842,6 +842,42 @@ class Kzg:
         return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
 
     @staticmethod
+    def _cell_many_sets_device(commitments, cell_indices, cells, proofs, cell_counts, s, prep_form, debug):
+        counts = [int(c) for c in cell_counts]
+        if any(c < 0 or c >= 1 << 64 for c in counts) or prep_form not in (0, 1, 2):
+            raise BadArgs("cell_counts or prep_form out of range")
+        N, G = sum(counts), len(counts)
+        ptrs = (Kzg._dev(commitments, "commitments", 48 * N, optional=N == 0), Kzg._dev(cell_indices, "cell_indices", N, "int64", optional=N == 0),
+                Kzg._dev(cells, "cells", BYTES_PER_CELL * N, optional=N == 0), Kzg._dev(proofs, "proofs", 48 * N, optional=N == 0))
+        if G == 0:
+            return [], b""
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        cnt = (C.c_size_t * G)(*counts)
+        if debug:
+            out = C.create_string_buffer(176 * G)
+            rc = lib().kzg355_debug_cell_batch_intermediates_sets_device(out, ok, st, cnt, *ptrs, G, prep_form, s.handle)
+        else:
+            rc = lib().kzg355_verify_cell_kzg_proof_batch_many_sets_device(ok, st, cnt, *ptrs, G, s.handle)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_cell_kzg_proof_batch_many_sets_device")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify_cell") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_cell_kzg_proof_batch_many_sets_device(commitments, cell_indices, cells, proofs, cell_counts, s):
+        """verify_cell_kzg_proof_batch_many_sets on device memory: commitments (sum(cell_counts) * 48 bytes, uint8), cell_indices (int64), cells
+        (* 2048) and proofs (* 48), group after group with no padding; cell_counts is a host list.  Returns a list of bool / Error per group."""
+        return Kzg._cell_many_sets_device(commitments, cell_indices, cells, proofs, cell_counts, s, 0, False)[0]
+
+    @staticmethod
+    def debug_cell_batch_intermediates_sets_device(commitments, cell_indices, cells, proofs, cell_counts, s, prep_form=0):
+        """(verdicts, [176 bytes per group; zero bytes for an empty group]) as debug_cell_batch_intermediates_sets; prep_form 0 by shape, 1 device
+        preparation, 2 host preparation."""
+        res, raw = Kzg._cell_many_sets_device(commitments, cell_indices, cells, proofs, cell_counts, s, prep_form, True)
+        return res, [raw[176 * i:176 * i + 176] for i in range(len(res))]
+
+    @staticmethod
     def _cell_outputs(cells_out, proofs_out, slots):
         if cells_out is None and proofs_out is None:
             raise BadArgs("cells_out and proofs_out are both missing")

@@ -141,6 +141,13 @@ extern "C" {
     pub fn kzg355_debug_cell_batch_intermediates_device(out: *mut u8, ok: *mut bool, status: *mut c_int, d_commitments: *const u8,
                                                         d_cell_indices: *const usize, d_cells: *const u8, d_proofs: *const u8, n_per_group: usize,
                                                         groups: usize, prep_form: c_int, s: *const kzg355_settings) -> c_int;
+    // groups of different sizes on device-resident data: cell_counts stays in host memory, the four arrays hold the sum of the counts entries
+    pub fn kzg355_verify_cell_kzg_proof_batch_many_sets_device(ok: *mut bool, status: *mut c_int, cell_counts: *const usize, d_commitments: *const u8,
+                                                               d_cell_indices: *const usize, d_cells: *const u8, d_proofs: *const u8, groups: usize,
+                                                               s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_debug_cell_batch_intermediates_sets_device(out: *mut u8, ok: *mut bool, status: *mut c_int, cell_counts: *const usize,
+                                                             d_commitments: *const u8, d_cell_indices: *const usize, d_cells: *const u8,
+                                                             d_proofs: *const u8, groups: usize, prep_form: c_int, s: *const kzg355_settings) -> c_int;
     // blobs against their EIP-7594 cell proofs (the Fulu counterpart of verify_blob_kzg_proof_batch): blobs n*131072, commitments n*48, cell_proofs
     // n*128*48; interp_form: 0 what the call does, 1 from the blobs' coefficients, 2 the column kernel over the computed cells
     pub fn kzg355_verify_blob_cell_proofs_batch(ok: *mut bool, blobs: *const u8, n_blobs: usize, commitments: *const u8, n_commitments: usize,

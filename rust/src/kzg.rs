@@ -826,6 +826,28 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
     }
 
+    /// `verify_cell_kzg_proof_batch_many_sets` on device-resident data: group `g` is `cell_counts[g]` entries of the four DEVICE arrays (byte
+    /// buffers 16-byte aligned, the indices 8-byte aligned), group after group; `cell_counts` is host memory.  An empty group is `Ok(true)`.
+    ///
+    /// # Safety
+    /// The pointers must be valid device allocations of the sum of the counts entries each, untouched until the call returns.
+    pub unsafe fn verify_cell_kzg_proof_batch_many_sets_device(
+        cell_counts: &[usize],
+        d_commitments: *const u8,
+        d_cell_indices: *const usize,
+        d_cells: *const u8,
+        d_proofs: *const u8,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let groups = cell_counts.len();
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = ffi::kzg355_verify_cell_kzg_proof_batch_many_sets_device(ok.as_mut_ptr(), st.as_mut_ptr(), cell_counts.as_ptr(), d_commitments,
+                                                                          d_cell_indices, d_cells, d_proofs, groups, s.raw);
+        whole_call(rc, &st[..groups], "verify_cell_kzg_proof_batch_many_sets_device")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_cell").map(|_| ok[g])).collect())
+    }
+
     /// `compute_cells_and_kzg_proofs` of `n` resident blobs into the caller's device buffers (either may be null, not both); one `Result` per
     /// blob, the output slots of a failed blob unspecified.
     ///
