@@ -544,6 +544,48 @@ int kzg355_recover_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out /* m*12
  * misaligned pointer refuses the call as a whole); counts and indices stay HOST arguments.  The cells are read where they are. */
 int kzg355_recover_cells_and_kzg_proofs_many_sets_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const size_t *cell_counts,
                                                          const size_t *cell_indices, const uint8_t *d_cells, size_t m, const kzg355_settings *s);
+/* ---- commitments out of the FK20 chain --------------------------------------------------------------------------------------------------------
+ * The six calls below are kzg355_compute_cells_and_kzg_proofs_many, kzg355_recover_cells_and_kzg_proofs_many, .._many_sets and their *_device
+ * forms with one more output in front: commitments_out, 48 bytes per blob, the blob's KZG commitment (what kzg355_blob_to_kzg_commitment
+ * returns for it; the zero polynomial gives c0 00..00).  The chain computes it on its way to the proofs: slot 63 of the 128-point convolution
+ * whose slots 0..62 are the proofs' H_e is sum_m f_m [tau^m]_1, so a block builder gets commitment, cells and proofs
+ * from one call and no wide MSM table is built, and a node that rebuilt blobs from columns can compare 48 bytes per blob with the block's
+ * blob_kzg_commitments.  Any of the three outputs may be NULL (that part is not computed), not all three: KZG355_BADARGS, every status marked.
+ * With commitments_out == NULL a call is the one it is named after, byte for byte, and every other rule of that call holds unchanged: per-blob
+ * statuses, what refuses the call as a whole, n == 0, mainnet handles only, chunks, the spread over the devices of a handle over several
+ * (host forms).  The commitment slot of a blob whose status is not KZG355_OK is unspecified, like its other slots.  Recovery from more than 64
+ * cells that lie on no polynomial of degree < 4096 returns the commitment of the 4096 coefficients the algorithm keeps, so that the
+ * comparison with the expected commitment is what shows such cells up.  A call that wants commitments alone is legal: it builds the proof
+ * setup (384 MiB table) and runs the chain up to the inverse G1 transform; for computing, kzg355_blob_to_kzg_commitment_many is the cheaper
+ * route to commitments alone.  *_device: d_commitments_out is device memory on the handle's first device, 16-byte aligned like the other
+ * pointers (a misaligned one refuses the call as a whole, and nothing is written). */
+int kzg355_compute_commitments_cells_and_kzg_proofs_many(uint8_t *commitments_out /* n*48 or NULL */, uint8_t *cells_out /* n*128*2048 or NULL */,
+                                                         uint8_t *proofs_out /* n*128*48 or NULL */, int *status /* n or NULL */,
+                                                         const uint8_t *blobs, size_t n, const kzg355_settings *s);
+int kzg355_compute_commitments_cells_and_kzg_proofs_many_device(uint8_t *d_commitments_out /* n*48 or NULL */,
+                                                                uint8_t *d_cells_out /* n*128*2048 or NULL */,
+                                                                uint8_t *d_proofs_out /* n*128*48 or NULL */, int *status /* host, n or NULL */,
+                                                                const uint8_t *d_blobs, size_t n, const kzg355_settings *s);
+int kzg355_recover_commitments_cells_and_kzg_proofs_many(uint8_t *commitments_out /* m*48 or NULL */, uint8_t *cells_out /* m*128*2048 or NULL */,
+                                                         uint8_t *proofs_out /* m*128*48 or NULL */, int *status /* m or NULL */,
+                                                         const size_t *cell_indices /* n, shared by all blobs */,
+                                                         const uint8_t *cells /* m*n*2048: blob after blob */, size_t n, size_t m,
+                                                         const kzg355_settings *s);
+int kzg355_recover_commitments_cells_and_kzg_proofs_many_device(uint8_t *d_commitments_out /* m*48 or NULL */,
+                                                                uint8_t *d_cells_out /* m*128*2048 or NULL */,
+                                                                uint8_t *d_proofs_out /* m*128*48 or NULL */, int *status /* host, m or NULL */,
+                                                                const size_t *cell_indices /* HOST, n, shared by all blobs */,
+                                                                const uint8_t *d_cells /* m*n*2048: blob after blob */, size_t n, size_t m,
+                                                                const kzg355_settings *s);
+int kzg355_recover_commitments_cells_and_kzg_proofs_many_sets(uint8_t *commitments_out /* m*48 or NULL */,
+                                                              uint8_t *cells_out /* m*128*2048 or NULL */,
+                                                              uint8_t *proofs_out /* m*128*48 or NULL */, int *status /* m or NULL */,
+                                                              const size_t *cell_counts /* m */, const size_t *cell_indices /* sum of the counts */,
+                                                              const uint8_t *cells /* (sum of the counts)*2048 */, size_t m,
+                                                              const kzg355_settings *s);
+int kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device(uint8_t *d_commitments_out, uint8_t *d_cells_out, uint8_t *d_proofs_out,
+                                                                     int *status, const size_t *cell_counts, const size_t *cell_indices,
+                                                                     const uint8_t *d_cells, size_t m, const kzg355_settings *s);
 /* Test form of the device verify call: the 176 bytes per group of kzg355_debug_cell_batch_intermediates, with the preparation pinned by
  * prep_form: 0 by shape (what the call above does), 1 on the device, 2 copy back and prepare on the host; anything else is KZG355_BADARGS. */
 int kzg355_debug_cell_batch_intermediates_device(uint8_t *out /* host, groups*176 */, bool *ok /* host, groups */, int *status /* host, groups or NULL */,

@@ -340,6 +340,96 @@ struct Kzg {
         return out;
     }
 
+    // ---- the compute and recover calls with the blobs' commitments: the FK20 chain computes them on its way to the proofs (slot 63 of the
+    // convolution whose other slots give the proofs), so no second call and no wide MSM table is needed
+    struct CommitmentCellsProofs {
+        KzgCommitment commitment;
+        std::vector<Cell> cells;
+        std::vector<KzgProof> proofs;
+    };
+    // per unit its status, or what the three host output buffers of a *_commitments_* call hold for it
+    static std::vector<Result<CommitmentCellsProofs>> unpack_commitments_cells_proofs(const std::vector<int> &st, const std::vector<uint8_t> &k,
+                                                                                     const std::vector<uint8_t> &c, const std::vector<uint8_t> &p,
+                                                                                     const char *what) {
+        const size_t per_cells = (size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL, per_proofs = (size_t)KZG355_CELLS_PER_EXT_BLOB * 48;
+        std::vector<Result<CommitmentCellsProofs>> out;
+        for (size_t i = 0; i < st.size(); i++) {
+            if (st[i]) { out.push_back(from_status(st[i], what)); continue; }
+            CommitmentCellsProofs r;
+            r.commitment = KzgCommitment::from_bytes(&k[48 * i], 48).value();
+            for (int j = 0; j < KZG355_CELLS_PER_EXT_BLOB; j++) {
+                r.cells.push_back(Cell::from_bytes(&c[per_cells * i + (size_t)j * KZG355_BYTES_PER_CELL], KZG355_BYTES_PER_CELL).value());
+                r.proofs.push_back(KzgProof::from_bytes(&p[per_proofs * i + (size_t)j * 48], 48).value());
+            }
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+    static Result<std::vector<Result<CommitmentCellsProofs>>> compute_commitment_cells_and_kzg_proofs_many(const std::vector<Blob> &blobs,
+                                                                                                           const KzgSettings &s) {
+        const size_t n = blobs.size();
+        std::vector<uint8_t> in((size_t)KZG355_BYTES_PER_BLOB * n + 1), k(48 * (n + 1)),
+            c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL * (n + 1)), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48 * (n + 1));
+        for (size_t i = 0; i < n; i++) std::memcpy(&in[(size_t)KZG355_BYTES_PER_BLOB * i], blobs[i].data(), KZG355_BYTES_PER_BLOB);
+        std::vector<int> st(n + 1, 0);
+        int rc = kzg355_compute_commitments_cells_and_kzg_proofs_many(k.data(), c.data(), p.data(), st.data(), in.data(), n, s.raw());
+        st.resize(n);
+        if (whole_call_failed(rc, st)) return from_status(rc, "compute_commitment_cells_and_kzg_proofs_many");
+        return unpack_commitments_cells_proofs(st, k, c, p, "compute_cells");
+    }
+    static Result<CommitmentCellsProofs> compute_commitment_cells_and_kzg_proofs(const Blob &blob, const KzgSettings &s) {
+        auto res = compute_commitment_cells_and_kzg_proofs_many(std::vector<Blob>{blob}, s);
+        if (res.is_err()) return res.error();
+        return std::move(res.value()[0]);
+    }
+    // m blobs known at the same cell_indices: cells holds blob after blob, cell_indices.size() cells each
+    static Result<std::vector<Result<CommitmentCellsProofs>>> recover_commitment_cells_and_kzg_proofs_many(const std::vector<size_t> &cell_indices,
+                                                                                                           const std::vector<Cell> &cells, size_t m,
+                                                                                                           const KzgSettings &s) {
+        const size_t n = cell_indices.size();
+        if (cells.size() != n * m) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<uint8_t> in(cells.size() * KZG355_BYTES_PER_CELL + 1), k(48 * (m + 1)),
+            c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL * (m + 1)), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48 * (m + 1));
+        for (size_t i = 0; i < cells.size(); i++) std::memcpy(&in[i * KZG355_BYTES_PER_CELL], cells[i].data(), KZG355_BYTES_PER_CELL);
+        std::vector<size_t> idx(cell_indices);
+        idx.push_back(0);                                          // (data() of an empty vector may be null)
+        std::vector<int> st(m + 1, 0);
+        int rc = kzg355_recover_commitments_cells_and_kzg_proofs_many(k.data(), c.data(), p.data(), st.data(), idx.data(), in.data(), n, m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_commitment_cells_and_kzg_proofs_many");
+        return unpack_commitments_cells_proofs(st, k, c, p, "recover_cells");
+    }
+    static Result<CommitmentCellsProofs> recover_commitment_cells_and_kzg_proofs(const std::vector<size_t> &cell_indices, const std::vector<Cell> &cells,
+                                                                                 const KzgSettings &s) {
+        if (cell_indices.size() != cells.size()) return Error{Error::BadArgs, "length mismatch"};
+        auto res = recover_commitment_cells_and_kzg_proofs_many(cell_indices, cells, 1, s);
+        if (res.is_err()) return res.error();
+        return std::move(res.value()[0]);
+    }
+    static Result<std::vector<Result<CommitmentCellsProofs>>> recover_commitment_cells_and_kzg_proofs_many_sets(const std::vector<RecoverUnit> &units,
+                                                                                                                const KzgSettings &s) {
+        const size_t m = units.size();
+        std::vector<size_t> counts, indices;
+        std::vector<uint8_t> in;
+        for (const RecoverUnit &u : units) {
+            if (u.first.size() != u.second.size()) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(u.first.size());
+            indices.insert(indices.end(), u.first.begin(), u.first.end());
+            for (const Cell &c : u.second) in.insert(in.end(), c.data(), c.data() + KZG355_BYTES_PER_CELL);
+        }
+        std::vector<uint8_t> k(48 * (m + 1)), c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL * (m + 1)),
+            p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48 * (m + 1));
+        std::vector<int> st(m + 1, 0);
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        indices.push_back(0);
+        in.push_back(0);
+        int rc = kzg355_recover_commitments_cells_and_kzg_proofs_many_sets(k.data(), c.data(), p.data(), st.data(), counts.data(), indices.data(),
+                                                                           in.data(), m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_commitment_cells_and_kzg_proofs_many_sets");
+        return unpack_commitments_cells_proofs(st, k, c, p, "recover_cells");
+    }
+
     // The cells of a blob at chosen indices (each < 128, any order, repeats allowed) and their proofs, entry j what compute_cells_and_kzg_proofs
     // returns at cell_indices[j]: every index through its own quotient and one MSM instead of the FK20 chain
     static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cell_kzg_proofs_at(const Blob &blob, const std::vector<size_t> &cell_indices,
@@ -529,6 +619,46 @@ struct Kzg {
                                                                       m, s.raw());
         st.resize(m);
         if (whole_call_failed(rc, st)) return from_status(rc, "recover_cells_and_kzg_proofs_many_sets_device");
+        return st;
+    }
+
+    // the three calls above with the blobs' commitments (48 bytes per blob) written to d_commitments_out as well; any of the three outputs may be
+    // null, not all
+    static Result<std::vector<int>> compute_commitment_cells_and_kzg_proofs_many_device(uint8_t *d_commitments_out, uint8_t *d_cells_out,
+                                                                                        uint8_t *d_proofs_out, const uint8_t *d_blobs, size_t n,
+                                                                                        const KzgSettings &s) {
+        std::vector<int> st(n + 1, 0);
+        int rc = kzg355_compute_commitments_cells_and_kzg_proofs_many_device(d_commitments_out, d_cells_out, d_proofs_out, st.data(), d_blobs, n, s.raw());
+        st.resize(n);
+        if (whole_call_failed(rc, st)) return from_status(rc, "compute_commitment_cells_and_kzg_proofs_many_device");
+        return st;
+    }
+    static Result<std::vector<int>> recover_commitment_cells_and_kzg_proofs_many_device(uint8_t *d_commitments_out, uint8_t *d_cells_out,
+                                                                                        uint8_t *d_proofs_out, const std::vector<size_t> &cell_indices,
+                                                                                        const uint8_t *d_cells, size_t m, const KzgSettings &s) {
+        std::vector<int> st(m + 1, 0);
+        int rc = kzg355_recover_commitments_cells_and_kzg_proofs_many_device(d_commitments_out, d_cells_out, d_proofs_out, st.data(), cell_indices.data(),
+                                                                             d_cells, cell_indices.size(), m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_commitment_cells_and_kzg_proofs_many_device");
+        return st;
+    }
+    static Result<std::vector<int>> recover_commitment_cells_and_kzg_proofs_many_sets_device(uint8_t *d_commitments_out, uint8_t *d_cells_out,
+                                                                                             uint8_t *d_proofs_out, const std::vector<size_t> &cell_counts,
+                                                                                             const std::vector<size_t> &cell_indices,
+                                                                                             const uint8_t *d_cells, const KzgSettings &s) {
+        const size_t m = cell_counts.size();
+        size_t total = 0;
+        for (size_t c : cell_counts) {
+            if (c > cell_indices.size() - total) return Error{Error::BadArgs, "length mismatch"};
+            total += c;
+        }
+        if (total != cell_indices.size()) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<int> st(m + 1, 0);
+        int rc = kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device(d_commitments_out, d_cells_out, d_proofs_out, st.data(),
+                                                                                  cell_counts.data(), cell_indices.data(), d_cells, m, s.raw());
+        st.resize(m);
+        if (whole_call_failed(rc, st)) return from_status(rc, "recover_commitment_cells_and_kzg_proofs_many_sets_device");
         return st;
     }
 

@@ -114,6 +114,12 @@ def load():
         "kzg355_compute_cells_and_kzg_proofs_many_device": [vp, vp, ip, vp, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many_device": [vp, vp, ip, szp, vp, sz, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_many_sets_device": [vp, vp, ip, szp, szp, vp, sz, vp],
+        "kzg355_compute_commitments_cells_and_kzg_proofs_many": [u8p, u8p, u8p, ip, u8p, sz, vp],
+        "kzg355_compute_commitments_cells_and_kzg_proofs_many_device": [vp, vp, vp, ip, vp, sz, vp],
+        "kzg355_recover_commitments_cells_and_kzg_proofs_many": [u8p, u8p, u8p, ip, szp, u8p, sz, sz, vp],
+        "kzg355_recover_commitments_cells_and_kzg_proofs_many_device": [vp, vp, vp, ip, szp, vp, sz, sz, vp],
+        "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets": [u8p, u8p, u8p, ip, szp, szp, u8p, sz, vp],
+        "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device": [vp, vp, vp, ip, szp, szp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_device": [u8p, bp, ip, vp, vp, vp, vp, sz, sz, C.c_int, vp],
         "kzg355_verify_cell_kzg_proof_batch_many_sets_device": [bp, ip, szp, vp, vp, vp, vp, sz, vp],
         "kzg355_debug_cell_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, vp, sz, C.c_int, vp],
@@ -185,4 +191,7 @@ EXPORTED_SYMBOLS = [
     "kzg355_compute_cell_kzg_proofs_at", "kzg355_compute_cell_kzg_proofs_at_many", "kzg355_compute_cell_kzg_proofs_at_many_device",
     "kzg355_recover_cells_and_kzg_proofs_at", "kzg355_recover_cells_and_kzg_proofs_at_many_sets",
     "kzg355_recover_cells_and_kzg_proofs_at_many_sets_device",
+    "kzg355_compute_commitments_cells_and_kzg_proofs_many", "kzg355_compute_commitments_cells_and_kzg_proofs_many_device",
+    "kzg355_recover_commitments_cells_and_kzg_proofs_many", "kzg355_recover_commitments_cells_and_kzg_proofs_many_device",
+    "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets", "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device",
 ]

@@ -73,22 +73,24 @@ static int ensure_cc_proof_setup(kzg355_settings *s, Workspace *w) {
 
 // The device chain behind the field stage.  compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs (cell_recover.hip) differ in their field
 // stage only, and both leave the same two things on the device: coefficients in w->y and cells in w->q.  The workspace's buffers by role:
-// y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H.
-// With dev_out the cells and proofs go straight into the caller's device buffers: q is not needed, nor out48 when the caller takes the proofs
-// (dev_proofs; H alone leaves them in out48).
-static int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_proofs, bool want_h, bool dev_out, bool dev_proofs) {
+// y = coefficients, scal_a = column scalars, partials = Z, q = cells, out48 = proofs, small = H, commitments = commitments.
+// want_chain: proofs, H or commitments are wanted.  out48 only when proofs (or H, which leaves them there) stay in the workspace (ws_proofs),
+// commitments only when they go to the host (ws_commit).  With dev_out the cells, proofs and commitments go straight into the caller's device
+// buffers and q is not needed.
+static int cc_chain_buffers(Workspace *w, size_t CH, bool want_cells, bool want_chain, bool want_h, bool dev_out, bool ws_proofs, bool ws_commit) {
     int rc;
     if ((rc = w->err.ensure(sizeof(int) * CH)) || (rc = w->h_err.ensure(sizeof(int) * CH)) ||
         (want_cells && !dev_out && (rc = w->q.ensure((size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * CH))) ||
-        (want_proofs && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
-                         (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (!dev_proofs && (rc = w->out48.ensure((size_t)48 * CC_FFT * CH))))) ||
+        (want_chain && ((rc = w->y.ensure(sizeof(Fr) * N_FE * CH)) || (rc = w->scal_a.ensure(sizeof(uint32_t) * 8 * CC_FFT * CELL_FE * CH)) ||
+                        (rc = w->partials.ensure(sizeof(G1Jac) * CC_FFT * CH)) || (ws_proofs && (rc = w->out48.ensure((size_t)48 * CC_FFT * CH))) ||
+                        (ws_commit && (rc = w->commitments.ensure((size_t)48 * CH))))) ||
         (want_h && (rc = w->small.ensure((size_t)48 * CELL_FE * CH))))
         return rc;
     return KZG355_OK;
 }
-// coefficients of m blobs in w->y -> proofs in d_proofs (w->out48, or the caller's device buffer at the chunk's offset; and H in w->small), queued
-// on w->stream
-static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h, uint8_t *d_proofs) {
+// coefficients of m blobs in w->y -> proofs in d_proofs (w->out48, or the caller's device buffer at the chunk's offset; null: none wanted; and H
+// in w->small) and commitments in d_commit (w->commitments or the caller's device buffer; null: none wanted), queued on w->stream
+static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, bool want_h, uint8_t *d_proofs, uint8_t *d_commit) {
     const CellComputeConsts *cc = s->cc_consts.as<CellComputeConsts>();
     hipStream_t st = w->stream;
     tm.begin("cc_columns");
@@ -98,18 +100,19 @@ static void cc_proof_chain(kzg355_settings *s, Workspace *w, Timed &tm, int m, b
     launch_cc_msm(w->scal_a.as<uint32_t>(), m, s->cc_table.as<G1Affine>(), w->partials.as<G1Jac>(), st);
     tm.end();
     tm.begin("cc_proofs");
-    launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, d_proofs, want_h ? w->small.as<uint8_t>() : nullptr, st);
+    launch_cc_proofs(w->partials.as<G1Jac>(), m, cc, d_proofs, want_h ? w->small.as<uint8_t>() : nullptr, d_commit, st);
     tm.end();
 }
 // the results of a chunk of m blobs (blob c0 onwards) back to the host (dev_out: they are in the caller's device buffers already), the wait, and
 // the per-blob statuses
-static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, size_t c0, int m, int &first,
-                            bool dev_out) {
+static int cc_collect_chunk(Workspace *w, Timed &tm, uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
+                            size_t c0, int m, int &first, bool dev_out) {
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     hipStream_t st = w->stream;
     HIPCHK(hipGetLastError());
     int rc;
     if ((rc = launch_set_results(w, m))) return rc;
+    if (commitments_out && !dev_out) HIPCHK(hipMemcpyAsync(commitments_out + 48 * c0, w->commitments.p, (size_t)48 * m, hipMemcpyDeviceToHost, st));
     if (cells_out && !dev_out) HIPCHK(hipMemcpyAsync(cells_out + cell_bytes * c0, w->q.p, cell_bytes * m, hipMemcpyDeviceToHost, st));
     if (proofs_out && !dev_out) HIPCHK(hipMemcpyAsync(proofs_out + (size_t)48 * CC_FFT * c0, w->out48.p, (size_t)48 * CC_FFT * m, hipMemcpyDeviceToHost, st));
     if (h_dbg) HIPCHK(hipMemcpyAsync(h_dbg + (size_t)48 * CELL_FE * c0, w->small.p, (size_t)48 * CELL_FE * m, hipMemcpyDeviceToHost, st));
@@ -131,21 +134,23 @@ int cell_call_begin(const kzg355_settings *cs, size_t units, std::unique_ptr<WsG
 
 // What the two calls share once the caller has checked its own arguments (`units` > 0 blobs, some output wanted): the remaining refusals, the
 // setups, and the chunk loop.  `reserve` sizes the caller's own workspace buffers for CH blobs; `stage` copies the input of blobs c0 .. c0 + m - 1
-// in (or reads it where it is, for device-resident input) and queues the kernels that leave their coefficients in w->y (when proofs or H are
-// wanted) and their cells in the d_cells it is handed (when cells are; null otherwise).
-// cells_out / proofs_out: host memory, or with dev_out device memory on the handle's device, 16-byte aligned (the kernels then write there at
-// the chunk's offset: no copy); h_dbg: host memory (any of the three may be null, not all); status (or null): per blob, host.
-int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
-           const std::function<int(Workspace *, size_t)> &reserve, const std::function<int(Workspace *, Timed &, size_t, int, uint8_t *)> &stage,
-           bool dev_out) {
+// in (or reads it where it is, for device-resident input) and queues the kernels that leave their coefficients in w->y (want_chain: proofs, H
+// or commitments are wanted) and their cells in the d_cells it is handed (when cells are; null otherwise).
+// commitments_out / cells_out / proofs_out: host memory, or with dev_out device memory on the handle's device, 16-byte aligned (the kernels then
+// write there at the chunk's offset: no copy); h_dbg: host memory (any of the four may be null, not all); status (or null): per blob, host.
+int cc_run(const kzg355_settings *cs, size_t units, uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
+           const std::function<int(Workspace *, size_t)> &reserve,
+           const std::function<int(Workspace *, Timed &, size_t, int, uint8_t *, bool)> &stage, bool dev_out) {
     auto refuse = [&](int code) { return refuse_call(status, units, code); };
-    const bool want_proofs = proofs_out || h_dbg;
+    const bool want_chain = proofs_out || h_dbg || commitments_out;
+    const bool dev_proofs = dev_out && proofs_out, ws_proofs = (proofs_out || h_dbg) && !dev_proofs;
     std::unique_ptr<WsGuard> g;
     int rc;
-    if ((rc = cell_call_begin(cs, units, g, want_proofs ? ensure_cc_proof_setup : nullptr))) return refuse(rc);
+    if ((rc = cell_call_begin(cs, units, g, want_chain ? ensure_cc_proof_setup : nullptr))) return refuse(rc);
     kzg355_settings *s = g->s; Workspace *w = g->w;
     const size_t CH = units < CC_CHUNK ? units : CC_CHUNK;
-    if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_proofs, h_dbg, dev_out, dev_out && proofs_out))) return refuse(rc);
+    if ((rc = reserve(w, CH)) || (rc = cc_chain_buffers(w, CH, cells_out, want_chain, h_dbg, dev_out, ws_proofs, commitments_out && !dev_out)))
+        return refuse(rc);
     const size_t cell_bytes = (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES;
     Timed tm(s, w);
     int first = KZG355_OK;
@@ -155,10 +160,11 @@ int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t 
         int crc;
         if ((crc = launch_set_begin(w, m))) return crc;           // (cc_chain_buffers has sized the words for CH)
         uint8_t *d_cells = !cells_out ? nullptr : dev_out ? cells_out + cell_bytes * c0 : w->q.as<uint8_t>();
-        uint8_t *d_proofs = dev_out && proofs_out ? proofs_out + (size_t)48 * CC_FFT * c0 : w->out48.as<uint8_t>();
-        if ((crc = stage(w, tm, c0, m, d_cells))) return crc;
-        if (want_proofs) cc_proof_chain(s, w, tm, m, h_dbg, d_proofs);
-        if ((crc = cc_collect_chunk(w, tm, cells_out, proofs_out, h_dbg, status, c0, m, first, dev_out))) return crc;
+        uint8_t *d_proofs = dev_proofs ? proofs_out + (size_t)48 * CC_FFT * c0 : ws_proofs ? w->out48.as<uint8_t>() : nullptr;
+        uint8_t *d_commit = !commitments_out ? nullptr : dev_out ? commitments_out + 48 * c0 : w->commitments.as<uint8_t>();
+        if ((crc = stage(w, tm, c0, m, d_cells, want_chain))) return crc;
+        if (want_chain) cc_proof_chain(s, w, tm, m, h_dbg, d_proofs, d_commit);
+        if ((crc = cc_collect_chunk(w, tm, commitments_out, cells_out, proofs_out, h_dbg, status, c0, m, first, dev_out))) return crc;
     }
     return KZG355_OK;
     };
@@ -176,35 +182,37 @@ int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::
 }
 
 // n blobs on the device of cs (a replica, for a handle over several devices); the arguments are checked
-static int cc_single(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
-                     bool device) {
-    return cc_run(cs, n, cells_out, proofs_out, h_dbg, status,
+static int cc_single(uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n,
+                     const kzg355_settings *cs, bool device) {
+    return cc_run(cs, n, commitments_out, cells_out, proofs_out, h_dbg, status,
         [&](Workspace *w, size_t CH) { return device ? KZG355_OK : w->blobs.ensure((size_t)BLOB_BYTES * CH); },
-        [&](Workspace *w, Timed &tm, size_t c0, int m, uint8_t *d_cells) -> int {
+        [&](Workspace *w, Timed &tm, size_t c0, int m, uint8_t *d_cells, bool want_coef) -> int {
             const uint8_t *d_blobs = device ? blobs + (size_t)BLOB_BYTES * c0 : w->blobs.as<uint8_t>();
             if (!device) HIPCHK(hipMemcpyAsync(w->blobs.p, blobs + (size_t)BLOB_BYTES * c0, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, w->stream));
             tm.begin("cc_field");
-            launch_cc_field(d_blobs, m, cs->cc_consts.as<CellComputeConsts>(), proofs_out || h_dbg ? w->y.as<Fr>() : nullptr, d_cells, w->err.as<int>(),
+            launch_cc_field(d_blobs, m, cs->cc_consts.as<CellComputeConsts>(), want_coef ? w->y.as<Fr>() : nullptr, d_cells, w->err.as<int>(),
                             w->stream);
             tm.end();
             return KZG355_OK;
         }, device);
 }
 
-// device: blobs, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where they are -- on
-// the first device of a handle over several, where they live
-static int cc_impl(uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *cs,
-                   bool device = false) {
-    if (!cs || (!cells_out && !proofs_out && !h_dbg)) return refuse_call(status, n, KZG355_BADARGS);
+// device: blobs, commitments_out, cells_out and proofs_out are device memory on the handle's device (16-byte aligned), read and written where
+// they are -- on the first device of a handle over several, where they live
+static int cc_impl(uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status, const uint8_t *blobs, size_t n,
+                   const kzg355_settings *cs, bool device = false) {
+    if (!cs || (!commitments_out && !cells_out && !proofs_out && !h_dbg)) return refuse_call(status, n, KZG355_BADARGS);
     if (n == 0) return KZG355_OK;
     if (!blobs) return refuse_call(status, n, KZG355_BADARGS);
-    if (device && misaligned(cells_out, proofs_out, blobs)) return refuse_call(status, n, KZG355_BADARGS);
+    if (device && misaligned(commitments_out, cells_out, proofs_out, blobs)) return refuse_call(status, n, KZG355_BADARGS);
     if (cs->multi && !device)
         return cc_fan_out(cs, n, status, [&](const kzg355_settings *rep, size_t u0, size_t k) {
-            return cc_single(cells_out ? cells_out + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * u0 : nullptr, proofs_out ? proofs_out + (size_t)48 * CC_FFT * u0 : nullptr,
-                             h_dbg ? h_dbg + (size_t)48 * CELL_FE * u0 : nullptr, status ? status + u0 : nullptr, blobs + (size_t)BLOB_BYTES * u0, k, rep, false);
+            return cc_single(commitments_out ? commitments_out + 48 * u0 : nullptr,
+                             cells_out ? cells_out + (size_t)CELLS_PER_EXT_BLOB * CELL_BYTES * u0 : nullptr,
+                             proofs_out ? proofs_out + (size_t)48 * CC_FFT * u0 : nullptr, h_dbg ? h_dbg + (size_t)48 * CELL_FE * u0 : nullptr,
+                             status ? status + u0 : nullptr, blobs + (size_t)BLOB_BYTES * u0, k, rep, false);
         });
-    return cc_single(cells_out, proofs_out, h_dbg, status, blobs, n, cs, device);
+    return cc_single(commitments_out, cells_out, proofs_out, h_dbg, status, blobs, n, cs, device);
 }
 
 }  // namespace kzg355_impl
@@ -214,21 +222,31 @@ extern "C" {
 
 int kzg355_compute_cells_and_kzg_proofs_many(uint8_t *cells_out, uint8_t *proofs_out, int *status, const uint8_t *blobs, size_t n,
                                              const kzg355_settings *s) {
-    return cc_impl(cells_out, proofs_out, nullptr, status, blobs, n, s);
+    return cc_impl(nullptr, cells_out, proofs_out, nullptr, status, blobs, n, s);
+}
+
+int kzg355_compute_commitments_cells_and_kzg_proofs_many(uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, int *status,
+                                                         const uint8_t *blobs, size_t n, const kzg355_settings *s) {
+    return cc_impl(commitments_out, cells_out, proofs_out, nullptr, status, blobs, n, s);
+}
+
+int kzg355_compute_commitments_cells_and_kzg_proofs_many_device(uint8_t *d_commitments_out, uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status,
+                                                                const uint8_t *d_blobs, size_t n, const kzg355_settings *s) {
+    return cc_impl(d_commitments_out, d_cells_out, d_proofs_out, nullptr, status, d_blobs, n, s, true);
 }
 
 int kzg355_compute_cells_and_kzg_proofs_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status, const uint8_t *d_blobs, size_t n,
                                                     const kzg355_settings *s) {
-    return cc_impl(d_cells_out, d_proofs_out, nullptr, status, d_blobs, n, s, true);
+    return cc_impl(nullptr, d_cells_out, d_proofs_out, nullptr, status, d_blobs, n, s, true);
 }
 
 int kzg355_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blob, const kzg355_settings *s) {
-    return cc_impl(cells_out, proofs_out, nullptr, nullptr, blob, 1, s);
+    return cc_impl(nullptr, cells_out, proofs_out, nullptr, nullptr, blob, 1, s);
 }
 
 int kzg355_debug_cell_compute_h(uint8_t *out, int *status, const uint8_t *blobs, size_t n, const kzg355_settings *s) {
     if (!out) return KZG355_BADARGS;
-    return cc_impl(nullptr, nullptr, out, status, blobs, n, s);
+    return cc_impl(nullptr, nullptr, nullptr, out, status, blobs, n, s);
 }
 
 int kzg355_debug_cell_setup_monomial_all(uint8_t *out, const kzg355_settings *cs) {

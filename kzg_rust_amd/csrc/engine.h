@@ -467,16 +467,18 @@ static const size_t CQ_CHUNK = 1152;       // (blob, cell) pairs per launch set 
 int build_monomial_points(kzg355_settings *s, Workspace *w, int count, uint8_t *d_mono48, G1Affine *d_mono);
 int ensure_cc_consts(kzg355_settings *s, Workspace *w);
 int cc_fan_out(const kzg355_settings *cs, size_t units, int *status, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
-int cc_run(const kzg355_settings *cs, size_t units, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
+int cc_run(const kzg355_settings *cs, size_t units, uint8_t *commitments_out, uint8_t *cells_out, uint8_t *proofs_out, uint8_t *h_dbg, int *status,
            const std::function<int(Workspace *, size_t CH)> &reserve,
-           const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells)> &stage, bool dev_out = false);
+           const std::function<int(Workspace *, Timed &, size_t c0, int m, uint8_t *d_cells, bool want_coef)> &stage, bool dev_out = false);
 // how every chunked cell call starts (cc_run and the chosen-cell calls): the refusal by size or preset, the workspace (g.w), the field-stage
 // constants, the caller's second setup (the FK20 proof setup or the MSM table; null: none is needed) and, when all that succeeded, the count of
 // the call among the handle's cell launch sets.  Not OK: the code the whole call is refused with.
 int cell_call_begin(const kzg355_settings *cs, size_t units, std::unique_ptr<WsGuard> &g, int (*second_setup)(kzg355_settings *, Workspace *));
 inline int wide_table_setup(kzg355_settings *s, Workspace *) { return ensure_wide_table(s); }   // (the first call that wants proofs builds the table)
 // the device forms take 16-byte aligned device pointers (null is aligned)
-inline bool misaligned(const void *a, const void *b, const void *c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0; }
+inline bool misaligned(const void *a, const void *b, const void *c, const void *d = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) != 0;
+}
 // cell_plan.h lays out the chunks of the recover and chosen-cell calls without HIP; its constants are the kernels'
 static_assert(PLAN_CELLS == (size_t)CELLS_PER_EXT_BLOB && PLAN_CELL_BYTES == (size_t)CELL_BYTES && PLAN_REFUSED == ERR_NONCANONICAL_FR, "cell_plan.h");
 // cell_recover.hip: the field stage of a recover chunk that rs has laid out (mc blobs; `cells` is the call's known cells, host or device memory;

@@ -8,7 +8,8 @@
 //   field stage  (k_cc_field)   canonical check, inverse NTT 4096 -> f, coset NTT 4096 of f_m w^m -> cells 64..127;
 //                (k_cc_columns) C_r = NTT128(c_r) for the 64 columns r;
 //   fixed-base   (k_cc_msm)     Z[i] = sum_r C_r[i] X_r[i], X_r = NTT128(x_r) built once per handle (k_cc_table: signed 4-bit comb table);
-//   G1 FFT       (k_cc_proofs)  conv = iNTT128(Z); h_e = conv[62-e] (e < 63), 0 above; pi = NTT128(h); compressed.
+//   G1 FFT       (k_cc_proofs)  conv = iNTT128(Z); h_e = conv[62-e] (e < 63), 0 above; pi = NTT128(h); compressed.  conv[63] = sum_r sum_d
+//                               c_r[d] x_r[63-d] = sum_m f_m [tau^m]_1 is the blob's commitment (no index wraps), written out when asked for.
 // Every transform of size 2^k is radix 2 in one of two orders: "dif" takes natural order and leaves the outputs bit-reversed, "dit" takes
 // bit-reversed order and leaves them natural.  Forward transforms are dif, inverse ones dit, so no permutation runs anywhere: the blob is
 // already in bit-reversed order, cells 64..127 are the coset evaluations in 12-bit bit-reversed order, Z is bit-reversed on both factors, and
@@ -213,8 +214,9 @@ __global__ void __launch_bounds__(64) k_cc_msm(const uint32_t *scal, const G1Aff
     if (r == 0) Z[bi] = red[0];
 }
 // workgroup blob: conv = dit_inv(Z); h_e = conv[62 - e] (e < 63), infinity above; pi = dif(h), compressed in cell order.  h_dbg (or null):
-// H_0 .. H_63 compressed (H_63 = infinity).
-__global__ void __launch_bounds__(64) k_cc_proofs(const G1Jac *Z, const CellComputeConsts *cc, uint8_t *proofs48, uint8_t *h_dbg) {
+// H_0 .. H_63 compressed (H_63 = infinity).  commit48 (or null): conv[63] = sum_m f_m [tau^m]_1, the blob's commitment, compressed; the lane
+// that holds no h takes it.  With neither proofs48 nor h_dbg the kernel ends there (the whole workgroup: no barrier follows a divergent return).
+__global__ void __launch_bounds__(64) k_cc_proofs(const G1Jac *Z, const CellComputeConsts *cc, uint8_t *proofs48, uint8_t *h_dbg, uint8_t *commit48) {
     __shared__ G1Jac a[CC_FFT];
     const int b = blockIdx.x, L = threadIdx.x;
     a[L] = Z[(size_t)b * CC_FFT + L];
@@ -222,6 +224,11 @@ __global__ void __launch_bounds__(64) k_cc_proofs(const G1Jac *Z, const CellComp
     __syncthreads();
     cc_g1_dit_inv(a, cc, L);
     const G1Jac h = L < CELL_FE - 1 ? a[CELL_FE - 2 - L] : g1_inf();
+    if (commit48 && L == CELL_FE - 1) {
+        G1Affine p; g1_to_affine(p, a[CELL_FE - 1]);
+        g1_compress_affine(commit48 + 48 * (size_t)b, p);
+    }
+    if (!proofs48 && !h_dbg) return;
     __syncthreads();
     a[L] = h;
     a[L + CC_FFT / 2] = g1_inf();
@@ -263,8 +270,8 @@ void launch_cc_columns(const Fr *d_coef, int n, const CellComputeConsts *d_cc, u
 void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *d_Z, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_cc_msm, dim3(n * CC_FFT), dim3(64), 0, st, d_scal, d_tab, d_Z);
 }
-void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st) {
-    if (n > 0) hipLaunchKernelGGL(k_cc_proofs, dim3(n), dim3(64), 0, st, d_Z, d_cc, d_proofs48, d_h_dbg);
+void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, uint8_t *d_commit48, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_cc_proofs, dim3(n), dim3(64), 0, st, d_Z, d_cc, d_proofs48, d_h_dbg, d_commit48);
 }
 
 }  // namespace kzg

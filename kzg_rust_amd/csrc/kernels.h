@@ -302,7 +302,8 @@ void launch_cc_setup_points(const G1Affine *d_mono, const CellComputeConsts *d_c
 void launch_cc_field(const uint8_t *d_blobs, int n, const CellComputeConsts *d_cc, Fr *d_coef, uint8_t *d_cells, int *d_err, hipStream_t st);
 void launch_cc_columns(const Fr *d_coef, int n, const CellComputeConsts *d_cc, uint32_t *d_scal, hipStream_t st);
 void launch_cc_msm(const uint32_t *d_scal, int n, const G1Affine *d_tab, G1Jac *d_Z, hipStream_t st);
-void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, hipStream_t st);
+// d_commit48 (or null): the blobs' commitments, conv[63] of the same chain, [n][48]; d_proofs48 may be null when d_h_dbg is too (commitments only)
+void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, uint8_t *d_proofs48, uint8_t *d_h_dbg, uint8_t *d_commit48, hipStream_t st);
 
 // ---- k_cell_quotient.hip: compute_cell_kzg_proofs_at, the proofs of chosen cells (mainnet handles only)
 // d_coef and d_err (per blob of the chunk) as launch_cc_field leaves them; d_scal: pairs * 4096 Fr, Montgomery, in blob order -- the d_scalars of

@@ -343,6 +343,14 @@ def _cell_results(rc, st, slots, c_out, p_out, call, label):
     return res
 
 
+def _commitment_cell_results(rc, st, units, k_out, c_out, p_out, call, label):
+    """_cell_results of a call that also returns a commitment per unit: (commitment, cells, proofs) or Error(label) per unit, None for a part
+    that was not asked for"""
+    res = _cell_results(rc, st, [CELLS_PER_EXT_BLOB] * units, c_out, p_out, call, label)
+    kraw = None if k_out is None else k_out.raw
+    return [r if isinstance(r, Error) else ((KzgCommitment(kraw[48 * i:48 * i + 48]) if kraw is not None else None,) + r) for i, r in enumerate(res)]
+
+
 def _device_results(rc, st, units, call, label):
     """What a device form returns: per unit None or Error(label); a failure of the whole call raises."""
     if _whole_call_failed(rc, st, units):
@@ -692,6 +700,78 @@ class Kzg:
         """The cells alone, per unit a list of 128 cells or Error (no proof is computed and no proof setup built)."""
         return [r if isinstance(r, Error) else r[0] for r in Kzg._recover_sets(units, s, True, False)]
 
+    # ---- the compute and recover calls with the blobs' commitments: slot 63 of the FK20 convolution whose other slots give the proofs ----
+    @staticmethod
+    def _commitment_buffer(commitments, cells, proofs, units):
+        if not (commitments or cells or proofs):
+            raise BadArgs("no output is asked for")
+        return C.create_string_buffer(48 * max(units, 1)) if commitments else None
+
+    @staticmethod
+    def _compute_commitments_cells(blobs, s, commitments, cells, proofs):
+        bl = [_b(x, Blob) for x in blobs]
+        n = len(bl)
+        k_out = Kzg._commitment_buffer(commitments, cells, proofs, n)
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * n, n)
+        rc = lib().kzg355_compute_commitments_cells_and_kzg_proofs_many(k_out, c_out, p_out, st, b"".join(bl), n, s.handle)
+        return _commitment_cell_results(rc, st, n, k_out, c_out, p_out, "compute_commitment_cells_and_kzg_proofs", "compute_cells")
+
+    @staticmethod
+    def compute_commitment_cells_and_kzg_proofs(blob, s):
+        """(KzgCommitment, [Cell] * 128, [KzgProof] * 128): compute_cells_and_kzg_proofs and blob_to_kzg_commitment in one call (the chain
+        computes the commitment on its way to the proofs; no wide MSM table is built)."""
+        return Kzg._one(Kzg._compute_commitments_cells([blob], s, True, True, True))
+
+    @staticmethod
+    def compute_commitment_cells_and_kzg_proofs_many(blobs, s):
+        """One independent compute_commitment_cells_and_kzg_proofs per blob in one call: a list of (commitment, cells, proofs) tuples or Error."""
+        return Kzg._compute_commitments_cells(blobs, s, True, True, True)
+
+    @staticmethod
+    def _recover_commitments(cell_indices, rows, s, commitments, cells, proofs):
+        ix = [int(i) for i in cell_indices]
+        rw = [[_b(x, Cell) for x in row] for row in rows]
+        n, m = len(ix), len(rw)
+        if any(len(row) != n for row in rw):
+            raise BadArgs("length mismatch")
+        _, idx = _size_t_arrays(None, ix, "cell index out of range")
+        k_out = Kzg._commitment_buffer(commitments, cells, proofs, m)
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * m, m)
+        rc = lib().kzg355_recover_commitments_cells_and_kzg_proofs_many(k_out, c_out, p_out, st, idx, b"".join(b"".join(row) for row in rw), n, m, s.handle)
+        return _commitment_cell_results(rc, st, m, k_out, c_out, p_out, "recover_commitment_cells_and_kzg_proofs", "recover_cells")
+
+    @staticmethod
+    def recover_commitment_cells_and_kzg_proofs(cell_indices, cells, s):
+        """(KzgCommitment, [Cell] * 128, [KzgProof] * 128) of the blob from 64..128 of its cells: recover_cells_and_kzg_proofs with the
+        commitment of the recovered blob, to compare with the block's blob_kzg_commitments (more than 64 cells that lie on no polynomial of
+        degree < 4096 are no error; the commitment is then that of the coefficients the algorithm keeps, and differs)."""
+        if len(cell_indices) != len(cells):
+            raise BadArgs("length mismatch")
+        return Kzg._one(Kzg._recover_commitments(cell_indices, [cells], s, True, True, True))
+
+    @staticmethod
+    def recover_commitment_cells_and_kzg_proofs_many(cell_indices, rows, s):
+        """recover_cells_and_kzg_proofs_many with the commitments: a list of (commitment, cells, proofs) tuples or Error."""
+        return Kzg._recover_commitments(cell_indices, rows, s, True, True, True)
+
+    @staticmethod
+    def _recover_commitments_sets(units, s, commitments, cells, proofs):
+        us = [([int(i) for i in ix], [_b(x, Cell) for x in row]) for ix, row in units]
+        m = len(us)
+        if any(len(ix) != len(row) for ix, row in us):
+            raise BadArgs("length mismatch")
+        counts, idx = _size_t_arrays([len(ix) for ix, _ in us], [i for ix, _ in us for i in ix], "cell index out of range")
+        k_out = Kzg._commitment_buffer(commitments, cells, proofs, m)
+        c_out, p_out, st = _cell_buffers(cells, proofs, CELLS_PER_EXT_BLOB * m, m)
+        rc = lib().kzg355_recover_commitments_cells_and_kzg_proofs_many_sets(k_out, c_out, p_out, st, counts, idx,
+                                                                             b"".join(b"".join(row) for _, row in us), m, s.handle)
+        return _commitment_cell_results(rc, st, m, k_out, c_out, p_out, "recover_commitment_cells_and_kzg_proofs_many_sets", "recover_cells")
+
+    @staticmethod
+    def recover_commitment_cells_and_kzg_proofs_many_sets(units, s):
+        """recover_cells_and_kzg_proofs_many_sets with the commitments: per unit (commitment, cells, proofs) or Error."""
+        return Kzg._recover_commitments_sets(units, s, True, True, True)
+
     # ---- proofs of chosen EIP-7594 cells of a blob (compute_cell_kzg_proofs_at): every (blob, cell) pair through its own quotient and one MSM ----
     @staticmethod
     def _cells_at(blobs, index_lists, s, cells, proofs):
@@ -926,6 +1006,55 @@ class Kzg:
         st = (C.c_int * max(m, 1))()
         rc = lib().kzg355_recover_cells_and_kzg_proofs_many_sets_device(c_out, p_out, st, counts, idx, d_cells, m, s.handle)
         return _device_results(rc, st, m, "recover_cells_and_kzg_proofs_many_sets_device", "recover_cells")
+
+    @staticmethod
+    def _commitment_cell_outputs(commitments_out, cells_out, proofs_out, units):
+        if commitments_out is None and cells_out is None and proofs_out is None:
+            raise BadArgs("commitments_out, cells_out and proofs_out are all missing")
+        return (Kzg._dev(commitments_out, "commitments_out", 48 * units, optional=True),
+                Kzg._dev(cells_out, "cells_out", BYTES_PER_CELL * CELLS_PER_EXT_BLOB * units, optional=True),
+                Kzg._dev(proofs_out, "proofs_out", 48 * CELLS_PER_EXT_BLOB * units, optional=True))
+
+    @staticmethod
+    def compute_commitment_cells_and_kzg_proofs_many_device(blobs, n, s, commitments_out=None, cells_out=None, proofs_out=None):
+        """compute_cells_and_kzg_proofs_many_device with the blobs' commitments written into the device tensor commitments_out (n * 48 bytes) as
+        well; any of the three outputs may be None, not all.  Returns one entry per blob: None, or the Error of that blob."""
+        n = int(n)
+        if n < 0:
+            raise BadArgs("n out of range")
+        k_out, c_out, p_out = Kzg._commitment_cell_outputs(commitments_out, cells_out, proofs_out, n)
+        d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_compute_commitments_cells_and_kzg_proofs_many_device(k_out, c_out, p_out, st, d_blobs, n, s.handle)
+        return _device_results(rc, st, n, "compute_commitment_cells_and_kzg_proofs_many_device", "compute_cells")
+
+    @staticmethod
+    def recover_commitment_cells_and_kzg_proofs_many_device(cell_indices, cells, m, s, commitments_out=None, cells_out=None, proofs_out=None):
+        """recover_cells_and_kzg_proofs_many_device with the commitments of the recovered blobs in commitments_out (m * 48 bytes) as well."""
+        cell_indices = list(cell_indices)
+        n, m = len(cell_indices), int(m)
+        if m < 0:
+            raise BadArgs("m or a cell index out of range")
+        _, idx = _size_t_arrays(None, cell_indices, "m or a cell index out of range")
+        k_out, c_out, p_out = Kzg._commitment_cell_outputs(commitments_out, cells_out, proofs_out, m)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * n * m, optional=m == 0)
+        st = (C.c_int * max(m, 1))()
+        rc = lib().kzg355_recover_commitments_cells_and_kzg_proofs_many_device(k_out, c_out, p_out, st, idx, d_cells, n, m, s.handle)
+        return _device_results(rc, st, m, "recover_commitment_cells_and_kzg_proofs_many_device", "recover_cells")
+
+    @staticmethod
+    def recover_commitment_cells_and_kzg_proofs_many_sets_device(cell_counts, cell_indices, cells, s, commitments_out=None, cells_out=None,
+                                                                 proofs_out=None):
+        """recover_cells_and_kzg_proofs_many_sets_device with the commitments of the recovered blobs in commitments_out (48 bytes per blob) as
+        well."""
+        cell_counts, cell_indices = list(cell_counts), list(cell_indices)
+        counts, idx = _size_t_arrays(cell_counts, cell_indices, "a count or a cell index out of range, or the counts do not add up to the indices")
+        m = len(cell_counts)
+        k_out, c_out, p_out = Kzg._commitment_cell_outputs(commitments_out, cells_out, proofs_out, m)
+        d_cells = Kzg._dev(cells, "cells", BYTES_PER_CELL * len(cell_indices), optional=m == 0)
+        st = (C.c_int * max(m, 1))()
+        rc = lib().kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device(k_out, c_out, p_out, st, counts, idx, d_cells, m, s.handle)
+        return _device_results(rc, st, m, "recover_commitment_cells_and_kzg_proofs_many_sets_device", "recover_cells")
 
     @staticmethod
     def compute_cell_kzg_proofs_at_many_device(blobs, n, cell_counts, cell_indices, s, cells_out=None, proofs_out=None):

@@ -138,6 +138,26 @@ extern "C" {
     pub fn kzg355_recover_cells_and_kzg_proofs_many_sets_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int, cell_counts: *const usize,
                                                                 cell_indices: *const usize, d_cells: *const u8, m: usize,
                                                                 s: *const kzg355_settings) -> c_int;
+    // the compute and recover calls with the blobs' commitments (48 bytes per blob, slot 63 of the FK20 convolution) as one more output in front:
+    // any of the three outputs may be null, not all; with commitments_out null they are the calls they are named after
+    pub fn kzg355_compute_commitments_cells_and_kzg_proofs_many(commitments_out: *mut u8, cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int,
+                                                                blobs: *const u8, n: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_compute_commitments_cells_and_kzg_proofs_many_device(d_commitments_out: *mut u8, d_cells_out: *mut u8, d_proofs_out: *mut u8,
+                                                                       status: *mut c_int, d_blobs: *const u8, n: usize,
+                                                                       s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_commitments_cells_and_kzg_proofs_many(commitments_out: *mut u8, cells_out: *mut u8, proofs_out: *mut u8, status: *mut c_int,
+                                                                cell_indices: *const usize, cells: *const u8, n: usize, m: usize,
+                                                                s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_commitments_cells_and_kzg_proofs_many_device(d_commitments_out: *mut u8, d_cells_out: *mut u8, d_proofs_out: *mut u8,
+                                                                       status: *mut c_int, cell_indices: *const usize, d_cells: *const u8, n: usize,
+                                                                       m: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_commitments_cells_and_kzg_proofs_many_sets(commitments_out: *mut u8, cells_out: *mut u8, proofs_out: *mut u8,
+                                                                     status: *mut c_int, cell_counts: *const usize, cell_indices: *const usize,
+                                                                     cells: *const u8, m: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device(d_commitments_out: *mut u8, d_cells_out: *mut u8, d_proofs_out: *mut u8,
+                                                                            status: *mut c_int, cell_counts: *const usize,
+                                                                            cell_indices: *const usize, d_cells: *const u8, m: usize,
+                                                                            s: *const kzg355_settings) -> c_int;
     pub fn kzg355_debug_cell_batch_intermediates_device(out: *mut u8, ok: *mut bool, status: *mut c_int, d_commitments: *const u8,
                                                         d_cell_indices: *const usize, d_cells: *const u8, d_proofs: *const u8, n_per_group: usize,
                                                         groups: usize, prep_form: c_int, s: *const kzg355_settings) -> c_int;

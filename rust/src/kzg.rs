@@ -680,6 +680,86 @@ impl Kzg {
             .collect())
     }
 
+    /// `compute_cells_and_kzg_proofs` with the blob's commitment as well: the FK20 chain computes it on its way to the proofs (slot 63 of the
+    /// convolution whose other slots give the proofs), so no second call and no wide MSM table is needed.
+    pub fn compute_commitment_cells_and_kzg_proofs(blob: &Blob, s: &KzgSettings) -> Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error> {
+        let mut res = Self::compute_commitment_cells_and_kzg_proofs_many(std::slice::from_ref(blob), s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// `blobs.len()` independent calls of the above in one set of launches; one `Result` per blob.
+    pub fn compute_commitment_cells_and_kzg_proofs_many(
+        blobs: &[Blob],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let n = blobs.len();
+        let staged = stage_blobs(blobs);
+        let mut out = CommitCellsProofs::new(n);
+        let rc = unsafe {
+            ffi::kzg355_compute_commitments_cells_and_kzg_proofs_many(out.commitments.as_mut_ptr(), out.cells.as_mut_ptr(), out.proofs.as_mut_ptr(),
+                                                                      out.st.as_mut_ptr(), staged.as_ptr(), n, s.raw)
+        };
+        whole_call(rc, &out.st[..n], "compute_commitment_cells_and_kzg_proofs_many")?;
+        Ok(out.unpack(n, "compute_cells"))
+    }
+
+    /// `recover_cells_and_kzg_proofs` with the commitment of the recovered blob as well, for the comparison with the block's
+    /// `blob_kzg_commitments`: more than 64 cells that lie on no polynomial of degree < 4096 are no error, and that comparison shows them up.
+    pub fn recover_commitment_cells_and_kzg_proofs(
+        cell_indices: &[usize],
+        cells: &[Cell],
+        s: &KzgSettings,
+    ) -> Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error> {
+        if cell_indices.len() != cells.len() {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let mut res = Self::recover_commitment_cells_and_kzg_proofs_many(cell_indices, cells, 1, s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// `m` blobs known at the same `cell_indices`, as `recover_cells_and_kzg_proofs_many`, with their commitments.
+    pub fn recover_commitment_cells_and_kzg_proofs_many(
+        cell_indices: &[usize],
+        cells: &[Cell],
+        m: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let n = cell_indices.len();
+        if cells.len() != n * m {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let input: Vec<u8> = cells.iter().flat_map(|x| x.iter().copied()).collect();
+        let mut out = CommitCellsProofs::new(m);
+        let rc = unsafe {
+            ffi::kzg355_recover_commitments_cells_and_kzg_proofs_many(out.commitments.as_mut_ptr(), out.cells.as_mut_ptr(), out.proofs.as_mut_ptr(),
+                                                                      out.st.as_mut_ptr(), cell_indices.as_ptr(), input.as_ptr(), n, m, s.raw)
+        };
+        whole_call(rc, &out.st[..m], "recover_commitment_cells_and_kzg_proofs_many")?;
+        Ok(out.unpack(m, "recover_cells"))
+    }
+
+    /// One unit `(cell_indices, cells)` per blob, as `recover_cells_and_kzg_proofs_many_sets`, with their commitments.
+    pub fn recover_commitment_cells_and_kzg_proofs_many_sets(
+        units: &[(&[usize], &[Cell])],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error>>, Error> {
+        let m = units.len();
+        if units.iter().any(|(ix, cells)| ix.len() != cells.len()) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let counts: Vec<usize> = units.iter().map(|(ix, _)| ix.len()).collect();
+        let indices: Vec<usize> = units.iter().flat_map(|(ix, _)| ix.iter().copied()).collect();
+        let input: Vec<u8> = units.iter().flat_map(|(_, cells)| cells.iter().flat_map(|x| x.iter().copied())).collect();
+        let mut out = CommitCellsProofs::new(m);
+        let rc = unsafe {
+            ffi::kzg355_recover_commitments_cells_and_kzg_proofs_many_sets(out.commitments.as_mut_ptr(), out.cells.as_mut_ptr(),
+                                                                           out.proofs.as_mut_ptr(), out.st.as_mut_ptr(), counts.as_ptr(),
+                                                                           indices.as_ptr(), input.as_ptr(), m, s.raw)
+        };
+        whole_call(rc, &out.st[..m], "recover_commitment_cells_and_kzg_proofs_many_sets")?;
+        Ok(out.unpack(m, "recover_cells"))
+    }
+
     /// The cells of the blob at `cell_indices` (each < 128, any order, repeats allowed) and their proofs: entry `j` is what
     /// `compute_cells_and_kzg_proofs` returns at index `cell_indices[j]`, at the price of one MSM per index instead of the FK20 chain.
     pub fn compute_cell_kzg_proofs_at(blob: &Blob, cell_indices: &[usize], s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
@@ -909,6 +989,71 @@ impl Kzg {
         Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
     }
 
+    /// `compute_cells_and_kzg_proofs_many_device` with the commitments (48 bytes per blob) written to `d_commitments_out` as well; any of the
+    /// three outputs may be null, not all.
+    ///
+    /// # Safety
+    /// As `compute_cells_and_kzg_proofs_many_device`; `d_commitments_out` holds `n * 48` bytes on the handle's device, 16-byte aligned.
+    pub unsafe fn compute_commitment_cells_and_kzg_proofs_many_device(
+        d_commitments_out: *mut u8,
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        d_blobs: *const u8,
+        n: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let mut st = vec![0i32; n.max(1)];
+        let rc = ffi::kzg355_compute_commitments_cells_and_kzg_proofs_many_device(d_commitments_out, d_cells_out, d_proofs_out, st.as_mut_ptr(),
+                                                                                  d_blobs, n, s.raw);
+        whole_call(rc, &st[..n], "compute_commitment_cells_and_kzg_proofs_many_device")?;
+        Ok((0..n).map(|i| check(st[i], "compute_cells")).collect())
+    }
+
+    /// `recover_cells_and_kzg_proofs_many_device` with the commitments of the recovered blobs written to `d_commitments_out` as well.
+    ///
+    /// # Safety
+    /// As `recover_cells_and_kzg_proofs_many_device`; `d_commitments_out` holds `m * 48` bytes on the handle's device, 16-byte aligned.
+    pub unsafe fn recover_commitment_cells_and_kzg_proofs_many_device(
+        d_commitments_out: *mut u8,
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        cell_indices: &[usize],
+        d_cells: *const u8,
+        m: usize,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let mut st = vec![0i32; m.max(1)];
+        let rc = ffi::kzg355_recover_commitments_cells_and_kzg_proofs_many_device(d_commitments_out, d_cells_out, d_proofs_out, st.as_mut_ptr(),
+                                                                                  cell_indices.as_ptr(), d_cells, cell_indices.len(), m, s.raw);
+        whole_call(rc, &st[..m], "recover_commitment_cells_and_kzg_proofs_many_device")?;
+        Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
+    }
+
+    /// `recover_cells_and_kzg_proofs_many_sets_device` with the commitments of the recovered blobs written to `d_commitments_out` as well.
+    ///
+    /// # Safety
+    /// As `recover_cells_and_kzg_proofs_many_sets_device`; `d_commitments_out` holds `cell_counts.len() * 48` bytes, 16-byte aligned.
+    pub unsafe fn recover_commitment_cells_and_kzg_proofs_many_sets_device(
+        d_commitments_out: *mut u8,
+        d_cells_out: *mut u8,
+        d_proofs_out: *mut u8,
+        cell_counts: &[usize],
+        cell_indices: &[usize],
+        d_cells: *const u8,
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(), Error>>, Error> {
+        let m = cell_counts.len();
+        if cell_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c)) != Some(cell_indices.len()) {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let mut st = vec![0i32; m.max(1)];
+        let rc = ffi::kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device(d_commitments_out, d_cells_out, d_proofs_out,
+                                                                                       st.as_mut_ptr(), cell_counts.as_ptr(), cell_indices.as_ptr(),
+                                                                                       d_cells, m, s.raw);
+        whole_call(rc, &st[..m], "recover_commitment_cells_and_kzg_proofs_many_sets_device")?;
+        Ok((0..m).map(|i| check(st[i], "recover_cells")).collect())
+    }
+
     /// `commitments.len()` independent `verify_kzg_proof` checks (one proof per call is what benches/kzg_benches.rs:70-81 times).
     pub fn verify_kzg_proof_many(
         commitments: &[KzgCommitment],
@@ -981,6 +1126,43 @@ fn stage_blobs(blobs: &[Blob]) -> Vec<u8> {
         staged.extend_from_slice(&b[..]);
     }
     staged
+}
+
+/// The host output buffers of a `*_commitment_cells_and_kzg_proofs_many*` call of `n` blobs, and their way into one `Result` per blob.
+struct CommitCellsProofs {
+    commitments: Vec<u8>,
+    cells: Vec<u8>,
+    proofs: Vec<u8>,
+    st: Vec<i32>,
+}
+
+impl CommitCellsProofs {
+    fn new(n: usize) -> Self {
+        CommitCellsProofs {
+            commitments: vec![0u8; BYTES_PER_COMMITMENT * n.max(1)],
+            cells: vec![0u8; BYTES_PER_CELL * CELLS_PER_EXT_BLOB * n.max(1)],
+            proofs: vec![0u8; BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * n.max(1)],
+            st: vec![0i32; n.max(1)],
+        }
+    }
+
+    fn unpack(&self, n: usize, what: &str) -> Vec<Result<(KzgCommitment, Vec<Cell>, Vec<KzgProof>), Error>> {
+        let per_cells = BYTES_PER_CELL * CELLS_PER_EXT_BLOB;
+        (0..n)
+            .map(|i| {
+                check(self.st[i], what)?;
+                let c = KzgCommitment::from(<[u8; BYTES_PER_COMMITMENT]>::try_from(&self.commitments[48 * i..48 * i + 48]).unwrap());
+                let cs = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| Cell::from_bytes(&self.cells[per_cells * i + BYTES_PER_CELL * k..per_cells * i + BYTES_PER_CELL * (k + 1)]))
+                    .collect::<Result<Vec<_>, _>>()?;
+                let base = BYTES_PER_PROOF * CELLS_PER_EXT_BLOB * i;
+                let ps = (0..CELLS_PER_EXT_BLOB)
+                    .map(|k| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&self.proofs[base + 48 * k..base + 48 * (k + 1)]).unwrap()))
+                    .collect();
+                Ok((c, cs, ps))
+            })
+            .collect()
+    }
 }
 
 /// A `*_many` call that failed as a whole (device, allocation or library failure -- or a non-zero return with no unit carrying a
