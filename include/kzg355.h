@@ -221,6 +221,41 @@ int kzg355_verify_kzg_proof_many_device(bool *ok /* host n */, int *status /* ho
 int kzg355_compute_kzg_proof_many_device(uint8_t *proofs_out /* host n*48 */, uint8_t *ys_out /* host n*32 */, int *status, const uint8_t *d_blobs,
                                          const uint8_t *d_zs /* n*32 */, size_t n, const kzg355_settings *s);
 
+/* ---- verify_blob_kzg_proof_batch on batches of different blob counts in one call ---------------- */
+/* A block brings 0..9 blobs, a blob transaction 1..6: `groups` batches, batch g being the next blob_counts[g] blobs / commitments / proofs of
+ * the three arrays, which hold the batches one after the other with no padding.  Per batch EXACTLY what kzg355_verify_blob_kzg_proof_batch
+ * returns on that slice: its own transcript (with its own n), challenge r, pairing, verdict and status; a count of 1 takes r^0 = 1 with no
+ * hash; a count of 0 is true / KZG355_OK (kzg.rs:653-655).  A blob element >= r, or a commitment or proof that fails validate_kzg_g1, is that
+ * batch's KZG355_BADARGS with ok[g] = false; the other batches are untouched.  Returns the first non-OK status in batch order.
+ * REFUSED AS A WHOLE, from the counts alone, before any array is read or any device touched, every status marked and every verdict false: a
+ * NULL handle, ok or (groups > 0) blob_counts; a NULL array while the sum of the counts is > 0; groups or the sum above 2^24 (or a sum that
+ * overflows); for the device form d_blobs not 16-byte aligned or a point array not 4-byte aligned.  groups == 0: KZG355_OK, nothing touched.
+ * Work and device memory follow the SUM of the counts.  The non-empty batches run in launch sets of whole batches, taken in order while a set
+ * stays within 32768 blobs (kzg355_settings_set_blob_sets_max_blobs, below, sets another limit); a batch
+ * is never cut, and a batch larger than the limit is a set of its own.  The host form stages the blobs set by set (a set of at most
+ * chunk_mb of blobs, chunks_in_flight sets on the device at a time).  A handle over D devices (host form): contiguous ranges of batches,
+ * balanced by BLOBS -- range d ends at the batch border nearest to d N / D on the prefix sums of the counts (N their sum; the lower border of
+ * two equally near); kzg355_settings_blob_sets_blobs_per_device tells how many blobs each device has run.  The device form expects its arrays
+ * on the handle's first device and runs there.  The minimal preset is served too. */
+int kzg355_verify_blob_kzg_proof_batch_many_sets(bool *ok /* groups */, int *status /* groups or NULL */, const size_t *blob_counts /* groups */,
+                                                 const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs /* sum of the counts, batch after batch */,
+                                                 size_t groups, const kzg355_settings *s);
+int kzg355_verify_blob_kzg_proof_batch_many_sets_device(bool *ok /* host */, int *status /* host or NULL */, const size_t *blob_counts /* HOST */,
+                                                        const uint8_t *d_blobs, const uint8_t *d_commitments, const uint8_t *d_proofs, size_t groups,
+                                                        const kzg355_settings *s);
+/* test / audit forms: out[128 g ..] = r | proof_lincomb | rhs as kzg355_debug_batch_intermediates lays them out (r reads 1 for a count of 1);
+ * zero bytes for a count of 0.  A NULL out refuses the call. */
+int kzg355_debug_batch_intermediates_sets(uint8_t *out /* groups*128 */, bool *ok, int *status, const size_t *blob_counts, const uint8_t *blobs,
+                                          const uint8_t *commitments, const uint8_t *proofs, size_t groups, const kzg355_settings *s);
+int kzg355_debug_batch_intermediates_sets_device(uint8_t *out /* host, groups*128 */, bool *ok, int *status, const size_t *blob_counts,
+                                                 const uint8_t *d_blobs, const uint8_t *d_commitments, const uint8_t *d_proofs, size_t groups,
+                                                 const kzg355_settings *s);
+/* Tuning knob and test hook: the blobs per launch set of the four calls above, on the handle and every replica of it; 1 .. 2^24, 0 = the default
+ * 32768, anything else KZG355_BADARGS.  Call it while no such call is running on the handle. */
+int kzg355_settings_set_blob_sets_max_blobs(kzg355_settings *s, size_t max_blobs);
+/* introspection for tests: returns the device count and fills out[d] (up to cap) with the blobs device d has run through the four calls above */
+int kzg355_settings_blob_sets_blobs_per_device(const kzg355_settings *s, long *out /* cap */, size_t cap);
+
 /* ---- sharded verification (one process per GPU; the exchange between the two stages is the caller's
  *      exchange of the 160-byte records, e.g. torch.distributed over RCCL) --------------------------- */
 /* Stage 1, per rank, over its contiguous shard of every batch: `groups` batches, n_local blobs of each (group-major:

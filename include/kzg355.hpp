@@ -274,6 +274,36 @@ struct Kzg {
         return out;
     }
 
+    // verify_blob_kzg_proof_batch on batches of different blob counts in one call: one independent check per group, each with its own challenge r
+    // (an empty group is true); a group whose three lengths differ is BadArgs before the library is called (kzg.rs:644-651)
+    struct ProofGroup {
+        std::vector<Blob> blobs;
+        std::vector<KzgCommitment> commitments;
+        std::vector<KzgProof> proofs;
+    };
+    static Result<std::vector<Result<bool>>> verify_blob_kzg_proof_batch_many_sets(const std::vector<ProofGroup> &groups, const KzgSettings &s) {
+        std::vector<size_t> counts;
+        std::vector<uint8_t> b, c, p;
+        for (const ProofGroup &g : groups) {
+            const size_t n = g.blobs.size();
+            if (g.commitments.size() != n || g.proofs.size() != n) return Error{Error::BadArgs, "length mismatch"};
+            counts.push_back(n);
+            for (size_t i = 0; i < n; i++) {
+                b.insert(b.end(), g.blobs[i].data(), g.blobs[i].data() + BYTES_PER_BLOB);
+                c.insert(c.end(), g.commitments[i].data(), g.commitments[i].data() + 48);
+                p.insert(p.end(), g.proofs[i].data(), g.proofs[i].data() + 48);
+            }
+        }
+        b.push_back(0); c.push_back(0); p.push_back(0);            // (data() of an empty vector may be null)
+        return blob_sets_call(counts, b.data(), c.data(), p.data(), s, false);
+    }
+    // the same on device memory (the handle's first device): the three arrays batch after batch with no padding, blob_counts on the host
+    static Result<std::vector<Result<bool>>> verify_blob_kzg_proof_batch_many_sets_device(const uint8_t *d_blobs, const uint8_t *d_commitments,
+                                                                                         const uint8_t *d_proofs, const std::vector<size_t> &blob_counts,
+                                                                                         const KzgSettings &s) {
+        return blob_sets_call(blob_counts, d_blobs, d_commitments, d_proofs, s, true);
+    }
+
     // EIP-7594 compute_cells_and_kzg_proofs: the 128 cells of the blob's 2x extension and their 128 proofs, in cell order
     static Result<std::pair<std::vector<Cell>, std::vector<KzgProof>>> compute_cells_and_kzg_proofs(const Blob &blob, const KzgSettings &s) {
         std::vector<uint8_t> c((size_t)KZG355_CELLS_PER_EXT_BLOB * KZG355_BYTES_PER_CELL), p((size_t)KZG355_CELLS_PER_EXT_BLOB * 48);
@@ -669,6 +699,24 @@ struct Kzg {
         if (rc == KZG355_OK) return false;
         for (int x : st) if (x) return false;
         return true;
+    }
+    // what the two verify_blob_kzg_proof_batch_many_sets forms share: the call and its per-group results
+    static Result<std::vector<Result<bool>>> blob_sets_call(const std::vector<size_t> &blob_counts, const uint8_t *blobs, const uint8_t *commitments,
+                                                           const uint8_t *proofs, const KzgSettings &s, bool device) {
+        const size_t G = blob_counts.size();
+        std::vector<size_t> counts(blob_counts);
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        std::unique_ptr<bool[]> ok(new bool[G + 1]());
+        std::vector<int> st(G + 1, 0);
+        int rc = device ? kzg355_verify_blob_kzg_proof_batch_many_sets_device(ok.get(), st.data(), counts.data(), blobs, commitments, proofs, G, s.raw())
+                        : kzg355_verify_blob_kzg_proof_batch_many_sets(ok.get(), st.data(), counts.data(), blobs, commitments, proofs, G, s.raw());
+        st.resize(G);
+        if (whole_call_failed(rc, st)) return from_status(rc, "verify_blob_kzg_proof_batch_many_sets");
+        std::vector<Result<bool>> out;
+        for (size_t g = 0; g < G; g++) {
+            if (st[g]) out.push_back(from_status(st[g], "verify")); else out.push_back(bool(ok[g]));
+        }
+        return out;
     }
     static Result<std::vector<Result<bool>>> verify_kzg_proof_many(const std::vector<KzgCommitment> &cs, const std::vector<Bytes32> &zs,
                                                                    const std::vector<Bytes32> &ys, const std::vector<KzgProof> &ps, const KzgSettings &s) {

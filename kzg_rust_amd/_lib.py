@@ -133,6 +133,12 @@ def load():
         "kzg355_verify_blob_cell_proofs_batch_many_sets_device": [bp, ip, szp, vp, vp, vp, sz, vp],
         "kzg355_debug_blob_cell_batch_intermediates_sets": [u8p, bp, ip, szp, u8p, u8p, u8p, sz, C.c_int, vp],
         "kzg355_debug_blob_cell_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, sz, C.c_int, C.c_int, vp],
+        "kzg355_verify_blob_kzg_proof_batch_many_sets": [bp, ip, szp, u8p, u8p, u8p, sz, vp],
+        "kzg355_verify_blob_kzg_proof_batch_many_sets_device": [bp, ip, szp, vp, vp, vp, sz, vp],
+        "kzg355_debug_batch_intermediates_sets": [u8p, bp, ip, szp, u8p, u8p, u8p, sz, vp],
+        "kzg355_debug_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, sz, vp],
+        "kzg355_settings_blob_sets_blobs_per_device": [vp, C.POINTER(C.c_long), sz],
+        "kzg355_settings_set_blob_sets_max_blobs": [vp, sz],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -194,4 +200,7 @@ EXPORTED_SYMBOLS = [
     "kzg355_compute_commitments_cells_and_kzg_proofs_many", "kzg355_compute_commitments_cells_and_kzg_proofs_many_device",
     "kzg355_recover_commitments_cells_and_kzg_proofs_many", "kzg355_recover_commitments_cells_and_kzg_proofs_many_device",
     "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets", "kzg355_recover_commitments_cells_and_kzg_proofs_many_sets_device",
+    "kzg355_verify_blob_kzg_proof_batch_many_sets", "kzg355_verify_blob_kzg_proof_batch_many_sets_device",
+    "kzg355_debug_batch_intermediates_sets", "kzg355_debug_batch_intermediates_sets_device", "kzg355_settings_blob_sets_blobs_per_device",
+    "kzg355_settings_set_blob_sets_max_blobs",
 ]

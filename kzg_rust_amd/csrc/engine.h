@@ -2,6 +2,7 @@
 // functions the translation units of the host code share.  Round 5 cut the single 2,200-line api.hip into
 //   workspace.hip      workspace pool, side streams, dispatch helpers, the launch-set frame (declared below: begin / results back / wait / read)
 //   verify_stages.hip  stage 1 / stage 2 of verification, launch sets, the device-resident call
+//   verify_sets.hip    verify_blob_kzg_proof_batch on batches of different blob counts in one call (added later): the refusals, launch sets, device cuts
 //   msm_ops.hip        the fixed-base MSM table and the commitment / proof chains
 //   host_pipeline.hip  host buffers -> chunks -> workspaces (H2D / kernels / results overlapped), the dispatch of the *_many host-buffer calls
 //   options.hip        kzg355_options, loading a handle on one device, the load-time self-test, getters / setters
@@ -190,6 +191,10 @@ struct kzg355_settings {
     // side streams are per workspace (round 4; measured with 4 threads of n = 64 calls: median call 5.0-7.9 ms with one pair per handle, 3.6-5.2 ms own with 4
     // hardware queues, 2.5-3.9 ms with 8); the handle's shared pair is the fallback when a stream cannot be created
     bool force_sharded = false;      // test hook (kzg355_options.force_sharded): a multi-device handle shards every batch
+    // kzg355_verify_blob_kzg_proof_batch_many_sets (verify_sets.hip): blobs per launch set of whole batches (kzg355_settings_set_blob_sets_max_blobs),
+    // and the blobs this handle (a replica: this device) has run through that call (kzg355_settings_blob_sets_blobs_per_device)
+    size_t blob_sets_max_blobs = 32768;
+    std::atomic<long> n_blob_sets_blobs{0};
     std::atomic<int> calls_in_flight{0};   // host-buffer calls inside host_pipeline right now
     int hw_queues = 4;                     // GPU_MAX_HW_QUEUES as the process has it when the handle is loaded (the runtime's default is 4)
     // 0 by size; 1: every submitted set on its workspace's own stream; 2: two-stage software pipeline over pipe_main / pipe_tail (KZG355_SUBMIT=sets|pipeline)
@@ -437,6 +442,12 @@ int verify_enqueue_stage2(kzg355_settings *s, Workspace *w, Timed &tm, int npg, 
 int verify_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, int npg, int G,
                    size_t res_off = 0, size_t res_cap = 0, HostFront *hf = nullptr, bool lone_call = false);
 int verify_collect(Workspace *w, Timed &tm, bool *ok, int *status, int G, size_t res_off = 0);
+// The same pair for G non-empty batches of different sizes in one launch set (verify_sets.hip): boff (host, G + 1 entries) holds the blobs before
+// each batch, strictly increasing from 0; stage 1 runs with one blob per "batch", stage 2 on the `_sets` entries of its kernels.  dump: r |
+// proof_lincomb | rhs per batch come back too (collect's `dump`, 128 bytes per batch).
+int verify_sets_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, const size_t *boff, int G,
+                        HostFront *hf, bool lone_call, bool dump);
+int verify_sets_collect(Workspace *w, Timed &tm, bool *ok, int *status, uint8_t *dump, int G);
 bool device_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs);
 bool host_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs);
 HostFront *resident_front(kzg355_settings *s, HostFront &hf, const uint8_t *d_commitments, size_t n_blobs, InFlight *count = nullptr);
@@ -576,6 +587,8 @@ void free_single(kzg355_settings *s);
 std::vector<kzg355_settings *> replicas_of(kzg355_settings *s);
 int fan_out(const kzg355_settings *cs, size_t D, size_t units, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
 int fan_out_guards(const GuardList &gs, size_t tasks, const std::function<int(size_t)> &fn);
+// the same with the ranges given: replica d takes units cut[d] .. cut[d + 1] - 1 (cut: non-decreasing, at most one entry more than there are replicas)
+int fan_out_cuts(const kzg355_settings *cs, const std::vector<size_t> &cut, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn);
 int multi_verify_sharded(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,
                          const kzg355_settings *cs, uint8_t *dump = nullptr);
 int multi_verify_many(bool *ok, int *status, const uint8_t *blobs, const uint8_t *commitments, const uint8_t *proofs, size_t npg, size_t groups,

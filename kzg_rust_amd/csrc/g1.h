@@ -540,6 +540,9 @@ KZG_HD void w4_load(G1Jac &v, const uint32_t *tab, int e, int lane) {
     for (int i = 0; i < NFP; i++) { v.x.l[i] = tab[((e * 3 + 0) * NFP + i) * 64 + lane]; v.y.l[i] = tab[((e * 3 + 1) * NFP + i) * 64 + lane];
             v.z.l[i] = tab[((e * 3 + 2) * NFP + i) * 64 + lane]; }
 }
+// NO_INDEX: the digit's word is picked by comparisons instead of a run-time index into e4 (which puts e4 into scratch memory: the 48 bytes of
+// k_lincomb_terms); the form of kernels that must stay out of scratch.
+template <bool NO_INDEX = false>
 KZG_HD void g1_mul128_w4(G1Jac &r, const G1Affine &p, const uint32_t k[4], uint32_t *tab, int lane) {
     G1Jac t; g1_from_affine(t, p);
     w4_store(tab, 0, lane, t);
@@ -560,7 +563,9 @@ KZG_HD void g1_mul128_w4(G1Jac &r, const G1Affine &p, const uint32_t k[4], uint3
         g1_dbl_lazy(acc, acc);
         if ((step & 3) == 0) {
             const int nib = step >> 2;
-            const int d = (int)((e4[nib >> 3] >> (4 * (nib & 7))) & 15u) - 8;
+            const int wi = nib >> 3;                       // 0..3
+            const uint32_t word = NO_INDEX ? (wi == 0 ? e4[0] : wi == 1 ? e4[1] : wi == 2 ? e4[2] : e4[3]) : e4[wi];
+            const int d = (int)((word >> (4 * (nib & 7))) & 15u) - 8;
             const int mag = d < 0 ? -d : d;
             G1Jac q = g1_inf();
             if (mag) { w4_load(q, tab, mag - 1, lane); if (d < 0) fp_neg(q.y, q.y); }

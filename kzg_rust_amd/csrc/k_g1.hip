@@ -237,6 +237,65 @@ __global__ void __launch_bounds__(64) k_lincomb_finish(const G1Jac *partials, in
     pair_pts[2 * (size_t)g + c] = a;
 }
 
+// ------------------------------------------------------------------------------------------------ lincomb, batches of different sizes
+// kzg355_verify_blob_kzg_proof_batch_many_sets: batch g holds n_g = goff[g + 1] - goff[g] records (goff strictly increasing), its points the
+// pairs [C_i, proof_i] at 2 i, 2 i + 1 (stage 1 run with one blob per "batch"), its scalars as k_rpowers_sets leaves them.  The term map is the
+// one above; each GLV half is one item, items numbered batch after batch: batch g holds 2 (3 n_g + 1) of them from lincomb_sets_item0 on.  A wave
+// of 64 items straddles batch borders, so the per-class butterfly of k_lincomb_terms does not carry over:
+//   k_lincomb_terms_sets    one lane per item: finds its batch (binary search over the item offsets, at most 24 steps beside a 128-step
+//                           ladder), walks the ladder, writes the item's Jacobian result
+//   k_lincomb_finish_sets   one wave per batch: per class the lanes stride over the batch's items (class 0 is items [0, 2 n), class 1 the rest),
+//                           then the butterfly; lane c converts the sum of class c -> (-proof_lincomb, rhs)
+// Points at infinity (a point that failed validation, an idle lane) are carried by the complete addition.
+__device__ __forceinline__ size_t lincomb_sets_item0(const int *goff, int g) { return 2 * (3 * (size_t)goff[g] + g); }
+__global__ void __launch_bounds__(64) k_lincomb_terms_sets(const G1Affine *pts, const uint32_t *scal_a, const uint32_t *scal_b, const uint32_t *scal_c,
+                                                            const int *goff, int groups, G1Jac *items, uint32_t *wtabs) {
+    const int lane = threadIdx.x;
+    uint32_t *wtab = wtabs + (size_t)blockIdx.x * (W4_ENTRIES * 3 * NFP * 64);
+    const size_t item = (size_t)blockIdx.x * 64 + lane;
+    if (item >= lincomb_sets_item0(goff, groups)) return;         // (the ladder has no cross-lane step: idle lanes of the last wave leave)
+    int lo = 0, hi = groups - 1;                                  // the last batch whose items start at or before this one
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (lincomb_sets_item0(goff, mid) <= item) lo = mid; else hi = mid - 1;
+    }
+    const int g = lo, n = goff[g + 1] - goff[g], j = (int)(item - lincomb_sets_item0(goff, g)), t = j >> 1, half = j & 1;
+    const size_t b0 = (size_t)goff[g];
+    G1Affine p; uint32_t k[8];
+    if (t < n) { p = pts[2 * (b0 + t) + 1]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * (b0 + t) + q]; }
+    else if (t < 2 * n) { p = pts[2 * (b0 + t - n) + 1]; for (int q = 0; q < 8; q++) k[q] = scal_b[8 * (b0 + t - n) + q]; }
+    else if (t < 3 * n) { p = pts[2 * (b0 + t - 2 * n)]; for (int q = 0; q < 8; q++) k[q] = scal_a[8 * (b0 + t - 2 * n) + q]; }
+    else { p = g1a_neg_gen(); for (int q = 0; q < 8; q++) k[q] = scal_c[8 * (size_t)g + q]; }
+    uint32_t ka[4], kb[4];
+    glv_split(ka, kb, k);
+    if (half) { G1Affine q; g1a_neg_phi(q, p); p = q; }
+    uint32_t kh[4];                                               // (picked word by word: a pointer to one of the two arrays would park both in scratch)
+#pragma unroll
+    for (int q = 0; q < 4; q++) kh[q] = half ? kb[q] : ka[q];
+    G1Jac m;
+    g1_mul128_w4<true>(m, p, kh, wtab, lane);
+    items[item] = m;
+}
+__global__ void __launch_bounds__(64) k_lincomb_finish_sets(const G1Jac *items, const int *goff, int groups, PairPt *pair_pts) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int n = goff[g + 1] - goff[g];
+    const G1Jac *it = items + lincomb_sets_item0(goff, g);
+    G1Jac mine = g1_inf();
+#pragma unroll 1
+    for (int c = 0; c < 2; c++) {                                 // one loop, one inlined instance of the complete addition per use
+        const int j0 = c == 0 ? 0 : 2 * n, j1 = c == 0 ? 2 * n : 2 * (3 * n + 1);
+        G1Jac v = g1_inf();
+#pragma unroll 1
+        for (int j = j0 + lane; j < j1; j += 64) { const G1Jac o = it[j]; g1_add(v, v, o); }
+#pragma unroll 1
+        for (int off = 1; off < 64; off <<= 1) { G1Jac o = g1_shfl_xor(v, off); g1_add(v, v, o); }
+        if (lane == c) mine = v;
+    }
+    if (lane >= 2) return;
+    PairPt a; pairpt_from_jac(a, mine, lane == 0);               // pairings_verify negates its first G1 argument (utils.rs:198-201)
+    pair_pts[2 * (size_t)g + lane] = a;
+}
+
 // ------------------------------------------------------------------------------------------------ lincomb, one record per check
 // MANY independent single-proof checks (verify_kzg_proof kzg.rs:409-426, verify_blob_kzg_proof kzg.rs:547-569; the *_many entry points): with one
 // record per "batch" the equation has r^0 = 1, so proof_lincomb IS the proof and rhs = C + [z] proof + [y](-G) -- two scalar multiplications, GLV-
@@ -828,6 +887,42 @@ __global__ void __launch_bounds__(64) k_dump_intermediates(const uint32_t *scal_
 void launch_dump_intermediates(const uint32_t *d_scal_a, const PairPt *d_pair_pts, int n_per_group, int groups, uint8_t *d_out, hipStream_t st) {
     if (groups <= 0) return;
     hipLaunchKernelGGL(k_dump_intermediates, dim3((2 * groups + 63) / 64), dim3(64), 0, st, d_scal_a, d_pair_pts, n_per_group, groups, d_out);
+}
+// the same for batches of different sizes: batch g's r is a_1 of its own scalars, at 8 (goff[g] + 1); a batch of one record reads a_0 = 1
+__global__ void __launch_bounds__(64) k_dump_intermediates_sets(const uint32_t *scal_a, const PairPt *pair_pts, const int *goff, int groups, uint8_t *out) {
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    const int g = id >> 1, which = id & 1;
+    if (g >= groups) return;
+    uint8_t *o = out + 128 * (size_t)g;
+    G1Affine p; pairpt_to_affine(p, pair_pts[2 * (size_t)g + which]);
+    if (which == 0 && !g1a_is_inf(p)) fp_neg(p.y, p.y);
+    uint8_t b[48]; g1_compress_affine(b, p);
+    for (int k = 0; k < 48; k++) o[32 + 48 * which + k] = b[k];
+    if (which == 0) {
+        const uint32_t *r = scal_a + 8 * ((size_t)goff[g] + (goff[g + 1] - goff[g] > 1 ? 1 : 0));
+        for (int k = 0; k < 8; k++) { const uint32_t v = r[7 - k]; o[4 * k] = (uint8_t)(v >> 24); o[4 * k + 1] = (uint8_t)(v >> 16);
+                o[4 * k + 2] = (uint8_t)(v >> 8); o[4 * k + 3] = (uint8_t)v; }
+    }
+}
+void launch_dump_intermediates_sets(const uint32_t *d_scal_a, const PairPt *d_pair_pts, const int *d_goff, int groups, uint8_t *d_out, hipStream_t st) {
+    if (groups <= 0) return;
+    hipLaunchKernelGGL(k_dump_intermediates_sets, dim3((2 * groups + 63) / 64), dim3(64), 0, st, d_scal_a, d_pair_pts, d_goff, groups, d_out);
+}
+// items | per-wave window tables, in one scratch allocation
+size_t lincomb_sets_items(size_t n_total, size_t groups) { return 2 * (3 * n_total + groups); }
+size_t lincomb_sets_bytes(size_t n_total, size_t groups) {
+    const size_t items = lincomb_sets_items(n_total, groups), waves = (items + 63) / 64;
+    return sizeof(G1Jac) * items + sizeof(uint32_t) * W4_ENTRIES * 3 * NFP * 64 * waves;
+}
+void launch_lincomb_sets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, const int *d_goff, int n_total,
+                         int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st) {
+    if (groups <= 0) return;
+    const size_t items = lincomb_sets_items((size_t)n_total, (size_t)groups);
+    G1Jac *d_items = reinterpret_cast<G1Jac *>(d_scratch);
+    uint32_t *d_wtabs = reinterpret_cast<uint32_t *>(d_items + items);
+    hipLaunchKernelGGL(k_lincomb_terms_sets, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, st, d_pts, d_scal_a, d_scal_b, d_scal_c, d_goff, groups, d_items,
+            d_wtabs);
+    hipLaunchKernelGGL(k_lincomb_finish_sets, dim3(groups), dim3(64), 0, st, d_items, d_goff, groups, d_pair_pts);
 }
 void launch_decompress_points(const uint8_t *d_commitments, const uint8_t *d_proofs, int n_total, int n_per_group, G1Affine *d_pts, int *d_err, hipStream_t st,
         int stride) {

@@ -420,10 +420,35 @@ __global__ void __launch_bounds__(64 * EVAL_WAVES, 2) k_eval(const uint8_t *blob
 // wave.  The one-wave-per-batch form above keeps 63 lanes idle during the rounds: fine while every wave has a SIMD to itself,
 // 64x the issue slots once the batches outnumber the SIMDs.  Writes the digest words (as fr_from_words takes them) to
 // digests[g][8]; k_rpowers then starts from those.
-__global__ void __launch_bounds__(64) k_rhash_lanes(const uint8_t *records, int n, int groups, uint32_t *digests, int n_fe) {
+// Where the batches of a launch set lie (the two entries of k_rhash_lanes share one body through it, as the cell kernels do through group_geo.h;
+// k_rpowers_sets is a sibling of k_rpowers and reads the ragged form):
+//   BatchGeoUniform   every batch has n records: arithmetic on n, the expressions the kernels had before there was a second form
+//   BatchGeoSets      every batch has its own count (kzg355_verify_blob_kzg_proof_batch_many_sets): goff[groups + 1], the records before each
+//                     batch, STRICTLY increasing (the host drops empty batches)
+// Batch g reads records + 160 first(g) and writes its scalars to scal_a / scal_b at 8 (first(g) + i), to scal_c at 8 g.
+struct BatchGeoUniform {
+    static constexpr bool RAGGED = false;
+    int n;
+    __device__ __forceinline__ size_t first(int g) const { return (size_t)g * n; }
+    __device__ __forceinline__ size_t rec_off(int g) const { return (size_t)RECORD_BYTES * n * g; }
+    __device__ __forceinline__ int count(int) const { return n; }
+};
+struct BatchGeoSets {
+    static constexpr bool RAGGED = true;
+    const int *goff;
+    __device__ __forceinline__ size_t first(int g) const { return (size_t)goff[g]; }
+    __device__ __forceinline__ size_t rec_off(int g) const { return (size_t)RECORD_BYTES * goff[g]; }
+    __device__ __forceinline__ int count(int g) const { return goff[g + 1] - goff[g]; }
+};
+
+template <class GEO>
+__device__ __forceinline__ void rhash_lanes_body(const uint8_t *records, const GEO geo, int groups, uint32_t *digests, int n_fe) {
     const int g = blockIdx.x * 64 + threadIdx.x;
     if (g >= groups) return;
-    const uint8_t *rec = records + (size_t)RECORD_BYTES * n * g;
+    const int n = geo.count(g);
+    if (GEO::RAGGED && n <= 1) return;                            // a batch of one record takes r^0 = 1 and has no transcript (k_rpowers)
+    // RECORD_BYTES = 160 is a multiple of 16: the 16-byte loads below stay aligned whatever first(g) is
+    const uint8_t *rec = records + geo.rec_off(g);
     const uint32_t total_words = 8u + 40u * (uint32_t)n;
     const uint32_t nblocks = (total_words * 4u + 9u + 63u) / 64u;
     const uint64_t bits = (uint64_t)total_words * 32u;
@@ -471,6 +496,12 @@ __global__ void __launch_bounds__(64) k_rhash_lanes(const uint8_t *records, int 
     }
 #pragma unroll
     for (int k = 0; k < 8; k++) digests[8 * (size_t)g + k] = hs[7 - k];
+}
+__global__ void __launch_bounds__(64) k_rhash_lanes(const uint8_t *records, int n, int groups, uint32_t *digests, int n_fe) {
+    rhash_lanes_body(records, BatchGeoUniform{n}, groups, digests, n_fe);
+}
+__global__ void __launch_bounds__(64) k_rhash_lanes_sets(const uint8_t *records, const int *goff, int groups, uint32_t *digests, int n_fe) {
+    rhash_lanes_body(records, BatchGeoSets{goff}, groups, digests, n_fe);
 }
 
 // Four batches (waves) per workgroup, one per SIMD of the CU it lands on (one-wave workgroups of long chains are placed
@@ -586,6 +617,131 @@ __global__ void __launch_bounds__(256) k_rpowers(const uint8_t *records, int n, 
     }
     if (bad && live) atomicOr(&err[g], ERR_NONCANONICAL_FR);
 }
+// The same kernel for batches of their own sizes (BatchGeoSets).  A sibling and not a second entry of one body: behind a shared template body
+// the uniform kernel above came out of the compiler with 149 VGPRs instead of its 142 (k_rhash_lanes kept its 42, and shares).
+__global__ void __launch_bounds__(256) k_rpowers_sets(const uint8_t *records, const int *goff, int groups, int check_zy, uint32_t *scal_a,
+                                                       uint32_t *scal_b, uint32_t *scal_c, int *err, int n_fe, int have_digest) {
+    const BatchGeoSets geo{goff};
+    __shared__ uint32_t wk_all[4][64][64];           // per wave: [t][block of the chunk]
+    __shared__ uint32_t digest_all[4][8];
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g_raw = blockIdx.x * (int)(blockDim.x >> 6) + wid;
+    if (g_raw >= groups) return;                                  // (the waves only synchronise with themselves)
+    const int g = g_raw;
+    const bool live = true;
+    uint32_t (*wk)[64] = wk_all[wid];
+    uint32_t *digest = digest_all[wid];
+    const int n = geo.count(g);
+    const uint8_t *rec = records + geo.rec_off(g);
+    Fr r = fr_one();
+    if (n > 1 && have_digest) {                                        // k_rhash_lanes left the digest where c goes (read here, overwritten at the end)
+        uint32_t dw[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) dw[k] = scal_c[8 * (size_t)g + k];
+        fr_from_words(r, dw);
+    } else if (n > 1) {   // for n == 1 only r^0 = 1 is used (the reference takes the single-proof path, kzg.rs:658-660)
+        const uint32_t total_words = 8u + 40u * (uint32_t)n;            // message length / 4
+        const uint32_t nblocks = (total_words * 4u + 9u + 63u) / 64u;
+        const uint64_t bits = (uint64_t)total_words * 32u;
+        uint32_t h0 = 0x6a09e667u, h1 = 0xbb67ae85u, h2 = 0x3c6ef372u, h3 = 0xa54ff53au, h4 = 0x510e527fu, h5 = 0x9b05688cu, h6 = 0x1f83d9abu, h7 = 0x5be0cd19u;
+        for (uint32_t b0 = 0; b0 < nblocks; b0 += 64) {
+            const uint32_t b = b0 + (uint32_t)lane;
+            if (b < nblocks) {                                          // this lane expands block b
+                uint32_t w[16];
+#pragma unroll
+                for (int t = 0; t < 16; t++) {
+                    const uint32_t idx = 16u * b + (uint32_t)t;
+                    uint32_t v;
+                    if (idx < 8u) {
+                        const uint32_t hdr[8] = {0x52434b5au, 0x47424154u, 0x43485f5fu, 0x5f56315fu, 0u, (uint32_t)n_fe, 0u, (uint32_t)n};
+                        v = hdr[idx];                                   // "RCKZGBATCH___V1_" | 4096 | n
+                    } else if (idx < total_words) v = bswap32(reinterpret_cast<const uint32_t *>(rec)[idx - 8u]);   // records are 4-byte aligned
+                    else if (idx == total_words) v = 0x80000000u;
+                    else if (idx == 16u * nblocks - 2u) v = (uint32_t)(bits >> 32);
+                    else if (idx == 16u * nblocks - 1u) v = (uint32_t)bits;
+                    else v = 0u;
+                    w[t] = v;
+                }
+#pragma unroll
+                for (int t = 0; t < 64; t++) {
+                    if (t >= 16) {
+                        const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+                        const uint32_t s0 = xor3(ror(w15, 7), ror(w15, 18), w15 >> 3);
+                        const uint32_t s1 = xor3(ror(w2, 17), ror(w2, 19), w2 >> 10);
+                        w[t & 15] = w[t & 15] + s0 + w[(t + 9) & 15] + s1;
+                    }
+                    wk[t][lane] = w[t & 15] + SHA_K[t];
+                }
+            }
+            SHA_WAVE_SYNC();
+            if (lane == 0) {
+                const uint32_t cnt = nblocks - b0 < 64u ? nblocks - b0 : 64u;
+#pragma unroll 1
+                for (uint32_t q = 0; q < cnt; q++) {
+                    uint32_t a = h0, bb = h1, c = h2, d = h3, e = h4, f = h5, gg = h6, h = h7;
+#pragma unroll
+                    for (int t = 0; t < 64; t++) {
+                        const uint32_t t1 = h + xor3(ror(e, 6), ror(e, 11), ror(e, 25)) + ch3(e, f, gg) + wk[t][q];
+                        const uint32_t t2 = xor3(ror(a, 2), ror(a, 13), ror(a, 22)) + maj3(a, bb, c);
+                        h = gg; gg = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + t2;
+                    }
+                    h0 += a; h1 += bb; h2 += c; h3 += d; h4 += e; h5 += f; h6 += gg; h7 += h;
+                }
+            }
+            SHA_WAVE_SYNC();
+        }
+        if (lane == 0) { digest[0] = h7; digest[1] = h6; digest[2] = h5; digest[3] = h4; digest[4] = h3; digest[5] = h2; digest[6] = h1; digest[7] = h0; }
+        SHA_WAVE_SYNC();
+        uint32_t dw[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) dw[k] = digest[k];
+        fr_from_words(r, dw);                                           // hash_to_bls_field (utils.rs:472)
+    }
+    // lane l: r^l by square-and-multiply over its 6 index bits; step r^64
+    Fr pw = fr_one(), r64 = r;
+#pragma unroll 1
+    for (int bit = 5; bit >= 0; bit--) {
+        Fr t;
+        fr_sqr(pw, pw);
+        fr_mul(t, pw, r);
+        fr_select(pw, (lane >> bit) & 1, pw, t);
+        fr_sqr(r64, r64);
+    }
+    Fr csum = fr_zero();
+    bool bad = false;
+#pragma unroll 1
+    for (int i = lane; i < n; i += 64) {
+        uint32_t zw[8], yw[8];
+        be32_to_words(zw, rec + (size_t)RECORD_BYTES * i + 48);
+        be32_to_words(yw, rec + (size_t)RECORD_BYTES * i + 80);
+        if (check_zy) bad = bad || !fr_words_canonical(zw) || !fr_words_canonical(yw);
+        Fr z, y, t; fr_from_words(z, zw); fr_from_words(y, yw);
+        uint32_t *pa = scal_a + 8 * (geo.first(g) + i), *pb = scal_b + 8 * (geo.first(g) + i);
+        uint32_t ow[8];
+        fr_to_words(ow, pw); if (live) for (int k = 0; k < 8; k++) pa[k] = ow[k];
+        fr_mul(t, pw, z); fr_to_words(ow, t); if (live) for (int k = 0; k < 8; k++) pb[k] = ow[k];
+        fr_mul(t, pw, y); fr_add(csum, csum, t);
+        fr_mul(pw, pw, r64);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { Fr o = fr_shfl_down(csum, off); fr_add(csum, csum, o); }
+    if (lane == 0 && live) {
+        uint32_t ow[8]; fr_to_words(ow, csum);
+        for (int k = 0; k < 8; k++) scal_c[8 * (size_t)g + k] = ow[k];
+    }
+    if (bad && live) atomicOr(&err[g], ERR_NONCANONICAL_FR);
+}
+// The per-blob error words of a stage 1 run with one blob per "batch" -> the words of the batches they belong to: one wave per batch, its lanes
+// striding over the batch's blobs, four batches per workgroup.
+__global__ void __launch_bounds__(256) k_err_fold_sets(const int *blob_err, const int *goff, int groups, int *err) {
+    const int g = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= groups) return;
+    int acc = 0;
+    for (int i = goff[g] + lane; i < goff[g + 1]; i += 64) acc |= blob_err[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc |= __shfl_xor(acc, off);
+    if (lane == 0 && acc) atomicOr(&err[g], acc);
+}
 
 // ------------------------------------------------------------------------------------------------ pairing
 // One lane per batch:  ML([tau]G2, -proof_lincomb) * ML(G2, rhs)  ->  final exponentiation  ->  == 1 ?
@@ -635,6 +791,19 @@ void launch_rpowers(const uint8_t *d_records, int n_per_group, int groups, int c
     if (lanes) hipLaunchKernelGGL(k_rhash_lanes, dim3((groups + 63) / 64), dim3(64), 0, st, d_records, n_per_group, groups, d_scal_c, n_fe);
     hipLaunchKernelGGL(k_rpowers, dim3((groups + wpw - 1) / wpw), dim3(64 * wpw), 0, st, d_records, n_per_group, groups, check_zy, d_scal_a, d_scal_b,
             d_scal_c, d_err, n_fe, lanes || have_digest);
+}
+void launch_rpowers_sets(const uint8_t *d_records, const int *d_goff, int groups, int check_zy, uint32_t *d_scal_a, uint32_t *d_scal_b, uint32_t *d_scal_c,
+                         int *d_err, hipStream_t st, int n_fe, int lanes_from, int have_digest) {
+    if (groups <= 0) return;
+    const int wpw = groups > 512 ? 4 : 1;                         // (launch_rpowers' rule)
+    const int lanes = (!have_digest && groups >= lanes_from) ? 1 : 0;
+    if (lanes) hipLaunchKernelGGL(k_rhash_lanes_sets, dim3((groups + 63) / 64), dim3(64), 0, st, d_records, d_goff, groups, d_scal_c, n_fe);
+    hipLaunchKernelGGL(k_rpowers_sets, dim3((groups + wpw - 1) / wpw), dim3(64 * wpw), 0, st, d_records, d_goff, groups, check_zy, d_scal_a, d_scal_b,
+            d_scal_c, d_err, n_fe, lanes || have_digest);
+}
+void launch_err_fold_sets(const int *d_blob_err, const int *d_goff, int groups, int *d_err, hipStream_t st) {
+    if (groups <= 0) return;
+    hipLaunchKernelGGL(k_err_fold_sets, dim3((groups + 3) / 4), dim3(256), 0, st, d_blob_err, d_goff, groups, d_err);
 }
 void launch_pairing_lane(const PairPt *d_pair_pts, DeviceTables t, int groups, int *d_ok, hipStream_t st) {
     if (groups <= 0) return;

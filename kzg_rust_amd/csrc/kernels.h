@@ -132,6 +132,18 @@ void launch_lincomb_preshift_bytes(const uint8_t *d_commitments, const uint8_t *
 void launch_lincomb_preshifted(const G1Affine *d_pts, const G1Jac *d_shifts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c,
                                int n_per_group, int groups, void *d_scratch, PairPt *d_pair_pts, hipStream_t st,
                                        int stage = 0 /* 1: digits only; 2: sums only */);
+// Stage 2 for batches of different sizes in one launch set (kzg355_verify_blob_kzg_proof_batch_many_sets).  Stage 1 has run with one blob per
+// "batch": records blob after blob, points as [C_i, proof_i] pairs at 2 i, 2 i + 1, one error word per blob.  d_goff (groups + 1 ints) holds
+// the blobs before each batch and must be STRICTLY increasing (the host drops empty batches); n_total = d_goff[groups].  Batch g's scalars go to
+// d_scal_a / d_scal_b at 8 (d_goff[g] + i) and to d_scal_c at 8 g; its 2 (3 n_g + 1) lincomb items start at 2 (3 d_goff[g] + g).
+void launch_err_fold_sets(const int *d_blob_err, const int *d_goff, int groups, int *d_err /* per batch: or-ed into */, hipStream_t st);
+void launch_rpowers_sets(const uint8_t *d_records, const int *d_goff, int groups, int check_zy, uint32_t *d_scal_a, uint32_t *d_scal_b, uint32_t *d_scal_c,
+                         int *d_err, hipStream_t st, int n_fe, int lanes_from, int have_digest);
+size_t lincomb_sets_bytes(size_t n_total, size_t groups);
+void launch_lincomb_sets(const G1Affine *d_pts, const uint32_t *d_scal_a, const uint32_t *d_scal_b, const uint32_t *d_scal_c, const int *d_goff, int n_total,
+                         int groups, void *d_scratch /* lincomb_sets_bytes() */, PairPt *d_pair_pts, hipStream_t st);
+void launch_dump_intermediates_sets(const uint32_t *d_scal_a, const PairPt *d_pair_pts, const int *d_goff, int groups, uint8_t *d_out /* [groups][128] */,
+                                    hipStream_t st);
 void launch_pairing(const PairPt *d_pair_pts, DeviceTables t, int groups, int *d_ok, hipStream_t st,
                     int two_wave_upto = 256 /* batches up to which the two Miller loops of a check run on two waves */,
                     Fp *d_f12 = nullptr /* groups * 12 Fp of scratch */,

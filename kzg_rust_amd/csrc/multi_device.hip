@@ -80,6 +80,16 @@ int fan_out(const kzg355_settings *cs, size_t D, size_t units, const std::functi
     return tasks.join();
 }
 
+int fan_out_cuts(const kzg355_settings *cs, const std::vector<size_t> &cut, const std::function<int(const kzg355_settings *, size_t, size_t)> &fn) {
+    Tasks tasks;
+    for (size_t d = 0; d + 1 < cut.size() && d < cs->multi->rep.size(); d++) {
+        const size_t lo = cut[d], hi = cut[d + 1];
+        const kzg355_settings *rep = cs->multi->rep[d];
+        if (hi > lo) tasks.start(rep->device, [&fn, rep, lo, hi] { return fn(rep, lo, hi - lo); });
+    }
+    return tasks.join();
+}
+
 // fn(t) for t < tasks, task t on the device of the workspace gs[t] that the caller has taken already
 int fan_out_guards(const GuardList &gs, size_t tasks, const std::function<int(size_t)> &fn) {
     Tasks ts;

@@ -283,6 +283,95 @@ int verify_collect(Workspace *w, Timed &tm, bool *ok, int *status, int G, size_t
     return launch_set_read(w, (size_t)G, status, res_off, [&](size_t i, int &st) { if (st == KZG355_OK) ok[i] = w->h_ok.as<int>()[res_off + i] != 0; });
 }
 
+// ---- batches of different sizes in one launch set (kzg355_verify_blob_kzg_proof_batch_many_sets; the call around it: verify_sets.hip) ----------
+// Stage 2 on the `_sets` entries of its kernels: one ladder lane per GLV half of every term, whatever the batch sizes (the bucket and pre-shifted
+// forms are shaped by a uniform size and have no ragged entry).  d_goff: boff on the device, as ints.
+static int run_stage2_sets(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_records, const int *d_goff, const size_t *boff, int G,
+                           const G1Affine *d_pts, bool lone_call) {
+    int rc;
+    const size_t N = boff[G], groups = (size_t)G;
+    w->shift_ready = false; w->q_ready = false;
+    if ((rc = w->scal_a.ensure(32 * N)) || (rc = w->scal_b.ensure(32 * N)) || (rc = w->scal_c.ensure(32 * groups)) ||
+        (rc = w->pair_pts.ensure(sizeof(PairPt) * 2 * groups)) || (rc = w->lc_partials.ensure(lincomb_sets_bytes(N, groups)))) return rc;
+    // the batch challenges of a lone small call on the host, as run_stage2 does it: every batch of two records or more has a transcript
+    bool hashed = false;
+    for (int g = 0; g < G; g++) hashed = hashed || boff[g + 1] - boff[g] > 1;
+    const bool host_rhash = lone_call && hashed && s->host_rhash >= 0 && N <= (size_t)s->host_rhash_max_records && !is_small(s);
+    if (host_rhash) {
+        if ((rc = w->h_records.ensure((size_t)RECORD_BYTES * N)) || (rc = w->h_rdig.ensure(32 * groups))) return rc;
+        HIPCHK(hipMemcpyAsync(w->h_records.p, d_records, (size_t)RECORD_BYTES * N, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        std::vector<uint8_t> msg;
+        memset(w->h_rdig.p, 0, 32 * groups);                      // (a batch of one record has no digest: k_rpowers_sets does not read its slot)
+        for (int g = 0; g < G; g++) {
+            const size_t n = boff[g + 1] - boff[g];
+            if (n <= 1) continue;
+            msg.resize(32 + (size_t)RECORD_BYTES * n);
+            memcpy(msg.data(), "RCKZGBATCH___V1_", 16);            // RANDOM_CHALLENGE_KZG_BATCH_DOMAIN (consts.rs:25)
+            put_u64be(msg.data() + 16, (uint64_t)s->t.n_fe); put_u64be(msg.data() + 24, (uint64_t)n);
+            memcpy(msg.data() + 32, w->h_records.as<uint8_t>() + (size_t)RECORD_BYTES * boff[g], (size_t)RECORD_BYTES * n);
+            uint8_t dg[32];
+            kzg_host::sha256(dg, msg.data(), msg.size(), s->sha_impl);
+            uint32_t *dst = w->h_rdig.as<uint32_t>() + 8 * (size_t)g;      // the digest as an integer: 8 little-endian 32-bit words
+            for (int k = 0; k < 8; k++) dst[k] = ((uint32_t)dg[28 - 4 * k] << 24) | ((uint32_t)dg[29 - 4 * k] << 16) | ((uint32_t)dg[30 - 4 * k] << 8)
+                    | dg[31 - 4 * k];
+        }
+        HIPCHK(hipMemcpyAsync(w->scal_c.p, w->h_rdig.p, 32 * groups, hipMemcpyHostToDevice, w->stream));
+    }
+    tm.begin("rpowers"); launch_rpowers_sets(d_records, d_goff, G, 0, w->scal_a.as<uint32_t>(), w->scal_b.as<uint32_t>(), w->scal_c.as<uint32_t>(),
+            w->err.as<int>(), w->stream, s->t.n_fe, s->rhash_lanes_from, host_rhash ? 1 : 0); tm.end();
+    if ((rc = join_points(w))) return rc;                         // the decoded points are needed from here on
+    tm.begin("lincomb");
+    launch_lincomb_sets(d_pts, w->scal_a.as<uint32_t>(), w->scal_b.as<uint32_t>(), w->scal_c.as<uint32_t>(), d_goff, (int)N, G, w->lc_partials.p,
+            w->pair_pts.as<PairPt>(), w->stream);
+    tm.end();
+    tm.begin("pairing");
+    if (s->lane_pairing) launch_pairing_lane(w->pair_pts.as<PairPt>(), s->t, G, w->ok.as<int>(), w->stream);
+    else {
+        Fp *f12 = nullptr;                                        // (run_stage2's rule)
+        if (((s->pairing_hard12_from > 0 && G >= s->pairing_hard12_from) || G <= s->pairing_two_wave_upto) &&
+                w->pair_f.ensure(pairing_f12_bytes(G)) == KZG355_OK)
+            f12 = w->pair_f.as<Fp>();
+        launch_pairing(w->pair_pts.as<PairPt>(), s->t, G, w->ok.as<int>(), w->stream, s->pairing_two_wave_upto, f12, s->pairing_hard12_from,
+                s->miller_segments);
+    }
+    tm.end();
+    return KZG355_OK;
+}
+
+// Buffers by role beyond the uniform pair's: q = boff as ints | one error word per blob (what stage 1 writes with one blob per "batch"; folded into
+// the batches' words of launch_set_begin once the side streams have joined).
+int verify_sets_enqueue(kzg355_settings *s, Workspace *w, Timed &tm, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, const size_t *boff, int G,
+                        HostFront *hf, bool lone_call, bool dump) {
+    const size_t N = boff[G], groups = (size_t)G;
+    int rc;
+    if ((rc = w->records.ensure((size_t)RECORD_BYTES * N)) || (rc = w->pts.ensure(sizeof(G1Affine) * 2 * N)) ||
+        (rc = w->q.ensure(sizeof(int) * (groups + 1 + N))) || (dump && ((rc = w->out48.ensure(128 * groups)) || (rc = w->h_out.ensure(128 * groups)))))
+        return rc;
+    if ((rc = launch_set_begin(w, groups, true))) return rc;
+    int *d_goff = w->q.as<int>(), *d_blob_err = d_goff + (groups + 1);
+    std::vector<int> h_goff(groups + 1);
+    for (size_t g = 0; g <= groups; g++) h_goff[g] = (int)boff[g];
+    HIPCHK(hipMemcpyAsync(d_goff, h_goff.data(), sizeof(int) * h_goff.size(), hipMemcpyHostToDevice, w->stream));     // (pageable: staged before it returns)
+    HIPCHK(hipMemsetAsync(d_blob_err, 0, sizeof(int) * N, w->stream));
+    // no pre-shift and no Q's: neither has a ragged stage 2 to feed
+    if ((rc = run_stage1(s, w, tm, d_blobs, d_c, d_p, (int)N, 1, w->records.as<uint8_t>(), w->pts.as<G1Affine>(), d_blob_err, false, hf))) return rc;
+    if ((rc = run_stage2_sets(s, w, tm, w->records.as<uint8_t>(), d_goff, boff, G, w->pts.as<G1Affine>(), lone_call))) return rc;
+    if ((rc = join_side(w))) return rc;                           // the subgroup verdicts, before the error words are folded
+    tm.begin("err_fold"); launch_err_fold_sets(d_blob_err, d_goff, G, w->err.as<int>(), w->stream); tm.end();
+    if (dump) {
+        launch_dump_intermediates_sets(w->scal_a.as<uint32_t>(), w->pair_pts.as<PairPt>(), d_goff, G, w->out48.as<uint8_t>(), w->stream);
+        HIPCHK(hipMemcpyAsync(w->h_out.p, w->out48.p, 128 * groups, hipMemcpyDeviceToHost, w->stream));
+    }
+    return launch_set_results(w, groups, true);
+}
+
+int verify_sets_collect(Workspace *w, Timed &tm, bool *ok, int *status, uint8_t *dump, int G) {
+    const int rc = verify_collect(w, tm, ok, status, G);
+    if (dump && !call_failed(rc)) memcpy(dump, w->h_out.p, 128 * (size_t)G);        // (whatever the batches' statuses are, once the wait has succeeded)
+    return rc;
+}
+
 // Fiat-Shamir challenges of a host-buffer call hashed on the host threads (host_sha256.h), up to the measured crossover: the device hash is a 3.7 ms
 // chain for ANY call of up to 32,768 blobs; T host threads take ~35 us x blobs / T
 bool host_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs) {

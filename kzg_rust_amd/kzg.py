@@ -274,6 +274,18 @@ class KzgSettings:
             raise BadArgs("cell_calls_per_device")
         return list(out)
 
+    def set_blob_sets_max_blobs(self, max_blobs=0):
+        """Blobs per launch set of verify_blob_kzg_proof_batch_many_sets and its forms on this handle (0: the default, 32768)."""
+        _check(lib().kzg355_settings_set_blob_sets_max_blobs(self.handle, max_blobs), "set_blob_sets_max_blobs")
+
+    def blob_sets_blobs_per_device(self):
+        """One count per device of the handle: the blobs that device has run through verify_blob_kzg_proof_batch_many_sets and its forms."""
+        n = self.device_count
+        out = (C.c_long * n)()
+        if lib().kzg355_settings_blob_sets_blobs_per_device(self.handle, out, n) != n:
+            raise BadArgs("blob_sets_blobs_per_device")
+        return list(out)
+
     @property
     def host_threads(self):
         """host threads that hash for one call on this handle (its workers + the calling thread)"""
@@ -457,6 +469,77 @@ class Kzg:
         if _whole_call_failed(rc, st, G):                         # whole-call failure: the per-batch statuses are not to be trusted
             _check(rc, "verify_blob_kzg_proof_batch_many")
         return [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify") for i in range(G)]
+
+    @staticmethod
+    def _blob_sets(groups, s, debug):
+        flat = [[], [], []]
+        counts = []
+        for blobs, commitments, proofs in groups:
+            arrs = ([_blob(x, s) for x in blobs], [_b(x, KzgCommitment) for x in commitments], [_b(x, KzgProof) for x in proofs])
+            n = len(arrs[0])
+            if len(arrs[1]) != n or len(arrs[2]) != n:            # kzg.rs:644-651, before any FFI call
+                raise BadArgs("length mismatch")
+            counts.append(n)
+            for f, a in zip(flat, arrs):
+                f += a
+        G = len(counts)
+        ok = (C.c_bool * max(G, 1))()
+        st = (C.c_int * max(G, 1))()
+        cnt = (C.c_size_t * max(G, 1))(*counts)
+        args = (ok, st, cnt, b"".join(flat[0]), b"".join(flat[1]), b"".join(flat[2]), G, s.handle)
+        out = C.create_string_buffer(128 * max(G, 1)) if debug else None
+        rc = lib().kzg355_debug_batch_intermediates_sets(out, *args) if debug else lib().kzg355_verify_blob_kzg_proof_batch_many_sets(*args)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_kzg_proof_batch_many_sets")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_kzg_proof_batch_many_sets(groups, s):
+        """verify_blob_kzg_proof_batch_many for groups of any sizes (an empty group is True): list of (blobs, commitments, proofs), one
+        independent verify_blob_kzg_proof_batch per group, each with its own challenge r.  Returns a list of bool / Error."""
+        return Kzg._blob_sets(groups, s, False)[0]
+
+    @staticmethod
+    def debug_batch_intermediates_sets(groups, s):
+        """(verdicts as verify_blob_kzg_proof_batch_many_sets, [r (32) | proof_lincomb (48) | rhs (48) per group; zero bytes for an empty group])"""
+        res, raw = Kzg._blob_sets(groups, s, True)
+        return res, [raw[128 * i:128 * i + 128] for i in range(len(res))]
+
+    @staticmethod
+    def _blob_sets_device(blobs, commitments, proofs, blob_counts, s, debug):
+        counts = [int(c) for c in blob_counts]
+        if any(c < 0 for c in counts):
+            raise BadArgs("blob_counts out of range")
+        nb, G = sum(counts), len(counts)
+        ptrs = (Kzg._dev(blobs, "blobs", 32 * s.field_elements_per_blob * nb, optional=nb == 0), Kzg._dev(commitments, "commitments", 48 * nb, optional=nb == 0),
+                Kzg._dev(proofs, "proofs", 48 * nb, optional=nb == 0))
+        if G == 0:
+            return [], b""
+        ok = (C.c_bool * G)()
+        st = (C.c_int * G)()
+        cnt = (C.c_size_t * G)(*counts)
+        out = C.create_string_buffer(128 * G) if debug else None
+        if debug:
+            rc = lib().kzg355_debug_batch_intermediates_sets_device(out, ok, st, cnt, *ptrs, G, s.handle)
+        else:
+            rc = lib().kzg355_verify_blob_kzg_proof_batch_many_sets_device(ok, st, cnt, *ptrs, G, s.handle)
+        if _whole_call_failed(rc, st, G):
+            _check(rc, "verify_blob_kzg_proof_batch_many_sets_device")
+        res = [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("verify") for i in range(G)]
+        return res, (out.raw if debug else b"")
+
+    @staticmethod
+    def verify_blob_kzg_proof_batch_many_sets_device(blobs, commitments, proofs, blob_counts, s):
+        """verify_blob_kzg_proof_batch_many_sets on device memory: blobs (sum(blob_counts) blobs, uint8), commitments and proofs (* 48), group
+        after group with no padding; blob_counts is a host list.  Returns a list of bool / Error per group."""
+        return Kzg._blob_sets_device(blobs, commitments, proofs, blob_counts, s, False)[0]
+
+    @staticmethod
+    def debug_batch_intermediates_sets_device(blobs, commitments, proofs, blob_counts, s):
+        """(verdicts, [128 bytes per group]) as debug_batch_intermediates_sets, on device memory"""
+        res, raw = Kzg._blob_sets_device(blobs, commitments, proofs, blob_counts, s, True)
+        return res, [raw[128 * i:128 * i + 128] for i in range(len(res))]
 
     @staticmethod
     def verify_kzg_proof_many(commitments, zs, ys, proofs, s):

@@ -196,6 +196,12 @@ extern "C" {
     pub fn kzg355_debug_blob_cell_batch_intermediates_sets_device(out: *mut u8, ok: *mut bool, status: *mut c_int, blob_counts: *const usize,
                                                                   d_blobs: *const u8, d_commitments: *const u8, d_cell_proofs: *const u8, groups: usize,
                                                                   interp_form: c_int, prep_form: c_int, s: *const kzg355_settings) -> c_int;
+    // verify_blob_kzg_proof_batch on batches of different blob counts: blob_counts (host, `groups` entries), the three arrays batch after batch
+    pub fn kzg355_verify_blob_kzg_proof_batch_many_sets(ok: *mut bool, status: *mut c_int, blob_counts: *const usize, blobs: *const u8,
+                                                        commitments: *const u8, proofs: *const u8, groups: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_verify_blob_kzg_proof_batch_many_sets_device(ok: *mut bool, status: *mut c_int, blob_counts: *const usize, d_blobs: *const u8,
+                                                               d_commitments: *const u8, d_proofs: *const u8, groups: usize,
+                                                               s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_kzg_proof_many(ok: *mut bool, status: *mut c_int, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize,
                                         s: *const kzg355_settings) -> c_int;
     pub fn kzg355_verify_blob_kzg_proof_many(ok: *mut bool, status: *mut c_int, blobs: *const u8, commitments: *const u8, proofs: *const u8, n: usize,

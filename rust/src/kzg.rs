@@ -562,6 +562,43 @@ impl Kzg {
         Ok((0..groups).map(|g| check(st[g], "verify_blob_cells").map(|_| ok[g])).collect())
     }
 
+    /// `verify_blob_kzg_proof_batch` on batches of different blob counts in one call: batch `g` is the next `blob_counts[g]` entries of the three
+    /// slices, which hold the batches one after the other with no padding.  Each batch has its own challenge `r`, pairing and verdict; an empty
+    /// batch is `Ok(true)`.
+    pub fn verify_blob_kzg_proof_batch_many_sets(
+        blobs: &[Blob],
+        commitments: &[KzgCommitment],
+        proofs: &[KzgProof],
+        blob_counts: &[usize],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<bool, Error>>, Error> {
+        let n = blobs.len();
+        let total = blob_counts.iter().try_fold(0usize, |a, &c| a.checked_add(c));
+        if total != Some(n) || commitments.len() != n || proofs.len() != n {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let groups = blob_counts.len();
+        let staged = stage_blobs(blobs);
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let p: Vec<u8> = proofs.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut ok = vec![false; groups.max(1)];
+        let mut st = vec![0i32; groups.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_verify_blob_kzg_proof_batch_many_sets(
+                ok.as_mut_ptr(),
+                st.as_mut_ptr(),
+                blob_counts.as_ptr(),
+                staged.as_ptr(),
+                c.as_ptr(),
+                p.as_ptr(),
+                groups,
+                s.raw,
+            )
+        };
+        whole_call(rc, &st[..groups], "verify_blob_kzg_proof_batch_many_sets")?;
+        Ok((0..groups).map(|g| check(st[g], "verify_blob_kzg_proof_batch").map(|_| ok[g])).collect())
+    }
+
     /// EIP-7594 `compute_cells_and_kzg_proofs`: the 128 cells of the blob's 2x extension (cells 0..63 are the blob itself) and their 128 proofs,
     /// in cell order (FK20 on the device).
     pub fn compute_cells_and_kzg_proofs(blob: &Blob, s: &KzgSettings) -> Result<(Vec<Cell>, Vec<KzgProof>), Error> {
