@@ -193,6 +193,37 @@ int kzg355_verify_blob_kzg_proof_many(bool *ok /* n */, int *status /* n or NULL
 int kzg355_compute_kzg_proof_many(uint8_t *proofs_out /* n*48 */, uint8_t *ys_out /* n*32 */, int *status /* n or NULL */, const uint8_t *blobs,
                                   const uint8_t *zs /* n*32 */, size_t n, const kzg355_settings *s);
 
+/* ---- the EIP-4844 point-evaluation precompile (address 0x0A), batched ---------------------------- */
+/* The KZG question of the execution side.  Input i is KZG355_BYTES_PER_POINT_EVALUATION_INPUT bytes, versioned_hash[32] | z[32] | y[32] |
+ * commitment[48] | proof[48]; with vh(C) = 0x01 || SHA-256(C)[1:32]:
+ *   hash_match[i] = (versioned_hash == vh(commitment)) -- all 32 bytes compared (a wrong version byte is a mismatch), only the 48 bytes hashed,
+ *   nothing validated at this step;
+ *   no match: ok[i] = false, status[i] = KZG355_OK and NOTHING ELSE about that input is reported -- the precompile fails at the hash before it looks
+ *   at the rest, so invalid point bytes or a non-canonical z behind a wrong hash are still KZG355_OK / false;
+ *   match: ok[i] / status[i] are exactly what kzg355_verify_kzg_proof_many gives for (commitment, z, y, proof): a point that fails validate_kzg_g1
+ *   or a non-canonical z or y is that input's KZG355_BADARGS with ok[i] = false, and the other inputs are unaffected.
+ * Returns the first non-OK status in input order.  status may be NULL, hash_match may be NULL.  n == 0: KZG355_OK, nothing touched.
+ * REFUSED AS A WHOLE, from the arguments alone, before any array is read or any device touched, every status marked and every ok / hash_match
+ * false: a NULL handle, a NULL ok, a NULL inputs with n > 0, n above 2^24; for the device forms d_inputs or d_out not 16-byte aligned, or
+ * d_commitments not 4-byte aligned.  (The two hash calls have no per-input arrays: they return KZG355_BADARGS and write nothing.)
+ * Both _many forms run in launch sets of at most 2^17 inputs, whatever n is: per set one kernel hashes, compares and writes the 160-byte records
+ * C | z | y | proof, then the records chain of kzg355_verify_kzg_proof_many checks them (inputs whose hash does not match run through it with
+ * the others; its answer for them is dropped).  The host form stages the raw inputs of a set in pinned memory -- nothing is hashed or re-packed
+ * on the host -- and follows kzg355_verify_kzg_proof_many on a handle over several devices: contiguous ranges of inputs per device when n is at
+ * least the device count, else one device.  The device forms run on the handle's first device.  The caller's buffers are only read.  Every
+ * handle is served, the minimal preset included (verify_kzg_proof does not depend on the blob size). */
+#define KZG355_BYTES_PER_POINT_EVALUATION_INPUT 192
+/* pure host, no handle, no device: out[32 i ..] = 0x01 || sha256(commitments[48 i ..])[1:] */
+int kzg355_kzg_to_versioned_hash_many(uint8_t *out /* n*32 */, const uint8_t *commitments /* n*48 */, size_t n);
+int kzg355_kzg_to_versioned_hash_many_device(uint8_t *d_out /* n*32 */, const uint8_t *d_commitments /* n*48 */, size_t n, const kzg355_settings *s);
+int kzg355_point_evaluation_many(bool *ok, int *status /* or NULL */, bool *hash_match /* or NULL */, const uint8_t *inputs /* n*192 */, size_t n,
+                                 const kzg355_settings *s);
+int kzg355_point_evaluation_many_device(bool *ok /* host */, int *status /* host or NULL */, bool *hash_match /* host or NULL */,
+                                        const uint8_t *d_inputs /* n*192, 16-byte aligned */, size_t n, const kzg355_settings *s);
+/* one precompile call as the EIP words it.  KZG355_OK means success, and out = u256be(FIELD_ELEMENTS_PER_BLOB of the handle) | u256be(BLS_MODULUS).
+ * input_len != 192, a hash mismatch, an invalid input or a false proof: KZG355_BADARGS, and out is not written. */
+int kzg355_point_evaluation(uint8_t out[64], const uint8_t *input, size_t input_len, const kzg355_settings *s);
+
 /* ---- device-resident inputs (what bench.py times: blobs already in HBM) ----------------------- */
 /* As above, but d_* are DEVICE pointers (hipMalloc / torch tensors .data_ptr()) on the settings' device.
  * ok / status are host pointers.  Synchronous: returns when the verdicts are on the host. */

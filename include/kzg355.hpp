@@ -770,6 +770,69 @@ struct Kzg {
         }
         return out;
     }
+
+    // ---- the EIP-4844 point-evaluation precompile (address 0x0A): an input is versioned_hash (32) | z (32) | y (32) | commitment (48) | proof (48)
+    using PointEvaluationInput = FixedBytes<KZG355_BYTES_PER_POINT_EVALUATION_INPUT, Error::BadArgs>;
+    // per input: what verify_kzg_proof_many gives for its four fields, and whether its versioned hash is that of its commitment.  No match: false,
+    // and nothing else about the input is reported (the precompile fails at the hash before it looks at the rest)
+    struct PointEvaluation { Result<bool> result; bool hash_match; };
+    // 0x01 || sha256(commitment)[1:] per commitment, on the host: no handle, no device, nothing validated
+    static Result<std::vector<Bytes32>> kzg_to_versioned_hash_many(const std::vector<KzgCommitment> &cs) {
+        const size_t n = cs.size();
+        std::vector<uint8_t> c(n * 48 + 1), h(n * 32 + 1);
+        for (size_t i = 0; i < n; i++) std::memcpy(&c[i * 48], cs[i].data(), 48);
+        int rc = kzg355_kzg_to_versioned_hash_many(h.data(), c.data(), n);
+        if (rc) return from_status(rc, "kzg_to_versioned_hash_many");
+        std::vector<Bytes32> out(n);
+        for (size_t i = 0; i < n; i++) std::memcpy(out[i].bytes.data(), &h[i * 32], 32);
+        return out;
+    }
+    static Result<Bytes32> kzg_to_versioned_hash(const KzgCommitment &c) {
+        auto r = kzg_to_versioned_hash_many({c});
+        if (r.is_err()) return r.error();
+        return r.value()[0];
+    }
+    // d_commitments (n * 48 bytes, 4-byte aligned) -> d_out (n * 32 bytes, 16-byte aligned), device memory on the handle's first device
+    static Result<bool> kzg_to_versioned_hash_many_device(uint8_t *d_out, const uint8_t *d_commitments, size_t n, const KzgSettings &s) {
+        int rc = kzg355_kzg_to_versioned_hash_many_device(d_out, d_commitments, n, s.raw());
+        if (rc) return from_status(rc, "kzg_to_versioned_hash_many_device");
+        return true;
+    }
+    // what the two point_evaluation_many forms share: the call and its per-input results
+    static Result<std::vector<PointEvaluation>> point_evaluation_call(const uint8_t *inputs, size_t n, const KzgSettings &s, bool device) {
+        std::unique_ptr<bool[]> ok(new bool[n + 1]()), match(new bool[n + 1]());
+        std::vector<int> st(n, 0);
+        int rc = device ? kzg355_point_evaluation_many_device(ok.get(), st.data(), match.get(), inputs, n, s.raw())
+                        : kzg355_point_evaluation_many(ok.get(), st.data(), match.get(), inputs, n, s.raw());
+        if (whole_call_failed(rc, st)) return from_status(rc, "point_evaluation_many");
+        std::vector<PointEvaluation> out;
+        for (size_t i = 0; i < n; i++) {
+            if (st[i]) out.push_back(PointEvaluation{from_status(st[i], "point_evaluation"), match[i]});
+            else out.push_back(PointEvaluation{bool(ok[i]), match[i]});
+        }
+        return out;
+    }
+    static Result<std::vector<PointEvaluation>> point_evaluation_many(const std::vector<PointEvaluationInput> &inputs, const KzgSettings &s) {
+        const size_t n = inputs.size();
+        std::vector<uint8_t> in(n * KZG355_BYTES_PER_POINT_EVALUATION_INPUT + 1);
+        for (size_t i = 0; i < n; i++) std::memcpy(&in[i * KZG355_BYTES_PER_POINT_EVALUATION_INPUT], inputs[i].data(), KZG355_BYTES_PER_POINT_EVALUATION_INPUT);
+        return point_evaluation_call(in.data(), n, s, false);
+    }
+    // d_inputs: n * 192 bytes of device memory on the handle's first device, 16-byte aligned, only read
+    static Result<std::vector<PointEvaluation>> point_evaluation_many_device(const uint8_t *d_inputs, size_t n, const KzgSettings &s) {
+        return point_evaluation_call(d_inputs, n, s, true);
+    }
+    // one precompile call as the EIP words it: u256be(FIELD_ELEMENTS_PER_BLOB) | u256be(BLS_MODULUS) on success; BadArgs on a length other than 192,
+    // a hash mismatch, an invalid input or a false proof
+    static Result<std::vector<uint8_t>> point_evaluation(const uint8_t *input, size_t input_len, const KzgSettings &s) {
+        std::vector<uint8_t> out(64);
+        int rc = kzg355_point_evaluation(out.data(), input, input_len, s.raw());
+        if (rc) return from_status(rc, "point_evaluation");
+        return out;
+    }
+    static Result<std::vector<uint8_t>> point_evaluation(const std::vector<uint8_t> &input, const KzgSettings &s) {
+        return point_evaluation(input.data(), input.size(), s);
+    }
 };
 
 }  // namespace kzg355

@@ -139,6 +139,11 @@ def load():
         "kzg355_debug_batch_intermediates_sets_device": [u8p, bp, ip, szp, vp, vp, vp, sz, vp],
         "kzg355_settings_blob_sets_blobs_per_device": [vp, C.POINTER(C.c_long), sz],
         "kzg355_settings_set_blob_sets_max_blobs": [vp, sz],
+        "kzg355_kzg_to_versioned_hash_many": [u8p, u8p, sz],
+        "kzg355_kzg_to_versioned_hash_many_device": [vp, vp, sz, vp],
+        "kzg355_point_evaluation_many": [bp, ip, bp, u8p, sz, vp],
+        "kzg355_point_evaluation_many_device": [bp, ip, bp, vp, sz, vp],
+        "kzg355_point_evaluation": [u8p, u8p, sz, vp],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -203,4 +208,6 @@ EXPORTED_SYMBOLS = [
     "kzg355_verify_blob_kzg_proof_batch_many_sets", "kzg355_verify_blob_kzg_proof_batch_many_sets_device",
     "kzg355_debug_batch_intermediates_sets", "kzg355_debug_batch_intermediates_sets_device", "kzg355_settings_blob_sets_blobs_per_device",
     "kzg355_settings_set_blob_sets_max_blobs",
+    "kzg355_kzg_to_versioned_hash_many", "kzg355_kzg_to_versioned_hash_many_device", "kzg355_point_evaluation_many",
+    "kzg355_point_evaluation_many_device", "kzg355_point_evaluation",
 ]

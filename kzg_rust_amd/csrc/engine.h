@@ -15,6 +15,8 @@
 //   blob_cells.hip     verify_blob_cell_proofs_batch: blobs against all their cell proofs, the extension and the check in one launch set
 //   cell_proofs_at.hip compute_cell_kzg_proofs_at: the proofs of chosen cells, each the commitment to its own quotient (kernels: k_cell_quotient.hip)
 //   cell_recover_at.hip recover_cells_and_kzg_proofs_at: the field stage of the recovery, then the chain of chosen cells
+//   point_eval.hip     the EIP-4844 point-evaluation precompile, batched: versioned hashes and records on the device (kernels: k_point_eval.hip; the byte
+//                      layout: point_eval.h), then the records chain of verify_kzg_proof_many
 //   cell_plan.h        the chunk layout of the last three, plain host arithmetic without HIP (included through kernels.h)
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
@@ -453,6 +455,10 @@ bool host_call_hashes_on_host(const kzg355_settings *s, size_t n_blobs);
 HostFront *resident_front(kzg355_settings *s, HostFront &hf, const uint8_t *d_commitments, size_t n_blobs, InFlight *count = nullptr);
 int verify_many_device_impl(bool *ok, int *status, const uint8_t *d_blobs, const uint8_t *d_c, const uint8_t *d_p, size_t npg, size_t groups,
                             const kzg355_settings *cs);
+// entry_points.hip: stage 2 over `groups` batches of n records each in device memory, on a workspace of its own (validate: full validate_kzg_g1 on the
+// records' points and the canonical checks of z and y -- with n = 1 the chain of kzg355_verify_kzg_proof_many); the other arguments as described there
+int verify_records_impl(bool *ok, int *status, uint8_t *dump, const uint8_t *d_records, size_t n, size_t groups, int validate, const kzg355_settings *cs,
+                        const uint8_t *d_points = nullptr, int32_t *d_words = nullptr);
 int ensure_wide_table(kzg355_settings *s);
 // n MSMs over the handle's Lagrange points, scalars from blobs or (d_scalars: n * 4096 Montgomery Fr, blob order) as given: the 48-byte results in
 // w->out48 (msm_to_device), and copied on to w->h_out (msm_to_host)

@@ -54,8 +54,9 @@ static int shard_records_impl(uint8_t *d_records, uint8_t *d_points, int *status
 
 // stage 2 over gathered records; `dump` (host, groups*128 bytes or null) receives r | proof_lincomb | rhs per batch; d_points (or
 // null): the validated affine points of the records as stage 1 produced them ([batch][commitments, proofs]), sparing their decompression
-static int verify_records_impl(bool *ok, int *status, uint8_t *dump, const uint8_t *d_records, size_t n, size_t groups, int validate, const kzg355_settings *cs,
-                        const uint8_t *d_points = nullptr, int32_t *d_words = nullptr) {
+// (declared in engine.h: point_eval.hip runs the same chain behind its own front)
+int verify_records_impl(bool *ok, int *status, uint8_t *dump, const uint8_t *d_records, size_t n, size_t groups, int validate, const kzg355_settings *cs,
+                        const uint8_t *d_points, int32_t *d_words) {
     if (!cs || (!ok && !d_words)) return KZG355_BADARGS;
     if (groups == 0) return KZG355_OK;
     // (whole-call refusals mark every batch)

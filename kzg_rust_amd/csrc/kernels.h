@@ -193,6 +193,13 @@ void launch_fr_from_bytes(const uint8_t *d_in32, int n, Fr *d_out, int *d_err /*
 void launch_fr_to_bytes(const Fr *d_in, int n, uint8_t *d_out32, hipStream_t st);
 void launch_status_words(const int *d_err, const int *d_ok /* or null */, int32_t *d_words, int groups, hipStream_t st);
 
+// ---- k_point_eval.hip: the front of the point-evaluation precompile (point_eval.h has the byte layout), one lane per input
+// d_inputs: n * 192 bytes, versioned_hash | z | y | commitment | proof, 16-byte aligned and only read; d_records: n * RECORD_BYTES, 16-byte aligned;
+// d_match[i] = 1 when input i's versioned hash is 0x01 || sha256(commitment)[1:], else 0
+void launch_pe_unpack(const uint8_t *d_inputs, int n, uint8_t *d_records, int *d_match, hipStream_t st);
+// d_out[32 i ..] = 0x01 || sha256(d_commitments[48 i ..])[1:]; d_commitments 4-byte, d_out 16-byte aligned
+void launch_versioned_hash(const uint8_t *d_commitments, int n, uint8_t *d_out, hipStream_t st);
+
 // ---- k_cells.hip: verify_cell_kzg_proof_batch (EIP-7594 cells of the 2x extended blob; mainnet handles only)
 constexpr int CELL_FE = 64;                // FIELD_ELEMENTS_PER_CELL
 constexpr int CELL_BYTES = CELL_FE * 32;   // BYTES_PER_CELL

@@ -22,6 +22,7 @@ TRUSTED_SETUP_NUM_G2_POINTS = 65  # consts.rs:37
 # EIP-7594 (PeerDAS) cells: 64 field elements of a blob's 2x Reed-Solomon extension
 FIELD_ELEMENTS_PER_CELL = 64
 BYTES_PER_CELL = 2048
+BYTES_PER_POINT_EVALUATION_INPUT = 192   # versioned_hash | z | y | commitment | proof (EIP-4844, point_evaluation_precompile)
 CELLS_PER_EXT_BLOB = 128
 
 
@@ -590,6 +591,76 @@ class Kzg:
             _check(rc, "compute_kzg_proof_many")
         return [(KzgProof(out.raw[48 * i:48 * i + 48]), Bytes32(ys.raw[32 * i:32 * i + 32])) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("proof")
                 for i in range(n)]
+
+    # ---- the EIP-4844 point-evaluation precompile (address 0x0A): an input is versioned_hash (32) | z (32) | y (32) | commitment (48) | proof (48) ----
+    @staticmethod
+    def kzg_to_versioned_hash_many(commitments):
+        """0x01 || sha256(commitment)[1:] per commitment, on the host (no handle, no device; nothing is validated).  Returns a list of 32-byte hashes."""
+        cs = [_b(x, KzgCommitment) for x in commitments]
+        n = len(cs)
+        out = C.create_string_buffer(32 * max(n, 1))
+        _check(lib().kzg355_kzg_to_versioned_hash_many(out, b"".join(cs), n), "kzg_to_versioned_hash_many")
+        return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+    @staticmethod
+    def kzg_to_versioned_hash(commitment):
+        """kzg_to_versioned_hash of EIP-4844: the 32-byte versioned hash of one commitment."""
+        return Kzg.kzg_to_versioned_hash_many([commitment])[0]
+
+    @staticmethod
+    def kzg_to_versioned_hash_many_device(out, commitments, n, s):
+        """The same on device memory: commitments (n * 48 bytes, uint8, 4-byte aligned) -> out (n * 32 bytes, uint8, 16-byte aligned), both on the
+        handle's first device; out is written by a kernel of the library's own."""
+        n = int(n)
+        if n < 0:
+            raise BadArgs("n out of range")
+        ptrs = (Kzg._dev(out, "out", 32 * n, optional=n == 0), Kzg._dev(commitments, "commitments", 48 * n, optional=n == 0))
+        _check(lib().kzg355_kzg_to_versioned_hash_many_device(*ptrs, n, s.handle), "kzg_to_versioned_hash_many_device")
+
+    @staticmethod
+    def _point_evaluation_results(rc, ok, st, match, n, call):
+        if _whole_call_failed(rc, st, n):
+            _check(rc, call)
+        return [bool(ok[i]) if st[i] == 0 else _ERRORS.get(st[i], InternalError)("point_evaluation") for i in range(n)], [bool(match[i]) for i in range(n)]
+
+    @staticmethod
+    def point_evaluation_many(inputs, s):
+        """n point-evaluation precompile inputs of 192 bytes in one call.  Returns (results, hash_match): per input True, False or an Error as
+        verify_kzg_proof_many gives them, and whether its versioned hash is that of its commitment.  An input whose hash does not match is False
+        and nothing else about it is reported (the precompile fails at the hash before it looks at the rest)."""
+        data = [bytes(x) for x in inputs]
+        if any(len(d) != BYTES_PER_POINT_EVALUATION_INPUT for d in data):
+            raise BadArgs(f"point evaluation input: expected {BYTES_PER_POINT_EVALUATION_INPUT} bytes")
+        n = len(data)
+        if n == 0:
+            return [], []
+        ok, st, match = (C.c_bool * n)(), (C.c_int * n)(), (C.c_bool * n)()
+        rc = lib().kzg355_point_evaluation_many(ok, st, match, b"".join(data), n, s.handle)
+        return Kzg._point_evaluation_results(rc, ok, st, match, n, "point_evaluation_many")
+
+    @staticmethod
+    def point_evaluation_many_device(inputs, n, s):
+        """point_evaluation_many on device memory: inputs (n * 192 bytes, uint8, 16-byte aligned) on the handle's first device, only read."""
+        n = int(n)
+        if n < 0:
+            raise BadArgs("n out of range")
+        ptr = Kzg._dev(inputs, "inputs", BYTES_PER_POINT_EVALUATION_INPUT * n, optional=n == 0)
+        if n == 0:
+            return [], []
+        ok, st, match = (C.c_bool * n)(), (C.c_int * n)(), (C.c_bool * n)()
+        rc = lib().kzg355_point_evaluation_many_device(ok, st, match, ptr, n, s.handle)
+        return Kzg._point_evaluation_results(rc, ok, st, match, n, "point_evaluation_many_device")
+
+    @staticmethod
+    def point_evaluation(input, s):
+        """One precompile call as EIP-4844 words it: the 64 bytes u256be(FIELD_ELEMENTS_PER_BLOB) | u256be(BLS_MODULUS) on success; BadArgs on an
+        input that is not 192 bytes, a hash mismatch, an invalid input or a false proof."""
+        data = bytes(input)
+        if len(data) != BYTES_PER_POINT_EVALUATION_INPUT:
+            raise BadArgs(f"point evaluation input: expected {BYTES_PER_POINT_EVALUATION_INPUT} bytes")
+        out = C.create_string_buffer(64)
+        _check(lib().kzg355_point_evaluation(out, data, len(data), s.handle), "point_evaluation")
+        return out.raw
 
     # ---- EIP-7594 cell proofs (consensus specs fulu/polynomial-commitments-sampling.md; no reference counterpart) ----
     @staticmethod

@@ -15,3 +15,5 @@ pub const TRUSTED_SETUP_NUM_G2_POINTS: usize = 65;
 pub const FIELD_ELEMENTS_PER_CELL: usize = 64;
 pub const BYTES_PER_CELL: usize = 2048;
 pub const CELLS_PER_EXT_BLOB: usize = 128;
+// EIP-4844 point-evaluation precompile input: versioned_hash | z | y | commitment | proof
+pub const BYTES_PER_POINT_EVALUATION_INPUT: usize = 192;

@@ -208,6 +208,15 @@ extern "C" {
                                              s: *const kzg355_settings) -> c_int;
     pub fn kzg355_compute_kzg_proof_many(proofs_out: *mut u8, ys_out: *mut u8, status: *mut c_int, blobs: *const u8, zs: *const u8, n: usize,
                                          s: *const kzg355_settings) -> c_int;
+    // the EIP-4844 point-evaluation precompile: inputs n*192 (versioned_hash | z | y | commitment | proof); status and hash_match may be null;
+    // the versioned hashes (n*32 from n*48) on host memory without a handle, or on device memory
+    pub fn kzg355_kzg_to_versioned_hash_many(out: *mut u8, commitments: *const u8, n: usize) -> c_int;
+    pub fn kzg355_kzg_to_versioned_hash_many_device(d_out: *mut u8, d_commitments: *const u8, n: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_point_evaluation_many(ok: *mut bool, status: *mut c_int, hash_match: *mut bool, inputs: *const u8, n: usize,
+                                        s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_point_evaluation_many_device(ok: *mut bool, status: *mut c_int, hash_match: *mut bool, d_inputs: *const u8, n: usize,
+                                               s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_point_evaluation(out: *mut u8, input: *const u8, input_len: usize, s: *const kzg355_settings) -> c_int;
 
     pub fn kzg355_settings_device(s: *const kzg355_settings) -> c_int;
     pub fn kzg355_settings_device_count(s: *const kzg355_settings) -> c_int;

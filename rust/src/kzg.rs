@@ -1154,6 +1154,63 @@ impl Kzg {
             })
             .collect())
     }
+
+    /// `kzg_to_versioned_hash` of EIP-4844 per commitment, on the host: `0x01 || sha256(commitment)[1..]`.  No handle, no device; nothing is validated.
+    pub fn kzg_to_versioned_hash_many(commitments: &[KzgCommitment]) -> Result<Vec<Bytes32>, Error> {
+        let n = commitments.len();
+        let c: Vec<u8> = commitments.iter().flat_map(|x| x.to_bytes()).collect();
+        let mut out = vec![0u8; 32 * n.max(1)];
+        check(unsafe { ffi::kzg355_kzg_to_versioned_hash_many(out.as_mut_ptr(), c.as_ptr(), n) }, "kzg_to_versioned_hash_many")?;
+        Ok((0..n).map(|i| Bytes32::from(<[u8; 32]>::try_from(&out[32 * i..32 * i + 32]).unwrap())).collect())
+    }
+
+    /// The versioned hash of one commitment.
+    pub fn kzg_to_versioned_hash(commitment: &KzgCommitment) -> Result<Bytes32, Error> {
+        Ok(Self::kzg_to_versioned_hash_many(std::slice::from_ref(commitment))?.remove(0))
+    }
+
+    /// The same on device memory: `d_commitments` (`n * 48` bytes) to `d_out` (`n * 32` bytes).
+    ///
+    /// # Safety
+    /// Both are device pointers on the handle's first device, `d_out` 16-byte and `d_commitments` 4-byte aligned, valid for the call.
+    pub unsafe fn kzg_to_versioned_hash_many_device(d_out: *mut u8, d_commitments: *const u8, n: usize, s: &KzgSettings) -> Result<(), Error> {
+        check(ffi::kzg355_kzg_to_versioned_hash_many_device(d_out, d_commitments, n, s.raw), "kzg_to_versioned_hash_many_device")
+    }
+
+    /// `inputs.len()` inputs of the EIP-4844 point-evaluation precompile (`versioned_hash | z | y | commitment | proof`) in one call.  Per input:
+    /// what `verify_kzg_proof_many` gives for its four fields, and whether its versioned hash is that of its commitment.  An input whose hash
+    /// does not match is `Ok(false)` and nothing else about it is reported: the precompile fails at the hash before it looks at the rest.
+    pub fn point_evaluation_many(inputs: &[[u8; BYTES_PER_POINT_EVALUATION_INPUT]], s: &KzgSettings) -> Result<Vec<(Result<bool, Error>, bool)>, Error> {
+        let n = inputs.len();
+        let staged: Vec<u8> = inputs.iter().flat_map(|x| x.iter().copied()).collect();
+        let mut ok = vec![false; n.max(1)];
+        let mut matched = vec![false; n.max(1)];
+        let mut st = vec![0i32; n.max(1)];
+        let rc = unsafe { ffi::kzg355_point_evaluation_many(ok.as_mut_ptr(), st.as_mut_ptr(), matched.as_mut_ptr(), staged.as_ptr(), n, s.raw) };
+        whole_call(rc, &st[..n], "point_evaluation_many")?;
+        Ok((0..n).map(|i| (check(st[i], "point_evaluation").map(|_| ok[i]), matched[i])).collect())
+    }
+
+    /// `point_evaluation_many` on `n` inputs in device memory.
+    ///
+    /// # Safety
+    /// `d_inputs` is a device pointer on the handle's first device to `n * 192` bytes, 16-byte aligned, valid for the call; it is only read.
+    pub unsafe fn point_evaluation_many_device(d_inputs: *const u8, n: usize, s: &KzgSettings) -> Result<Vec<(Result<bool, Error>, bool)>, Error> {
+        let mut ok = vec![false; n.max(1)];
+        let mut matched = vec![false; n.max(1)];
+        let mut st = vec![0i32; n.max(1)];
+        let rc = ffi::kzg355_point_evaluation_many_device(ok.as_mut_ptr(), st.as_mut_ptr(), matched.as_mut_ptr(), d_inputs, n, s.raw);
+        whole_call(rc, &st[..n], "point_evaluation_many_device")?;
+        Ok((0..n).map(|i| (check(st[i], "point_evaluation").map(|_| ok[i]), matched[i])).collect())
+    }
+
+    /// One precompile call as EIP-4844 words it: `u256be(FIELD_ELEMENTS_PER_BLOB) | u256be(BLS_MODULUS)` on success; `BadArgs` on an input that
+    /// is not 192 bytes, a hash mismatch, an invalid input or a false proof.
+    pub fn point_evaluation(input: &[u8], s: &KzgSettings) -> Result<[u8; 64], Error> {
+        let mut out = [0u8; 64];
+        check(unsafe { ffi::kzg355_point_evaluation(out.as_mut_ptr(), input.as_ptr(), input.len(), s.raw) }, "point_evaluation")?;
+        Ok(out)
+    }
 }
 
 /// `&[Blob]` is a slice of boxes: the blobs are not contiguous in memory, the ABI wants one buffer.
