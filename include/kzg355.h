@@ -529,6 +529,44 @@ int kzg355_compute_cell_kzg_proofs_at_many(uint8_t *cells_out /* (sum of the cou
 int kzg355_compute_cell_kzg_proofs_at_many_device(uint8_t *d_cells_out, uint8_t *d_proofs_out, int *status /* host */, const uint8_t *d_blobs, size_t n,
                                                   const size_t *cell_counts /* HOST */, const size_t *cell_indices /* HOST */,
                                                   const kzg355_settings *s);
+/* ---- openings at chosen points --------------------------------------------------------------------------------------------------------------
+ * A blob opened at k points of the caller's choice: the proofs and the values y = p(z) that kzg355_verify_kzg_proof and the point-evaluation
+ * precompile (kzg355_point_evaluation_many) consume.  kzg355_compute_kzg_proof_many takes one 128 KiB blob per opening; here the blob is given
+ * once (a server of preimage or fault-proof requests opens the same blob at many points), and every (blob, point) pair is computed on its own
+ * -- the quotient of the blob polynomial by X - z by synthetic division, which needs no inversion and is the same route for a z inside the
+ * domain as for any other, through the fixed-base MSM of the commitment calls.
+ * Layout: slot j receives the proof and y of point zs[32 j .. 32 j + 32), byte for byte what kzg355_compute_kzg_proof returns for (blob, z).
+ * Points may repeat, come in any order and lie inside the domain.  k may be 0 (the blob is still read and checked; zs may then be NULL) and
+ * may not exceed 4096, one opening per element of the blob.  Either output may be NULL, not both (KZG355_BADARGS); without proofs_out no MSM
+ * runs and no MSM table is built: the call is then evaluate_polynomial_in_evaluation_form at many points.  A blob element >= r, a point >= r
+ * (non-canonical) or k > 4096 -> KZG355_BADARGS.  The first call that wants proofs builds the handle's fixed-base MSM table, exactly as the
+ * first commitment does (kzg355_options.msm_bits; kzg355_settings_build_msm_table builds it ahead of time); a handle loaded with
+ * msm_bits = 8 runs the bucket form and gives the same bytes.  Mainnet handles only. */
+int kzg355_compute_kzg_proofs_at(uint8_t *proofs_out /* k*48 or NULL */, uint8_t *ys_out /* k*32 or NULL */, const uint8_t *blob,
+                                 const uint8_t *zs /* k*32 */, size_t k, const kzg355_settings *s);
+/* n independent calls of the above in one set of launches: blob i is opened at point_counts[i] points; with off_i = point_counts[0] + .. +
+ * point_counts[i-1], its points are zs[32 off_i .. 32 (off_i + point_counts[i])) and output slot off_i + j receives the proof and y of the
+ * j-th of them.  A count may be 0: that blob is still read and checked, and it fills no slot.  What is wrong with one blob is that blob's
+ * KZG355_BADARGS: an element >= r, any of its points >= r, a count > 4096.  The other blobs are computed and are right: the layout always
+ * follows the counts as given.  The return value is the first non-OK status in blob order; the output slots of a refused blob are
+ * unspecified.  What is wrong with the call refuses it as a whole and marks every status, before any array is read or any device is
+ * touched: a NULL handle, both outputs NULL, NULL blobs or point_counts with n > 0, NULL zs while the counts sum to more than 0, a handle of
+ * another FIELD_ELEMENTS_PER_BLOB, n > 2^32, a sum of the counts that overflows size_t (alone or times 48).  n == 0 -> OK, and nothing is
+ * touched.  A handle over several devices spreads contiguous ranges of blobs over them, each range's points and slots starting at the sum of
+ * the counts before it, and every range counts in kzg355_settings_cell_calls_per_device.  Large calls run in chunks of at most 512 blobs and
+ * 1152 openings; a blob with more openings than a chunk has room for is cut at the chunk's border and read again by the next chunk.
+ * Not offered: cutting one blob's points over several devices (a range is whole blobs); a status per point; an FK20 form for all 4096
+ * openings of a blob. */
+int kzg355_compute_kzg_proofs_at_many(uint8_t *proofs_out /* (sum of the counts)*48 or NULL */, uint8_t *ys_out /* (sum)*32 or NULL */,
+                                      int *status /* n or NULL */, const uint8_t *blobs /* n*131072 */, size_t n,
+                                      const size_t *point_counts /* n */, const uint8_t *zs /* (sum of the counts)*32 */,
+                                      const kzg355_settings *s);
+/* The same with the blobs and both outputs in HBM: device pointers on the handle's device (its first device, for a handle over several: the
+ * call runs on that device alone), 16-byte aligned -- a misaligned pointer refuses the call as a whole; status, the counts and zs stay HOST
+ * arguments (the host checks the points while it plans the chunks).  The blobs are read and the slots written where they are; nothing but
+ * the points, the pair list and the status words crosses PCIe. */
+int kzg355_compute_kzg_proofs_at_many_device(uint8_t *d_proofs_out, uint8_t *d_ys_out, int *status /* host */, const uint8_t *d_blobs, size_t n,
+                                             const size_t *point_counts /* HOST */, const uint8_t *zs /* HOST */, const kzg355_settings *s);
 /* ---- chosen cells of recovered blobs -----------------------------------------------------------------------------------------------------
  * kzg355_recover_cells_and_kzg_proofs runs the whole FK20 chain whatever is wanted of its 128 proofs.  A node that holds most columns of a
  * block and lacks a few wants the cells and proofs of the missing ones, or of the few it custodies: here the blob is recovered as there, and

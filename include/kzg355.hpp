@@ -771,6 +771,60 @@ struct Kzg {
         return out;
     }
 
+    // The blob opened at the points zs (any order, repeats allowed, inside the domain or not; at most 4096): entry j is what compute_kzg_proof returns
+    // for (blob, zs[j]), every point through its own quotient and one MSM, and the blob is handed over once
+    static Result<std::pair<std::vector<KzgProof>, std::vector<Bytes32>>> compute_kzg_proofs_at(const Blob &blob, const std::vector<Bytes32> &zs,
+                                                                                                const KzgSettings &s) {
+        const size_t k = zs.size();
+        std::vector<uint8_t> z(k * 32 + 1), pr(k * 48 + 1), ys(k * 32 + 1);      // (data() of an empty vector may be null)
+        for (size_t j = 0; j < k; j++) std::memcpy(&z[j * 32], zs[j].data(), 32);
+        int rc = kzg355_compute_kzg_proofs_at(pr.data(), ys.data(), blob.data(), z.data(), k, s.raw());
+        if (rc) return from_status(rc, "compute_kzg_proofs_at");
+        std::pair<std::vector<KzgProof>, std::vector<Bytes32>> out;
+        for (size_t j = 0; j < k; j++) {
+            KzgProof p; Bytes32 y;
+            std::memcpy(p.bytes.data(), &pr[j * 48], 48); std::memcpy(y.bytes.data(), &ys[j * 32], 32);
+            out.first.push_back(p); out.second.push_back(y);
+        }
+        return out;
+    }
+
+    // One independent compute_kzg_proofs_at per blob, each with its own list of points (which may be empty), in one set of launches.  One Result per
+    // blob; blobs and point_lists of different lengths are BadArgs for the call.
+    static Result<std::vector<Result<std::pair<std::vector<KzgProof>, std::vector<Bytes32>>>>> compute_kzg_proofs_at_many(
+        const std::vector<Blob> &blobs, const std::vector<std::vector<Bytes32>> &point_lists, const KzgSettings &s) {
+        const size_t n = blobs.size();
+        if (point_lists.size() != n) return Error{Error::BadArgs, "length mismatch"};
+        std::vector<size_t> counts;
+        std::vector<uint8_t> in(n * BYTES_PER_BLOB + 1), z;
+        for (size_t i = 0; i < n; i++) {
+            std::memcpy(&in[i * BYTES_PER_BLOB], blobs[i].data(), BYTES_PER_BLOB);
+            counts.push_back(point_lists[i].size());
+            for (const Bytes32 &x : point_lists[i]) z.insert(z.end(), x.data(), x.data() + 32);
+        }
+        const size_t total = z.size() / 32;
+        std::vector<uint8_t> pr((total + 1) * 48), ys((total + 1) * 32);
+        std::vector<int> st(n + 1, 0);
+        counts.push_back(0);                                       // (data() of an empty vector may be null)
+        z.push_back(0);
+        int rc = kzg355_compute_kzg_proofs_at_many(pr.data(), ys.data(), st.data(), in.data(), n, counts.data(), z.data(), s.raw());
+        st.resize(n);
+        if (whole_call_failed(rc, st)) return from_status(rc, "compute_kzg_proofs_at_many");
+        std::vector<Result<std::pair<std::vector<KzgProof>, std::vector<Bytes32>>>> out;
+        size_t off = 0;
+        for (size_t i = 0; i < n; off += counts[i], i++) {
+            if (st[i]) { out.push_back(from_status(st[i], "compute_kzg_proofs_at")); continue; }
+            std::pair<std::vector<KzgProof>, std::vector<Bytes32>> r;
+            for (size_t j = off; j < off + counts[i]; j++) {
+                KzgProof p; Bytes32 y;
+                std::memcpy(p.bytes.data(), &pr[j * 48], 48); std::memcpy(y.bytes.data(), &ys[j * 32], 32);
+                r.first.push_back(p); r.second.push_back(y);
+            }
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+
     // ---- the EIP-4844 point-evaluation precompile (address 0x0A): an input is versioned_hash (32) | z (32) | y (32) | commitment (48) | proof (48)
     using PointEvaluationInput = FixedBytes<KZG355_BYTES_PER_POINT_EVALUATION_INPUT, Error::BadArgs>;
     // per input: what verify_kzg_proof_many gives for its four fields, and whether its versioned hash is that of its commitment.  No match: false,

@@ -105,6 +105,9 @@ def load():
         "kzg355_compute_cell_kzg_proofs_at": [u8p, u8p, u8p, szp, sz, vp],
         "kzg355_compute_cell_kzg_proofs_at_many": [u8p, u8p, ip, u8p, sz, szp, szp, vp],
         "kzg355_compute_cell_kzg_proofs_at_many_device": [vp, vp, ip, vp, sz, szp, szp, vp],
+        "kzg355_compute_kzg_proofs_at": [u8p, u8p, u8p, u8p, sz, vp],
+        "kzg355_compute_kzg_proofs_at_many": [u8p, u8p, ip, u8p, sz, szp, u8p, vp],
+        "kzg355_compute_kzg_proofs_at_many_device": [vp, vp, ip, vp, sz, szp, u8p, vp],
         "kzg355_recover_cells_and_kzg_proofs_at": [u8p, u8p, szp, u8p, sz, szp, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_at_many_sets": [u8p, u8p, ip, szp, szp, u8p, szp, szp, sz, vp],
         "kzg355_recover_cells_and_kzg_proofs_at_many_sets_device": [vp, vp, ip, szp, szp, vp, szp, szp, sz, vp],
@@ -210,4 +213,5 @@ EXPORTED_SYMBOLS = [
     "kzg355_settings_set_blob_sets_max_blobs",
     "kzg355_kzg_to_versioned_hash_many", "kzg355_kzg_to_versioned_hash_many_device", "kzg355_point_evaluation_many",
     "kzg355_point_evaluation_many_device", "kzg355_point_evaluation",
+    "kzg355_compute_kzg_proofs_at", "kzg355_compute_kzg_proofs_at_many", "kzg355_compute_kzg_proofs_at_many_device",
 ]

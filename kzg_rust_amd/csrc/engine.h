@@ -17,7 +17,10 @@
 //   cell_recover_at.hip recover_cells_and_kzg_proofs_at: the field stage of the recovery, then the chain of chosen cells
 //   point_eval.hip     the EIP-4844 point-evaluation precompile, batched: versioned hashes and records on the device (kernels: k_point_eval.hip; the byte
 //                      layout: point_eval.h), then the records chain of verify_kzg_proof_many
-//   cell_plan.h        the chunk layout of the last three, plain host arithmetic without HIP (included through kernels.h)
+//   point_proofs_at.hip compute_kzg_proofs_at: a blob opened at many chosen points, each proof the commitment to its own quotient (kernels:
+//                      k_point_quotient.hip)
+//   cell_plan.h        the chunk layout of the three chosen-cell and recover calls, plain host arithmetic without HIP (included through kernels.h)
+//   point_plan.h       the same for compute_kzg_proofs_at, whose chunks may cut a blob
 // Mirrors the control flow of the reference's `impl Kzg` forwards and the functions behind them (src/kzg.rs:401-693, 833-979): argument
 // checks and early exits happen on the host, all arithmetic on the device.  There is no CPU fallback: without a usable HIP device every
 // entry point returns KZG355_NO_DEVICE (a HIP call that fails on a device that exists: KZG355_DEVICE_ERROR).
@@ -498,6 +501,8 @@ inline bool misaligned(const void *a, const void *b, const void *c, const void *
 }
 // cell_plan.h lays out the chunks of the recover and chosen-cell calls without HIP; its constants are the kernels'
 static_assert(PLAN_CELLS == (size_t)CELLS_PER_EXT_BLOB && PLAN_CELL_BYTES == (size_t)CELL_BYTES && PLAN_REFUSED == ERR_NONCANONICAL_FR, "cell_plan.h");
+// point_plan.h does the same for compute_kzg_proofs_at (point_proofs_at.hip)
+static_assert(PLAN_POINTS == (size_t)N_FE && PLAN_POINT_REFUSED == ERR_NONCANONICAL_FR, "point_plan.h");
 // cell_recover.hip: the field stage of a recover chunk that rs has laid out (mc blobs; `cells` is the call's known cells, host or device memory;
 // refused: the chunk's err words, or null when the host refused none).  Queues the host form's copy runs into w->blobs, the upload of the masks
 // and descriptors into w->z behind the tables (RecoverStage::masks_off) and rc_vanish, rc_interp and rc_columns: u in w->scal_b, and with

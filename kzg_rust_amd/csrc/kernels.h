@@ -12,6 +12,7 @@
 #include "pairing_coop.h"
 #include "eval_core.h"
 #include "cell_plan.h"
+#include "point_plan.h"
 
 namespace kzg {
 
@@ -330,6 +331,13 @@ void launch_cc_proofs(const G1Jac *d_Z, int n, const CellComputeConsts *d_cc, ui
 void launch_cq_quotient(const Fr *d_coef, const CqPair *d_pairs, int pairs, const int *d_err, const CellComputeConsts *d_cc, Fr *d_scal, hipStream_t st);
 // d_cells as launch_cc_field leaves them (128 cells per blob of the chunk); pair p's cell goes to d_out + 2048 * d_pairs[p].slot
 void launch_cq_gather(const uint8_t *d_cells, const CqPair *d_pairs, int pairs, uint8_t *d_out, hipStream_t st);
+
+// ---- k_point_quotient.hip: compute_kzg_proofs_at, openings of blobs at chosen points (mainnet handles only)
+// d_coef and d_err (per blob of the chunk) as launch_cc_field leaves them; d_zs: the pairs' points, Montgomery, in pair order.  d_ys (or null):
+// pair p's y = p(z), 32 canonical bytes, at d_ys + 32 * d_pairs[p].slot.  d_scal (or null: no quotient is formed): pairs * 4096 Fr, Montgomery, in
+// blob order, as launch_cq_quotient leaves them
+void launch_pq_quotient(const Fr *d_coef, const PqPair *d_pairs, const Fr *d_zs, int pairs, const int *d_err, const CellComputeConsts *d_cc, Fr *d_scal,
+                        uint8_t *d_ys, hipStream_t st);
 
 // ---- k_cell_recover.hip: the field stage of recover_cells_and_kzg_proofs (64..128 known cells -> coefficients and all 128 cells; mainnet handles only)
 struct RecoverTables {                                        // one per distinct index set of a chunk

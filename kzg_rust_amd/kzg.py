@@ -958,6 +958,48 @@ class Kzg:
         of (cells, proofs) tuples or Error; blobs and index_lists of different lengths raise BadArgs."""
         return Kzg._cells_at(blobs, index_lists, s, True, True)
 
+    # ---- openings of blobs at chosen points (compute_kzg_proofs_at): every (blob, point) pair through its own quotient and one MSM ----
+    @staticmethod
+    def compute_kzg_proofs_at_many(blobs, point_lists, s, proofs=True, ys=True):
+        """One independent compute_kzg_proofs_at per blob, each with its own list of points (32-byte big-endian field elements; the list may be
+        empty), in one call: the blob is handed over once however many openings it gets.  Returns (proofs, ys, statuses): per blob the list of
+        its KzgProof and of its Bytes32 y = p(z) in the order of its points -- None for a part that was not asked for (proofs=False runs no
+        MSM) and for a blob whose status is not 0 -- and the blobs' status codes.  blobs and point_lists of different lengths raise BadArgs,
+        a failure of the whole call raises."""
+        bl = [_b(x, Blob) for x in blobs]
+        lists = [[_b(z, Bytes32) for z in zs] for zs in point_lists]
+        n = len(bl)
+        if len(lists) != n:
+            raise BadArgs("length mismatch")
+        if not proofs and not ys:
+            raise BadArgs("proofs and ys are both declined")
+        slots = [len(zs) for zs in lists]
+        counts, total = (C.c_size_t * max(n, 1))(*slots), sum(slots)
+        p_out = C.create_string_buffer(48 * max(total, 1)) if proofs else None
+        y_out = C.create_string_buffer(32 * max(total, 1)) if ys else None
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_compute_kzg_proofs_at_many(p_out, y_out, st, b"".join(bl), n, counts, b"".join(z for zs in lists for z in zs), s.handle)
+        if _whole_call_failed(rc, st, n):
+            _check(rc, "compute_kzg_proofs_at_many")
+        praw, yraw = (None if b is None else b.raw for b in (p_out, y_out))
+        res_p, res_y, off = [], [], 0
+        for i, k in enumerate(slots):
+            good = st[i] == 0
+            res_p.append([KzgProof(praw[48 * j:48 * (j + 1)]) for j in range(off, off + k)] if good and praw is not None else None)
+            res_y.append([Bytes32(yraw[32 * j:32 * (j + 1)]) for j in range(off, off + k)] if good and yraw is not None else None)
+            off += k
+        return res_p, res_y, [st[i] for i in range(n)]
+
+    @staticmethod
+    def compute_kzg_proofs_at(blob, zs, s, proofs=True):
+        """([KzgProof], [Bytes32]) of the blob opened at the points zs (any order, repeats allowed, inside the domain or not; at most 4096):
+        entry j is what compute_kzg_proof returns for (blob, zs[j]).  proofs=False returns (None, ys) and runs no MSM.  BadArgs on a field
+        element >= r, a point >= r or more than 4096 points."""
+        res_p, res_y, st = Kzg.compute_kzg_proofs_at_many([blob], [zs], s, proofs=proofs)
+        if st[0] != 0:
+            raise _ERRORS.get(st[0], InternalError)("compute_kzg_proofs_at")
+        return res_p[0], res_y[0]
+
     # ---- chosen cells of recovered blobs (recover_cells_and_kzg_proofs_at): the recovery of recover_cells_and_kzg_proofs, then every wanted
     # (blob, cell) pair through its own quotient and one MSM ----
     @staticmethod
@@ -1226,6 +1268,27 @@ class Kzg:
         st = (C.c_int * max(n, 1))()
         rc = lib().kzg355_compute_cell_kzg_proofs_at_many_device(c_out, p_out, st, d_blobs, n, counts, idx, s.handle)
         return _device_results(rc, st, n, "compute_cell_kzg_proofs_at_many_device", "compute_cell_kzg_proofs_at")
+
+    @staticmethod
+    def compute_kzg_proofs_at_many_device(blobs, n, point_counts, zs, s, proofs_out=None, ys_out=None):
+        """compute_kzg_proofs_at_many of n resident blobs (n * 131072 bytes): blob i is opened at point_counts[i] points, which follow those of
+        blob i - 1 in zs (host: a sequence of 32-byte points, or their bytes joined).  Slot j of the device tensors proofs_out (sum of the
+        counts * 48 bytes) and ys_out (* 32) receives the proof and y of point j of zs; either may be None, not both.  Returns one entry per
+        blob: None, or the Error of that blob (its output slots are then unspecified)."""
+        point_counts = [int(c) for c in point_counts]
+        zz = bytes(zs) if isinstance(zs, (bytes, bytearray)) else b"".join(_b(z, Bytes32) for z in zs)
+        n, message = int(n), "n or a count out of range, or the counts do not add up to the points"
+        if n < 0 or len(point_counts) != n or any(c < 0 or c >= 1 << 64 for c in point_counts) or 32 * sum(point_counts) != len(zz):
+            raise BadArgs(message)
+        if proofs_out is None and ys_out is None:
+            raise BadArgs("proofs_out and ys_out are both missing")
+        total = sum(point_counts)
+        p_out = Kzg._dev(proofs_out, "proofs_out", 48 * total, optional=True)
+        y_out = Kzg._dev(ys_out, "ys_out", 32 * total, optional=True)
+        d_blobs = Kzg._dev(blobs, "blobs", 4096 * 32 * n, optional=n == 0)
+        st = (C.c_int * max(n, 1))()
+        rc = lib().kzg355_compute_kzg_proofs_at_many_device(p_out, y_out, st, d_blobs, n, (C.c_size_t * max(n, 1))(*point_counts), zz, s.handle)
+        return _device_results(rc, st, n, "compute_kzg_proofs_at_many_device", "compute_kzg_proofs_at")
 
     @staticmethod
     def recover_cells_and_kzg_proofs_at_many_sets_device(cell_counts, cell_indices, cells, want_counts, want_indices, s, cells_out=None, proofs_out=None):

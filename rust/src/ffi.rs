@@ -115,6 +115,13 @@ extern "C" {
                                                   cell_counts: *const usize, cell_indices: *const usize, s: *const kzg355_settings) -> c_int;
     pub fn kzg355_compute_cell_kzg_proofs_at_many_device(d_cells_out: *mut u8, d_proofs_out: *mut u8, status: *mut c_int, d_blobs: *const u8, n: usize,
                                                          cell_counts: *const usize, cell_indices: *const usize, s: *const kzg355_settings) -> c_int;
+    // openings of a blob at chosen points, each pair through its own quotient and one MSM: blob i is opened at point_counts[i] points, its points
+    // (32 bytes each) follow those of blob i - 1 in zs, and output slot j receives the proof and y of point j of zs
+    pub fn kzg355_compute_kzg_proofs_at(proofs_out: *mut u8, ys_out: *mut u8, blob: *const u8, zs: *const u8, k: usize, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_compute_kzg_proofs_at_many(proofs_out: *mut u8, ys_out: *mut u8, status: *mut c_int, blobs: *const u8, n: usize,
+                                             point_counts: *const usize, zs: *const u8, s: *const kzg355_settings) -> c_int;
+    pub fn kzg355_compute_kzg_proofs_at_many_device(d_proofs_out: *mut u8, d_ys_out: *mut u8, status: *mut c_int, d_blobs: *const u8, n: usize,
+                                                    point_counts: *const usize, zs: *const u8, s: *const kzg355_settings) -> c_int;
     // chosen cells of recovered blobs and their proofs: the input of recover_cells_and_kzg_proofs_many_sets (blob i known at cell_counts[i] cells),
     // the output of compute_cell_kzg_proofs_at_many (blob i asks for want_counts[i] cells; output slot j belongs to entry j of want_indices)
     pub fn kzg355_recover_cells_and_kzg_proofs_at(cells_out: *mut u8, proofs_out: *mut u8, cell_indices: *const usize, cells: *const u8, n: usize,

@@ -1155,6 +1155,49 @@ impl Kzg {
             .collect())
     }
 
+    /// The blob opened at the points `zs` (any order, repeats allowed, inside the domain or not; at most 4096): entry `j` is what
+    /// `compute_kzg_proof` returns for `(blob, zs[j])`, and the blob is handed over once.
+    pub fn compute_kzg_proofs_at(blob: &Blob, zs: &[Bytes32], s: &KzgSettings) -> Result<(Vec<KzgProof>, Vec<Bytes32>), Error> {
+        let mut res = Self::compute_kzg_proofs_at_many(std::slice::from_ref(blob), &[zs], s)?;
+        res.pop().unwrap_or(Err(Error::InternalError))
+    }
+
+    /// One independent `compute_kzg_proofs_at` per blob, each with its own list of points (which may be empty), in one set of launches.  One
+    /// `Result` per blob; `blobs` and `point_lists` of different lengths are `BadArgs` for the call.
+    pub fn compute_kzg_proofs_at_many(
+        blobs: &[Blob],
+        point_lists: &[&[Bytes32]],
+        s: &KzgSettings,
+    ) -> Result<Vec<Result<(Vec<KzgProof>, Vec<Bytes32>), Error>>, Error> {
+        let n = blobs.len();
+        if point_lists.len() != n {
+            return Err(Error::BadArgs("length mismatch".into()));
+        }
+        let staged = stage_blobs(blobs);
+        let counts: Vec<usize> = point_lists.iter().map(|zs| zs.len()).collect();
+        let z: Vec<u8> = point_lists.iter().flat_map(|zs| zs.iter().flat_map(|x| x.bytes)).collect();
+        let total = z.len() / 32;
+        let mut proofs = vec![0u8; BYTES_PER_PROOF * total.max(1)];
+        let mut ys = vec![0u8; 32 * total.max(1)];
+        let mut st = vec![0i32; n.max(1)];
+        let rc = unsafe {
+            ffi::kzg355_compute_kzg_proofs_at_many(proofs.as_mut_ptr(), ys.as_mut_ptr(), st.as_mut_ptr(), staged.as_ptr(), n, counts.as_ptr(), z.as_ptr(),
+                                                   s.raw)
+        };
+        whole_call(rc, &st[..n], "compute_kzg_proofs_at_many")?;
+        let mut off = 0usize;
+        Ok((0..n)
+            .map(|i| {
+                let (lo, hi) = (off, off + counts[i]);
+                off = hi;
+                check(st[i], "compute_kzg_proofs_at")?;
+                let ps = (lo..hi).map(|j| KzgProof::from(<[u8; BYTES_PER_PROOF]>::try_from(&proofs[48 * j..48 * (j + 1)]).unwrap())).collect();
+                let vs = (lo..hi).map(|j| Bytes32::from(<[u8; 32]>::try_from(&ys[32 * j..32 * (j + 1)]).unwrap())).collect();
+                Ok((ps, vs))
+            })
+            .collect())
+    }
+
     /// `kzg_to_versioned_hash` of EIP-4844 per commitment, on the host: `0x01 || sha256(commitment)[1..]`.  No handle, no device; nothing is validated.
     pub fn kzg_to_versioned_hash_many(commitments: &[KzgCommitment]) -> Result<Vec<Bytes32>, Error> {
         let n = commitments.len();
